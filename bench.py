@@ -13,7 +13,10 @@ For N > 1 the SAME tree is sharded by subtree below stage 2 (18 crown nodes repl
 with one RCCL all-reduce of the cut parents' children sums per iteration => strong scaling.  torch.distributed (gloo) only
 carries the rendezvous, the ncclUniqueId and the timing barriers; the data path is the library's own ncclAllReduce.
 
-Rank 0 prints one JSON line (see README / DESIGN.md for the fields).
+Rank 0 prints one JSON line (see README / DESIGN.md for the fields).  A plain run sets up, warms up, times the K steps and
+prints the headline; --full adds every secondary measurement (PMC passes, the per-launch profile and roofline, repeat
+regions, the structured mode, the other configs, the replay path, shard_ceiling, quasi_newton, the CPU baselines).
+--dump-outputs DIR writes the iterates the timed steps computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -65,7 +68,37 @@ def parse():
     ap.add_argument("--tune-iterations", type=int, default=200, help="N > 1, second worker: iterations per candidate of rn_exchange_autotune")
     ap.add_argument("--allow-oversubscribe", action="store_true", help="rehearsal only: with fewer GPUs than ranks the ranks share devices; RCCL refuses "
                     "that (duplicate GPU), so the exchange falls back to torch.distributed/gloo and the JSON line says so")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="besides the headline, run every secondary measurement: PMC traffic / MFMA passes, the per-launch hipEvent "
+                    "pass (roofline, kernel_classes), repeat regions, the control step, the structured mode, the other configs, the replay path, shard_ceiling, "
+                    "quasi_newton, the CPU baselines.  The options above that tune or skip these apply with --full only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="1 GPU: after the timed steps, write the iterates they computed (what rn_get hands a caller: "
+                    "%s) as DIR/<name>.npy, float64; above %d MB in all, a fixed seeded sample of each" % (", ".join(DUMP_BUFFERS), DUMP_LIMIT >> 20))
+    args = ap.parse_args()
+    if not args.full:   # a plain run: set-up, warm-up, the K timed steps, the result line -- nothing else
+        args.no_traffic = args.no_cpu_baseline = args.dense_only = args.no_shard_ceiling = args.no_quasi_newton = True
+        args.profile_steps, args.repeats, args.other_configs = 0, 0, ""
+    return args
+
+
+DUMP_BUFFERS = ("x", "u", "v", "updXi", "updPsi")
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(s, directory, seed=20260103):
+    """--dump-outputs: the iterates the timed steps left in the context, one DIR/<name>.npy per array (float64, as rn_get returns them).  Above
+    DUMP_LIMIT bytes in all, every array is cut to the same fraction of its entries: a sample drawn with a fixed seed, in index order."""
+    from rapidnet_amd import capi
+
+    ids = {"x": capi.BUF_X, "u": capi.BUF_U, "v": capi.BUF_V, "updXi": capi.BUF_UPD_XI, "updPsi": capi.BUF_UPD_PSI}
+    sizes = {nm: int(s.lib.rn_buffer_size(s.h, ids[nm])) for nm in DUMP_BUFFERS}
+    frac = min(1.0, DUMP_LIMIT / (8.0 * sum(sizes.values())))
+    os.makedirs(directory, exist_ok=True)
+    for nm in DUMP_BUFFERS:
+        a = s.get(ids[nm])
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, int(frac * a.size), replace=False))
+            a = a[idx]
+        np.save(os.path.join(directory, nm + ".npy"), a.astype(np.float64))
 
 
 def _free_port():
@@ -118,7 +151,8 @@ def measure_traffic(args, extra_probe_args=(), launcher_env=False, limit=150.0, 
     if launcher_env:     # called by a rank's supervisor: the probe is a one-process run of its own, not a rank of this job
         env = {k: v for k, v in env.items() if not (k.startswith("TORCHELASTIC_") or k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "GROUP_WORLD_SIZE",
                                                                                                 "ROLE_RANK", "ROLE_WORLD_SIZE", "ROLE_NAME", "MASTER_ADDR", "MASTER_PORT", "RAPIDNET_BENCH_FAULT"))}
-    probe = ["python3", os.path.abspath(__file__), "--traffic-probe", "--workload", args.workload, "--steps", "40", "--warmup", "20"] + list(extra_probe_args)
+    # (--full: the probe keeps its control step -- the launches of k_dual_stage, whose traffic the roofline reports, come from there)
+    probe = ["python3", os.path.abspath(__file__), "--full", "--traffic-probe", "--workload", args.workload, "--steps", "40", "--warmup", "20"] + list(extra_probe_args)
     if precision or args.precision:
         probe += ["--precision", precision or args.precision]
     for kv in args.knob:
@@ -179,7 +213,7 @@ def measure_mfma(args, limit=150.0):
     if exe is None or any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ):
         return {"error": "rocprofv3 not available (or this run is itself being profiled)"}
     tmp = tempfile.mkdtemp(prefix="rn_sq_", dir="/tmp")
-    probe = ["python3", os.path.abspath(__file__), "--traffic-probe", "--structured", "--workload", args.workload, "--steps", "40", "--warmup", "20"]
+    probe = ["python3", os.path.abspath(__file__), "--full", "--traffic-probe", "--structured", "--workload", args.workload, "--steps", "40", "--warmup", "20"]
     for kv in args.knob:
         probe += ["--knob", kv]
     try:
@@ -765,6 +799,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    if args.dump_outputs and (args.gpus > 1 or args.force_shard or args.emulate_world > 0):
+        sys.exit("bench.py: --dump-outputs needs an unsharded run on one GPU")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))     # one child process per rank, started before anything touches the GPU
     if args.worker and os.environ.get("RAPIDNET_BENCH_FAKE_WORKER"):
@@ -903,7 +939,7 @@ def main():
             rccl_library = "unavailable: %s" % e
 
     def run_mode(structured, steps, warmup, profile_steps, repeats=0, problem=problem, tree=tree, precision=precision, workload=args.workload,
-                 control_step=True, cut_stage=cut_stage, fatal=True, alt=False, fused_ab=False):
+                 control_step=True, cut_stage=cut_stage, fatal=True, alt=False, fused_ab=False, dump=None):
         if sharded:
             import torch
         def make_local():
@@ -1040,6 +1076,7 @@ def main():
             while time.perf_counter() - t_ramp < 0.08:
                 iterate(20)
                 s.synchronize()
+            s.apgReset()     # the ramp's length is a matter of time: warm-up and timed steps start from the same iterates in every run
         beat("warm-up (%s)" % workload)
         iterate(warmup)
         barrier()
@@ -1069,6 +1106,8 @@ def main():
             return float(t.item())
 
         dt = max_over_ranks(dt)
+        if dump:
+            dump_outputs(s, dump)
         # the contract's timed region is the one above; `repeats` further regions of the same K steps give its spread
         rep = []
         for _ in range(max(0, repeats)):
@@ -1233,11 +1272,11 @@ def main():
         dist.barrier()
         return
     # headline: the reference's storage model (dense per-node blocks); the structured mode is reported beside it on 1 GPU
-    dense = None if args.structured else run_mode(False, args.steps, args.warmup, args.profile_steps, repeats=args.repeats,
-                                                  fused_ab=not (args.dense_only or args.traffic_probe) and args.workload == "barcelona493")
+    dense = None if args.structured else run_mode(False, args.steps, args.warmup, args.profile_steps, repeats=args.repeats, control_step=args.full,
+                                                  fused_ab=not (args.dense_only or args.traffic_probe) and args.workload == "barcelona493", dump=args.dump_outputs)
     struct, struct_error = None, None
     if args.structured:
-        struct = run_mode(True, args.steps, args.warmup, args.profile_steps, repeats=args.repeats)
+        struct = run_mode(True, args.steps, args.warmup, args.profile_steps, repeats=args.repeats, control_step=args.full, dump=args.dump_outputs)
     elif not sharded and not args.dense_only:
         try:      # the opt-in mode rides along: a failure there is reported in the line, it does not take the headline with it
             # (the headline workload: with the repeat regions and the same-context A/B of the fused walk + dual update, as in the dense run)
@@ -1392,7 +1431,7 @@ def main():
             except Exception as e:   # noqa: BLE001
                 qn = {"error": "%s: %s" % (type(e).__name__, e)}
     same_box = None
-    if sharded and world > 1 and not args.structured and not args.traffic_probe:
+    if sharded and world > 1 and not args.structured and not args.traffic_probe and args.full:
         # the ceiling of THIS box: rank 0 runs its own shard once more with a one-rank communicator (every launch and collective of the sharded path,
         # no wire, no peer to wait for) while the other ranks wait at the barrier below; speedup_vs_shard_ceiling = that time / the measured time
         beat("shard ceiling on this box (rank 0)", 300.0)

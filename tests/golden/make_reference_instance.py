@@ -16,10 +16,13 @@ forecaster/nominalForecast.json are missing):
   forecastor.json  nominal demand = the held prevDemand with a daily profile; nominal prices = the held costAlpha2 (24 x 114)
   prevU            the steady-state control of prevDemand (the held prevU violates the mass balance E u + Ed d = 0 by 4e6)
 The oracle's iterates after k = 1, 10, 100, 500 APG iterations are stored with the inputs (iterates.npz: every 11th entry of
-x, u, y+ (xi and psi parts) and z, and the whole primal-infeasibility history).
+x, u, y+ (xi and psi parts) and z, and the whole primal-infeasibility history).  held_sha256.json holds the SHA-256 of every
+held value the fixture carries (float64 bytes per member), so that the tests check the fixture against the held files without
+reading them.
 
     python tests/golden/make_reference_instance.py      # needs /root/reference; deterministic
 """
+import hashlib
 import json
 import os
 import sys
@@ -35,6 +38,11 @@ SRC = "/root/reference/src/paser/dataSource"
 OUT = os.path.join(ROOT, "tests", "golden", "reference_barcelona30")
 CHECKPOINTS = (1, 10, 100, 500)
 STRIDE = 11
+HELD_CONFIG = ("matL", "matLhat", "costW", "matDiagPrecnd", "currentX", "prevDemand", "stepSize", "costAlpha1")
+
+
+def held_sha256(values):
+    return hashlib.sha256(np.ascontiguousarray(np.asarray(values, float)).tobytes()).hexdigest()
 
 
 def build():
@@ -106,6 +114,11 @@ def main():
     cfg = json.load(open(os.path.join(OUT, "controllerConfig.json")))
     cfg.update({"pathToNetwork": "network.json", "pathToScenarioTree": "scenarioTree.json", "pathToForecaster": "forecastor.json"})
     json.dump(cfg, open(os.path.join(OUT, "controllerConfig.json"), "w"))
+    c = json.load(open(os.path.join(SRC, "controllerConfig32.json")))
+    t = json.load(open(os.path.join(SRC, "scenarioTree65.json")))
+    held = {"controllerConfig32.json": {k: held_sha256(c[k]) for k in HELD_CONFIG}, "scenarioTree65.json": {k: held_sha256(t[k]) for k in t}}
+    with open(os.path.join(OUT, "held_sha256.json"), "w") as f:
+        json.dump(held, f)
     dh, ah = synth.forecast_at(problem["forecast"], 0)
     out = {"dt": np.array([info["dt"]]), "step_times_lipschitz": np.array([info["step_times_lipschitz"]])}
     o = Oracle(problem["network"], problem["tree"], problem["config"])

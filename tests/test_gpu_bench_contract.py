@@ -1,10 +1,12 @@
-"""bench.py's output contract, checked on the GPU box: exactly ONE JSON line on stdout carrying the driver's fields, the
-`roofline` object of the dominant kernel and the `cpu_baseline` object (a short run: 20 timed steps)."""
+"""bench.py's output contract, checked on the GPU box: exactly ONE JSON line on stdout carrying the driver's fields; with --full also the
+`roofline` object of the dominant kernel and the `cpu_baseline` object (a short run: 20 timed steps).  A plain run is the headline alone,
+and --dump-outputs writes the iterates its timed steps computed."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -14,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_prints_one_json_line_with_the_contract_fields():
     # (the default line minus what has tests of its own and takes long here: the 160 GB wide network -- test_gpu_baseline_configs.py -- and the
     #  quasi-Newton loops at full size -- test_gpu_fullsize.py; the round's collection runs the default line as the driver does)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--profile-steps", "10", "--cpu-iterations", "2",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "3", "--profile-steps", "10", "--cpu-iterations", "2",
                         "--other-configs", "barcelona31,barcelona493:f32", "--no-quasi-newton"],
                        cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
@@ -96,6 +98,36 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
     assert d["value"] > 10 * c["value"]                  # north_star: >= 10x the host-CPU baseline at 1 GPU
 
 
+def test_plain_run_times_the_headline_only_and_dumps_its_iterates(tmp_path):
+    """Without --full the line carries the headline and nothing that takes runs of its own; --dump-outputs writes the iterates of the timed
+    path's last step: W + K APG iterations from the initial point, the CPU oracle's iterates after as many."""
+    from oracle.oracle import Oracle
+    from rapidnet_amd import synth
+
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "barcelona31", "--steps", "20", "--warmup", "3",
+                        "--dump-outputs", str(out)], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert p.returncode == 0, p.stderr.decode()[-2000:]
+    lines = [l for l in p.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "apg_iterations_per_sec" and d["unit"] == "iterations/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 20 and d["warmup"] == 3 and abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    for k in ("cpu_baseline", "configs", "structured_mode", "shard_ceiling", "quasi_newton", "replay_path", "fused_walk_dual"):
+        assert k not in d, k
+    assert d["roofline"] is None and d["timing_spread"] is None and not any("PMC" in n_ for n_, _ in d["phases_s"])
+    pr = synth.make_problem("barcelona31")
+    dh, ah = synth.forecast_at(pr["forecast"], 0)
+    o = Oracle(pr["network"], pr["tree"], pr["config"])
+    o.initialise(dh, ah)
+    o.apg(23)
+    assert sorted(f.name for f in out.iterdir()) == ["u.npy", "updPsi.npy", "updXi.npy", "v.npy", "x.npy"]
+    for nm in ("x", "u", "v", "updXi", "updPsi"):
+        a, b = np.load(out / (nm + ".npy")), o.get(nm)
+        assert a.dtype == np.float64 and a.shape == b.shape, nm
+        assert np.abs(a - b).max() <= 1e-9 * np.abs(b).max(), nm
+
+
 def _devices():
     # asked in a child process: importing torch into the process that also drives librapidnet_hip contexts (every other GPU test
     # of the suite) ends in "double free or corruption" at interpreter exit
@@ -109,7 +141,7 @@ def test_gpus_2_spawns_its_own_ranks():
     device -- with a non-zero exit code and no JSON line; with --allow-oversubscribe it rehearses the whole launcher path (two
     processes, gloo rendezvous, rn_create_sharded on both, agreed fallback exchange, max-over-ranks timing) and labels the
     line as a fallback.  With two or more GPUs the plain form simply has to produce a sharded result."""
-    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--profile-steps", "10", "--repeats", "1",
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "10", "--warmup", "2", "--profile-steps", "10", "--repeats", "1",
             "--cpu-iterations", "2"]
     if _devices() >= 2:
         p = subprocess.run(base, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)

@@ -1,5 +1,5 @@
 """Long-run parity on REFERENCE-HELD Barcelona data: tests/golden/reference_barcelona30/, built by
-tests/golden/make_reference_instance.py from /root/reference/src/paser/dataSource/controllerConfig32.json (matL, matLhat,
+tests/golden/make_reference_instance.py from the reference's data files controllerConfig32.json (matL, matLhat,
 costW, matDiagPrecnd, prices, currentX, prevDemand, stepSize 1e-4, maxIterations 500) and scenarioTree65.json (K = 30,
 667 nodes), with only the network and the nominal forecast synthesised (the reference does not hold them).
 
@@ -11,6 +11,8 @@ size (0.25 ... 1 x the held 1e-4), the bounds or the size of the tree errors -- 
 after 500 iterations (primal infeasibility 30-70 of 1700) and the active set keeps changing.  So at 200 ... 500 iterations the
 bound is the oracle's own sensitivity (x 20; measured ratios are at most 3), as for the infeasible synthetic data; 1e-8 is asserted
 directly up to 200 iterations; the table is printed."""
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -63,17 +65,16 @@ def test_fixture_is_the_reference_held_data():
     E = np.array(n["matE"]).reshape(ne, nu, order="F")
     Ed = np.array(n["matEd"]).reshape(ne, nd, order="F")
     assert np.abs(E @ L).max() < 1e-12 and np.abs(E @ Lhat + Ed).max() < 1e-9 * np.abs(Ed).max()   # L = null(E), E Lhat = -Ed
-    if os.path.isdir("/root/reference"):   # the held files, value for value
-        import json
-
-        src = json.load(open("/root/reference/src/paser/dataSource/controllerConfig32.json"))
-        for k in ("matL", "matLhat", "costW", "matDiagPrecnd", "currentX", "prevDemand", "stepSize", "costAlpha1"):
-            ref = src[k]
-            got = c[k] if k != "costAlpha1" else n[k]
-            assert np.array_equal(np.asarray(ref, float), np.asarray(got, float)), k
-        tsrc = json.load(open("/root/reference/src/paser/dataSource/scenarioTree65.json"))
-        for k in tsrc:
-            assert np.array_equal(np.asarray(tsrc[k], float), np.asarray(t[k], float)), k
+    # the held files, value for value: SHA-256 of their members (float64 bytes), recorded by make_reference_instance.py
+    with open(os.path.join(DIR, "held_sha256.json")) as f:
+        held = json.load(f)
+    sha = lambda v: hashlib.sha256(np.ascontiguousarray(np.asarray(v, float)).tobytes()).hexdigest()
+    assert len(held["controllerConfig32.json"]) == 8 and len(held["scenarioTree65.json"]) == len(t)
+    for k, h in held["controllerConfig32.json"].items():
+        got = c[k] if k != "costAlpha1" else n[k]
+        assert sha(got) == h, k
+    for k, h in held["scenarioTree65.json"].items():
+        assert sha(t[k]) == h, k
 
 
 def test_oracle_reproduces_the_committed_iterates():

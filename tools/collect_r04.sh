@@ -6,15 +6,15 @@
 # fp32 on the headline tree, FBE / NAMA timings.  Outputs under gpurun_out/r04/.
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/r04; mkdir -p $O
-python3 bench.py > $O/bench_1gpu.json 2> $O/bench_1gpu.err || { echo "bench failed"; tail -5 $O/bench_1gpu.err; exit 1; }
+python3 bench.py --full > $O/bench_1gpu.json 2> $O/bench_1gpu.err || { echo "bench failed"; tail -5 $O/bench_1gpu.err; exit 1; }
 echo "bench done"
-rm -rf $O/ks1; rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks1 -o k -- python3 bench.py --no-cpu-baseline --no-traffic --other-configs "" > $O/bench_1gpu_under_rocprof.json 2> /dev/null || exit 1
+rm -rf $O/ks1; rocprofv3 --kernel-trace --stats --output-format csv -d $O/ks1 -o k -- python3 bench.py --full --no-cpu-baseline --no-traffic --other-configs "" > $O/bench_1gpu_under_rocprof.json 2> /dev/null || exit 1
 cp $(find $O/ks1 -name k_kernel_stats.csv | head -1) $O/kernel_stats.csv; rm -rf $O/ks1
 echo "kstats done"
 rm -f $O/emulated_shards.jsonl $O/emulated_shards_oneshot.jsonl
 for W in 2 4 8; do
-  python3 bench.py --emulate-world $W --no-cpu-baseline --steps 200 --warmup 20 --other-configs "" 2>/dev/null | grep '"metric"' >> $O/emulated_shards.jsonl
-  python3 bench.py --emulate-world $W --one-shot --no-cpu-baseline --steps 200 --warmup 20 --other-configs "" 2>/dev/null | grep '"metric"' >> $O/emulated_shards_oneshot.jsonl
+  python3 bench.py --full --emulate-world $W --no-cpu-baseline --steps 200 --warmup 20 --other-configs "" 2>/dev/null | grep '"metric"' >> $O/emulated_shards.jsonl
+  python3 bench.py --full --emulate-world $W --one-shot --no-cpu-baseline --steps 200 --warmup 20 --other-configs "" 2>/dev/null | grep '"metric"' >> $O/emulated_shards_oneshot.jsonl
 done
 for mode in rccl oneshot; do
   flag=""; [ $mode = oneshot ] && flag="--one-shot"
@@ -22,10 +22,10 @@ for mode in rccl oneshot; do
   cp $(find $O/ks8 -name k_kernel_stats.csv | head -1) $O/emulated_shard8_${mode}_kernel_stats.csv; rm -rf $O/ks8
 done
 echo "shards done"
-python3 bench.py --gpus 2 --steps 20 --warmup 5 --allow-oversubscribe --cpu-iterations 5 > $O/bench_2ranks_oversubscribed_rehearsal.json 2> $O/rehearsal.err; echo "rehearsal rc=$?"
+python3 bench.py --full --gpus 2 --steps 20 --warmup 5 --allow-oversubscribe --cpu-iterations 5 > $O/bench_2ranks_oversubscribed_rehearsal.json 2> $O/rehearsal.err; echo "rehearsal rc=$?"
 python3 bench.py --gpus 2 --steps 20 --warmup 5 > $O/bench_2ranks_strict.out 2> $O/bench_2ranks_strict.err; echo "strict rc=$?" | tee -a $O/bench_2ranks_strict.out; tail -3 $O/bench_2ranks_strict.err >> $O/bench_2ranks_strict.out
 ( time RAPIDNET_BENCH_FAULT=before_comm_init:1 python3 bench.py --gpus 2 --steps 20 --warmup 5 --allow-oversubscribe --no-cpu-baseline --other-configs "" ) > $O/bench_2ranks_fault.out 2> $O/bench_2ranks_fault.err; echo "fault rc=$?" | tee -a $O/bench_2ranks_fault.out; grep -h "injected\|real\|giving up\|rank" $O/bench_2ranks_fault.err | tail -8 >> $O/bench_2ranks_fault.out
-python3 bench.py --precision f32 --other-configs "" --cpu-iterations 5 > $O/barcelona493_f32_1gpu.json 2>/dev/null
+python3 bench.py --full --precision f32 --other-configs "" --cpu-iterations 5 > $O/barcelona493_f32_1gpu.json 2>/dev/null
 python3 tools/time_fbe_nama.py barcelona493 40 > $O/fbe_nama_timing.jsonl 2>/dev/null
 for alg in fbe nama; do
   rm -rf $O/ksf; rocprofv3 --kernel-trace --stats --output-format csv -d $O/ksf -o k -- python3 tools/profile_fbe.py barcelona493 40 0 $alg > $O/${alg}_profile_run.txt 2>/dev/null || exit 1

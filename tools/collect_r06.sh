@@ -15,13 +15,13 @@ ks() {   # ks <tag> <bench args...>: rocprofv3 kernel stats of one bench.py run 
 for step in "$@"; do
   case $step in
     tests)   timeout -k 10 840 python -m pytest tests -x -q -m gpu --durations=80 > $O/tests.log 2>&1; rc=$?; tail -5 $O/tests.log; [ $rc -eq 0 ] || exit $rc ;;
-    bench)   timeout -k 10 560 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; rc=$?; tail -c 400 $O/bench.json; [ $rc -eq 0 ] || { tail -20 $O/bench.err; exit $rc; } ;;
+    bench)   timeout -k 10 560 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench.json 2> $O/bench.err; rc=$?; tail -c 400 $O/bench.json; [ $rc -eq 0 ] || { tail -20 $O/bench.err; exit $rc; } ;;
     kstats)  ks dense --dense-only || exit 1 ;;
     kstats_struct) ks structured --structured || exit 1 ;;
     kstats_b31) ks b31 --workload barcelona31 --dense-only || exit 1; ks b31_structured --workload barcelona31 --structured || exit 1 ;;
     kstats_shard8) ks shard8 --emulate-world 8 --dense-only || exit 1 ;;
     n2)      # the two-rank rehearsal on ONE GPU (RCCL refuses the duplicate device: agreed fallback exchange) under the budgeted supervisors
-             timeout -k 10 420 python bench.py --gpus 2 --steps 10 --warmup 2 --profile-steps 10 --repeats 1 --cpu-iterations 3 --allow-oversubscribe --no-traffic --other-configs "" --time-budget 300 > $O/n2.json 2> $O/n2.err; echo "rc=$?"
+             timeout -k 10 420 python bench.py --full --gpus 2 --steps 10 --warmup 2 --profile-steps 10 --repeats 1 --cpu-iterations 3 --allow-oversubscribe --no-traffic --other-configs "" --time-budget 300 > $O/n2.json 2> $O/n2.err; echo "rc=$?"
              grep "supervisor" $O/n2.err | tail -20; tail -c 600 $O/n2.json ;;
     guard)   # whole test files under the buffer guard (RAPIDNET_GUARD=1: red zones + NaN poison) in one process
              timeout -k 10 1000 python tools/guard_suite.py -m gpu tests/test_gpu_slab_kernels.py tests/test_gpu_sharded_batched.py tests/test_gpu_fbe_nama.py \

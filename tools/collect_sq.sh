@@ -8,7 +8,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=$PWD/gpurun_out/r05; mkdir -p $O
 TAG=${1:+_$1}
 export TMPDIR=/tmp
-ARGS="--steps 40 --warmup 5 --no-cpu-baseline --no-traffic --other-configs= --profile-steps 0 --repeats 0 --no-shard-ceiling"
+ARGS="--full --steps 40 --warmup 5 --no-cpu-baseline --no-traffic --other-configs= --profile-steps 0 --repeats 0 --no-shard-ceiling"
 P1="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_WAVES"
 P2="SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU"
 i=0
