@@ -183,7 +183,7 @@
     }
     // SmpcController::computeHessianOracalGlobalFbe (:884-1055): the tree sweep with sigma = 0 and no affine terms
     int hessian_sweep(const T *in) {
-        return launch_sweep(0, in);
+        return launch_sweep(nullptr, 0, in);
     }
     int hessian_oracle() override {   // input = what devPtrVecHessianOracleXi/Psi point at (:356-357, :408-409)
         RN_FBE_READY("rn_compute_hessian_oracle")
@@ -543,7 +543,7 @@
             // the direction's correction (:1338-1340) only needs the residual.  So the correction comes first and both sweeps share one
             // pass over the operator blocks -- a third of the iteration's HBM traffic; same values as the sequence below.
             hipLaunchKernelGGL(k_axpby<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, d_dir, d_dir, d_res, (T)1, (T)-stepSize, n);   // :1338-1340
-            if (int rc = launch_sweep(0, d_res, true, d_dir)) return rc;                       // :1331 and :1341-1345
+            if (int rc = launch_sweep(nullptr, 0, d_res, true, d_dir)) return rc;                       // :1331 and :1341-1345
             TrialArgs<T> g{d_x, d_u, p_acc_view, d_hx, d_xdirB, d_udirB, d_res, d_hxDirB, (long long)d.nodes * d.nx, (long long)d.nodes * d.nu, n, (T)stepSize};
             hipLaunchKernelGGL(k_trial_step<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, g);                                      // :1332-1337
             sweepPairs++;

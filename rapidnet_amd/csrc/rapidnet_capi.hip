@@ -19,6 +19,7 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/rapidnet.h"
@@ -349,18 +350,38 @@ struct Ctx : CtxBase {
     int opsMode = RN_OPS_AUTO, structured = 1, warmStart = 0;
     struct SavedSystem { std::vector<double> B, Gd, L, Lhat, W, diag, xmin, xmax, xsafe, umin, umax, alpha1; } h_sys;   // the factor step's inputs (AUTO: for the dense re-factor)
     int optimistic = 1;      // multi-GPU: 1 = one collective per iteration + verification, 0 = exact two-collective path
-    bool pendingFin = false; // optimistic exchange: the previous iteration's bookkeeping has not been launched yet (it rides in the next k_cut_partial_sums)
-    bool carryTail = false;  // the cut payload carries 2 extra reals (rank-local dist^2 of the previous iteration)
+    // What one iteration of an rn_apg_iterate batch hands to the next: run_batch owns it, launch_sweep and launch_dual_main read and consume
+    // it (nullptr: a sweep outside a batch -- the step-wise API, the FBE / NAMA Hessian sweeps, rn_debug_sweep_phase).  A value-initialised
+    // Batch is the state between batches: every flag is false at each batch boundary on the success path (checked below, flag by flag),
+    // so whatever a batch abandoned half-way held goes away with it.
+    struct Batch {
+        bool optimistic = false;  // prox as a pure projection, verified once per batch (and the walk may leave Hx unscaled); else exact
+        bool sharded = false;     // has_comm() && cutStage > 0: the cut payload is all-reduced (or sent one-shot) every iteration
+        // the previous iteration's bookkeeping rides in this sweep's first chain / cut launch.  Set after every iteration but the last,
+        // whose bookkeeping has a launch of its own (k_finalize_optimistic): false at the end of a batch
+        bool pendingFin = false;
+        // the chain walk of the NEXT sweep was done by the last fused launch (k_down_chain_dual UPLIN).  Set only when !fuseMat, i.e. never
+        // by the last iteration, and cleared by every sweep: false at the end of a batch
+        bool upDone = false;
+        // d_hx holds the primal values of every node (k_down_chain UNSC): the dual update applies sqrt(p_i) d_k (k_dual_stage SCALE).  Set
+        // only by a sweep that writes no primal (not the last iteration), cleared by the same iteration's launch_dual_main
+        bool hxUnscaled = false;
+        // the fused walk + dual update (k_down_chain_dual): requested before a sweep and cleared after it; fuseDone is the sweep's answer,
+        // cleared by the iteration that reads it.  fuseMat / fuseArgs / fuseLn are the request's arguments, read only while fuseReq is set
+        bool fuseReq = false, fuseDone = false, fuseMat = false;
+        DualArgs<T> fuseArgs{};
+        double fuseLn = 0.0;
+        // an optimistic sharded batch: the cut payload carries 2 extra reals (rank-local dist^2 of the previous iteration)
+        bool carry_tail() const { return optimistic && sharded; }
+    };
     T *d_ck[3] = {nullptr, nullptr, nullptr};   // checkpoint of (y, y+, w) for the exact fallback
     long fallbacks = 0;          // optimistic batches that had to be replayed through the exact path
     long optBatches = 0, exactBatches = 0;
-    bool inReplay = false;
     int optHold = 0;             // batches still to run through the exact path after a replay (back-off: a state that violates its
                                  // soft bounds would otherwise pay checkpoint + replay on every batch of every control step)
     std::vector<double> h_T1, h_T2, h_Lt;   // zero-padded (rows % 16, cols % 4) copies for the MFMA GEMMs
     int chainStage = 0;
     int *h_verdict = nullptr;    // host-mapped word the last launch of a single-GPU optimistic batch writes the batch's verdict into (nullptr: not granted -- a copy is used)
-    bool hxUnscaled = false;     // d_hx holds the primal values of every node (k_down_chain<T, true>): the next dual update applies sqrt(p_i) d_k (k_dual_stage SCALE)
     bool unscaled_on() const { return knob[RN_KNOB_UNSCALED_WALK] != 0; }   // inner iterations of optimistic batches take that pair of kernels (default on)
     // rn_debug_set_knob (include/rapidnet_debug.h): launch-shape choices the library otherwise makes by problem size, forced by tests and A/B tools
     // on trees that would not take them by themselves; -1 = the library's own choice.  Before the factor step only.
@@ -376,7 +397,6 @@ struct Ctx : CtxBase {
         const long long total = ntot();
         const int blocks = (int)std::min<long long>((total + ELT_THREADS - 1) / ELT_THREADS, (long long)numCUs * 16);
         hipLaunchKernelGGL(k_hx_scale<T>, dim3(blocks), dim3(ELT_THREADS), 0, stream, d_hx, d_sqrtp, d_dy, d_stageOf, ny, total);
-        hxUnscaled = false;
     }
     T *d_lo = nullptr, *d_hi = nullptr, *d_z = nullptr, *d_res = nullptr;
     T *d_ybuf[2] = {nullptr, nullptr}, *d_wbuf[2] = {nullptr, nullptr};
@@ -608,7 +628,7 @@ struct Ctx : CtxBase {
         return upload(dst, tmp.data(), tmp.size());
     }
     TreeDev<T> tree_dev() const { return TreeDev<T>{d_stageCum, d_parent, d_childStart, d_childCount, d_stageOf, d_sqrtp, d_prob, d_dy}; }
-    SweepArgs<T> sweep_args() const {
+    SweepArgs<T> sweep_args(const Batch &b) const {
         SweepArgs<T> a{};
         a.tr = tree_dev();
         a.nx = d.nx; a.nu = d.nu; a.nv = d.nv; a.ny = ny; a.LD = LD; a.strideA = strideA; a.N = d.N; a.nodes = d.nodes;
@@ -624,7 +644,7 @@ struct Ctx : CtxBase {
         a.w = p_acc;
         a.my = d_my; a.my2 = d_my2; a.splitFirst = (splitFirst >= 0 && !structured) ? splitFirst : d.nodes; a.qa = d_qa; a.sk = d_sk; a.rkq = d_rkq; a.v = d_v; a.lvb = d_lvb; a.eb = d_eb; a.bw0 = d_bw0; a.bw = d_bw;
         a.x = d_x; a.u = d_u; a.hx = d_hx;
-        a.distTail = (carryTail && a.cutSums) ? d_cut + cut_tail_offset() : nullptr;
+        a.distTail = (b.carry_tail() && a.cutSums) ? d_cut + cut_tail_offset() : nullptr;
         a.thrX = penX / stepSize; a.thrS = penXs / stepSize; a.iterState = d_state;
         a.writePrimal = 1;
         a.chain0 = h_stageCum[a.chainStage]; a.chainAnc = chainAncStage == a.chainStage ? d_chainAnc : nullptr;
@@ -1321,8 +1341,12 @@ struct Ctx : CtxBase {
     // ONE pass over the operator blocks (k_stream_gemv NR = 2); the vector recursions and shared-operator products then run once per
     // right-hand side.  The first sweep's results go to the pair buffers (d_xdirB, d_udirB, d_hxDirB), the second's where a Hessian
     // sweep always leaves them (d_xdir, d_udir, d_hxDir).  Bitwise the results of two launch_sweep calls.
-    int launch_sweep(int phase = 0, const T *hessianInput = nullptr, bool primalOut = true, const T *hessianInput2 = nullptr, bool allowPending = false) {
-        SweepArgs<T> a = sweep_args();
+    // batch: the rn_apg_iterate batch this sweep is an iteration of (nullptr: none -- the sweep then reads and writes a batch of its own, in which
+    // every flag is false)
+    int launch_sweep(Batch *batch, int phase = 0, const T *hessianInput = nullptr, bool primalOut = true, const T *hessianInput2 = nullptr) {
+        Batch none{};
+        Batch &bt = batch ? *batch : none;
+        SweepArgs<T> a = sweep_args(bt);
         a.writePrimal = primalOut ? 1 : 0;
         if (vPending) { if (hessianInput) { if (int rc = v_flush()) return rc; } else vPending = false; }      // (see v_flush)
         if (hessianInput) {
@@ -1339,12 +1363,12 @@ struct Ctx : CtxBase {
         RN_CHECK(phase == 0 || a.cutSums, RN_E_STATE, "rn_debug_sweep_phase needs rn_set_cut_stage and nranks > 1");
         // one-shot exchange (inside rn_apg_iterate batches only): the launch that produces the cut parents' local sums pushes them
         // to every peer, the crown launch gathers them -- no collective in between
-        const bool oneShot = transport == 1 && peerReady && inBatch && phase == 0 && a.cutSums != nullptr && hessianInput == nullptr;
+        const bool oneShot = transport == 1 && peerReady && batch && phase == 0 && a.cutSums != nullptr && hessianInput == nullptr;
         if (oneShot) {
             // 0 is the "never written" tag; the wrap skips TWO values (... fffffffe, ffffffff, 2, 3 ...) so that the parity -- which of the
             // two inbox buffers an exchange uses -- keeps alternating (the tag 2 of four billion exchanges ago is long overwritten)
             if (++peerSeq == 0) peerSeq = 2;
-            a.peer = h_peer; a.peerSeq = peerSeq; a.peerTail = (pendingFin && carryTail) ? 1 : 0;
+            a.peer = h_peer; a.peerSeq = peerSeq; a.peerTail = (bt.pendingFin && bt.carry_tail()) ? 1 : 0;
         }
         const int nx = d.nx, nu = d.nu, nv = d.nv, cs = a.chainStage;
         auto nk = [&](int k) { return h_stageCum[k + 1] - h_stageCum[k]; };
@@ -1373,8 +1397,8 @@ struct Ctx : CtxBase {
         // one-shot exchange: gathered by the launch that produces the cut parents' sums, every parent's workgroup its own
         auto helpers = [&](SweepArgs<T> &a) -> int {
         e1 = prof_begin(1);
-        const bool rodeUp = upDone && a.lin && phase == 0 && !hessianInput;
-        upDone = false;
+        const bool rodeUp = bt.upDone && a.lin && phase == 0 && !hessianInput;
+        bt.upDone = false;
         FinArgs linFin{};
         // (2) leaf-to-root vector recursion: chains in one launch, crown stage by stage
         // sharded, cut right above the chains, few local chains per cut parent: one launch does the chain walks AND the cut
@@ -1383,25 +1407,25 @@ struct Ctx : CtxBase {
         if (mergedCut) {
             const int k = cutStage - 1, lanesPer = up_cut_lanes();
             FinArgs fin{};
-            if (pendingFin) fin = FinArgs{d_partials, main_partials(), d_state, (void *)(d_cut + cut_tail_offset()), d_hist, d_histParts, histCap, -1.0, -1.0};
+            if (bt.pendingFin) fin = FinArgs{d_partials, main_partials(), d_state, (void *)(d_cut + cut_tail_offset()), d_hist, d_histParts, histCap, -1.0, -1.0};
             const size_t ldsCut = (size_t)(UPCUT_THREADS / lanesPer) * (nv + 2 * nx) * sizeof(T);
-            const int grid = nk(k) + (pendingFin ? 1 : 0);
+            const int grid = nk(k) + (bt.pendingFin ? 1 : 0);
             if (oneShot) {
                 if (a.splitFirst < d.nodes) hipLaunchKernelGGL((k_up_chain_cut<T, true, true>), dim3(grid), dim3(UPCUT_THREADS), ldsCut, stream, a, d_cut, nk(k), lanesPer, fin);
                 else hipLaunchKernelGGL((k_up_chain_cut<T, false, true>), dim3(grid), dim3(UPCUT_THREADS), ldsCut, stream, a, d_cut, nk(k), lanesPer, fin);
                 a.peer.nranks = 0;      // d_cut holds the all-rank sums: every later launch of this sweep is the collective path's
             } else if (a.splitFirst < d.nodes) hipLaunchKernelGGL((k_up_chain_cut<T, true>), dim3(grid), dim3(UPCUT_THREADS), ldsCut, stream, a, d_cut, nk(k), lanesPer, fin);
             else hipLaunchKernelGGL((k_up_chain_cut<T, false>), dim3(grid), dim3(UPCUT_THREADS), ldsCut, stream, a, d_cut, nk(k), lanesPer, fin);
-            pendingFin = false;
+            bt.pendingFin = false;
         } else if (phase != 2) {
             // single-GPU optimistic bookkeeping: the previous iteration's fold / history entry / distance check rides here
             FinArgs fin{};
-            const bool ride = pendingFin && !a.cutSums;
+            const bool ride = bt.pendingFin && !a.cutSums;
             if (rodeUp) {
                 // the chain walk of this sweep rode in the previous iteration's fused walk + dual update; the bookkeeping goes with the first crown launch
-                if (ride) { linFin = FinArgs{d_partials, main_partials(), d_state, nullptr, d_hist, d_histParts, histCap, penX / stepSize, penXs / stepSize}; pendingFin = false; }
+                if (ride) { linFin = FinArgs{d_partials, main_partials(), d_state, nullptr, d_hist, d_histParts, histCap, penX / stepSize, penXs / stepSize}; bt.pendingFin = false; }
             } else {
-            if (ride) { fin = FinArgs{d_partials, main_partials(), d_state, nullptr, d_hist, d_histParts, histCap, penX / stepSize, penXs / stepSize}; pendingFin = false; }
+            if (ride) { fin = FinArgs{d_partials, main_partials(), d_state, nullptr, d_hist, d_histParts, histCap, penX / stepSize, penXs / stepSize}; bt.pendingFin = false; }
             if (a.lin) hipLaunchKernelGGL(k_up_chain_lin<T>, dim3(a.K + (ride ? 1 : 0)), dim3(CHAIN_THREADS), 0, stream, a, fin);
             else if (a.splitFirst < d.nodes) hipLaunchKernelGGL((k_up_chain<T, true>), dim3(a.K + (ride ? 1 : 0)), dim3(CHAIN_THREADS), 0, stream, a, fin);
             else hipLaunchKernelGGL((k_up_chain<T, false>), dim3(a.K + (ride ? 1 : 0)), dim3(CHAIN_THREADS), 0, stream, a, fin);
@@ -1414,17 +1438,17 @@ struct Ctx : CtxBase {
             // optimistic exchange: the bookkeeping of the previous iteration's dual update rides in this launch
             if (!mergedCut) {   // (k_up_chain_cut has already left the payload in d_cut)
                 FinArgs fin{};
-                if (pendingFin) fin = FinArgs{d_partials, main_partials(), d_state, (void *)(d_cut + cut_tail_offset()), d_hist, d_histParts, histCap, -1.0, -1.0};
+                if (bt.pendingFin) fin = FinArgs{d_partials, main_partials(), d_state, (void *)(d_cut + cut_tail_offset()), d_hist, d_histParts, histCap, -1.0, -1.0};
                 if (oneShot) {
-                    hipLaunchKernelGGL((k_cut_partial_sums<T, true>), dim3(nk(k) + (pendingFin ? 1 : 0)), dim3(CUT_THREADS), 0, stream, a, d_cut, nk(k), fin);
+                    hipLaunchKernelGGL((k_cut_partial_sums<T, true>), dim3(nk(k) + (bt.pendingFin ? 1 : 0)), dim3(CUT_THREADS), 0, stream, a, d_cut, nk(k), fin);
                     a.peer.nranks = 0;      // d_cut holds the all-rank sums
-                } else hipLaunchKernelGGL((k_cut_partial_sums<T, false>), dim3(nk(k) + (pendingFin ? 1 : 0)), dim3(CUT_THREADS), 0, stream, a, d_cut, nk(k), fin);
-                pendingFin = false;
+                } else hipLaunchKernelGGL((k_cut_partial_sums<T, false>), dim3(nk(k) + (bt.pendingFin ? 1 : 0)), dim3(CUT_THREADS), 0, stream, a, d_cut, nk(k), fin);
+                bt.pendingFin = false;
             }
             if (phase == 1 || !has_comm()) return RN_OK;     // emulation, or a single-rank "sharded" run
             if (oneShot) return RN_OK;                       // the payload has gone to the peers' inboxes straight from the kernel
             const size_t cnt = (size_t)nk(k) * (nv + 2 * nx);
-            return all_reduce(d_cut, cnt + (carryTail ? 2 : 0), sizeof(T) == 8, "ncclAllReduce(cut payload)");
+            return all_reduce(d_cut, cnt + (bt.carry_tail() ? 2 : 0), sizeof(T) == 8, "ncclAllReduce(cut payload)");
         };
         // the root's own recursion step is folded into workgroup 0 of the v / Lv launch (one launch less) whenever that
         // launch is the slab kernel and stage 0 is not the multi-GPU exchange stage (single GPU: also when the root IS the whole crown --
@@ -1469,20 +1493,20 @@ struct Ctx : CtxBase {
         const int split = fuse_split();                           // workgroups per chain of the fused launch
         const int fuseGrid = a.K * split + nCrownWg;
         // (every workgroup leaves one entry in d_partials: trees with more chains than it holds take the two launches)
-        if (fuseReq && foldCrown && phase == 0 && !hessianInput && fuseLds <= 64 * 1024 && fuseGrid <= std::max(ELT_MAX_BLOCKS, RN_DUAL_STAGE_MAX_BLOCKS)) {
+        if (bt.fuseReq && foldCrown && phase == 0 && !hessianInput && fuseLds <= 64 * 1024 && fuseGrid <= std::max(ELT_MAX_BLOCKS, RN_DUAL_STAGE_MAX_BLOCKS)) {
             // structured mode, linear form, inner iteration of a batch: the NEXT sweep's chain walk rides in this launch (phase C) when that sweep
             // has a crown launch to host the bookkeeping workgroup the chain walk otherwise carries (one workgroup per chain only: the walk needs the chain's rows in one tile)
-            const bool upRide = a.lin && !fuseMat && foldCrown == 1 && split == 1 && (cs - 1 >= (foldRoot ? 1 : 0)) && knob[RN_KNOB_STRUCT_LINEAR] != 2;
-            if (upRide) { hipLaunchKernelGGL((k_down_chain_dual<T, false, true>), dim3(fuseGrid), dim3(CHAIN_THREADS), fuseLds, stream, a, foldCrown, fuseArgs, fuseLn, 1); upDone = true; }
-            else if (fuseMat) hipLaunchKernelGGL((k_down_chain_dual<T, true>), dim3(fuseGrid), dim3(CHAIN_THREADS), fuseLds, stream, a, foldCrown, fuseArgs, fuseLn, split);
-            else hipLaunchKernelGGL((k_down_chain_dual<T, false>), dim3(fuseGrid), dim3(CHAIN_THREADS), fuseLds, stream, a, foldCrown, fuseArgs, fuseLn, split);
-            fuseDone = true; mainPartials = fuseGrid;
+            const bool upRide = a.lin && !bt.fuseMat && foldCrown == 1 && split == 1 && (cs - 1 >= (foldRoot ? 1 : 0)) && knob[RN_KNOB_STRUCT_LINEAR] != 2;
+            if (upRide) { hipLaunchKernelGGL((k_down_chain_dual<T, false, true>), dim3(fuseGrid), dim3(CHAIN_THREADS), fuseLds, stream, a, foldCrown, bt.fuseArgs, bt.fuseLn, 1); bt.upDone = true; }
+            else if (bt.fuseMat) hipLaunchKernelGGL((k_down_chain_dual<T, true>), dim3(fuseGrid), dim3(CHAIN_THREADS), fuseLds, stream, a, foldCrown, bt.fuseArgs, bt.fuseLn, split);
+            else hipLaunchKernelGGL((k_down_chain_dual<T, false>), dim3(fuseGrid), dim3(CHAIN_THREADS), fuseLds, stream, a, foldCrown, bt.fuseArgs, bt.fuseLn, split);
+            bt.fuseDone = true; mainPartials = fuseGrid;
         } else
         {
             // inner iterations of an optimistic batch whose dual update is the stage-tiled kernel reading w: the walk leaves the primal values and
             // the dual update scales them (k_down_chain UNSC / k_dual_stage SCALE: the walk requests no preconditioner entries; bitwise the same Hx)
-            const bool unsc = allowPending && !a.writePrimal && phase == 0 && !hessianInput && foldCrown && dualU != 0 && a.hx == d_hx && unscaled_on();
-            if (unsc) { hipLaunchKernelGGL((k_down_chain<T, true, RN_DOWN_PF_UNSC>), dim3(downGrid), dim3(CHAIN_THREADS), 0, stream, a, foldCrown); hxUnscaled = true; }
+            const bool unsc = bt.optimistic && !a.writePrimal && phase == 0 && !hessianInput && foldCrown && dualU != 0 && a.hx == d_hx && unscaled_on();
+            if (unsc) { hipLaunchKernelGGL((k_down_chain<T, true, RN_DOWN_PF_UNSC>), dim3(downGrid), dim3(CHAIN_THREADS), 0, stream, a, foldCrown); bt.hxUnscaled = true; }
             else hipLaunchKernelGGL((k_down_chain<T, false>), dim3(downGrid), dim3(CHAIN_THREADS), 0, stream, a, foldCrown);
         }
         prof_end(e1);
@@ -1548,7 +1572,8 @@ struct Ctx : CtxBase {
     }
     // main pass of the fused dual update (prox as a pure projection, residual, dual update, arg-max partials, next
     // extrapolation); `flat` forces the grid-stride kernel (eltBlocks partials), which the exact multi-GPU path folds
-    void launch_dual_main(const DualArgs<T> &a, bool materialize, bool flat = false) {
+    void launch_dual_main(Batch &b, const DualArgs<T> &a, bool materialize, bool flat) {
+        const bool hxUnscaled = std::exchange(b.hxUnscaled, false);
         if (flat || dualU == 0) {
             if (hxUnscaled) hx_scale_now();
             if (materialize) hipLaunchKernelGGL((k_dual_fused<T, true, false>), dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, a);
@@ -1562,7 +1587,6 @@ struct Ctx : CtxBase {
         if (hxUnscaled && !materialize) {   // unscaled walk: Hx = sqrt(p_i) d_k * (primal value) is formed here
             if (dualU == 1) hipLaunchKernelGGL((k_dual_stage<T, false, 1, true>), dim3(dualBlocks), dim3(ELT_THREADS), 0, stream, a, g);
             else hipLaunchKernelGGL((k_dual_stage<T, false, 2, true>), dim3(dualBlocks), dim3(ELT_THREADS), 0, stream, a, g);
-            hxUnscaled = false;
             return;
         }
         if (hxUnscaled) hx_scale_now();
@@ -1627,7 +1651,7 @@ struct Ctx : CtxBase {
         RN_HIP(hipMemsetAsync(d_state, 0, sizeof(IterState), stream));
         p_xi = d_ybuf[0]; p_upd = d_ybuf[1]; p_acc = d_wbuf[0]; p_acc_other = d_wbuf[1]; p_acc_view = p_acc;
         acc_ready = true;  // w_0 = (1+l) 0 - l 0 = 0
-        poisoned = false; carryTail = false; pendingFin = false; hxUnscaled = false; upDone = false;
+        poisoned = false;
         h_it = 0;      // (the lambda table is the same fixed sequence after every restart: kept, with its device copy)
         return ensure_tables(0);
     }
@@ -1642,65 +1666,6 @@ struct Ctx : CtxBase {
     }
     int set_warm_start(int on) override { warmStart = on ? 1 : 0; return RN_OK; }
     size_t cut_tail_offset() const { return (size_t)(h_stageCum[cutStage] - h_stageCum[cutStage - 1]) * (d.nv + 2 * d.nx); }
-    // Multi-GPU, optimistic exchange: ONE collective per iteration.  The prox runs as a pure projection (what happens
-    // unless a tree-global distance exceeds gamma/lambda, SmpcController.cu:793/811); every rank's dist^2 of iteration t
-    // rides in the tail of iteration t+1's cut all-reduce and is checked on the device.  If a threshold was ever
-    // exceeded, the batch is replayed from a checkpoint with the exact two-collective path.  Results are exact either way.
-    int apg_iterate_optimistic(int n, double *primalInfs) {
-        const int first = h_it;
-        for (int i = 0; i < 3; i++) if (!d_ck[i]) { if (int rc = dalloc(&d_ck[i], (size_t)ntot())) return rc; }
-        if (int rc = ensure_tables(h_it + n)) return rc;
-        // checkpoint
-        const size_t tail = cut_tail_offset();
-        if (int rc = batch_open(d_cut + tail)) return fail_batch(rc);  // checkpoint of (y, y+, w), the payload's dist^2 tail and the verdict flag cleared: one launch
-        const IterSave saved = save_iterates();
-        carryTail = true; inBatch = true;
-        for (int k = 0; k < n; k++) {
-            if (!acc_ready) {
-                hipLaunchKernelGGL(k_extrapolate<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, p_acc, p_xi, p_upd, (T)h_lam[h_it], ntot());
-                acc_ready = true;
-            }
-            fuseReq = fuse_want(); fuseDone = false;
-            if (fuseReq) { fuseArgs = dual_args(); fuseMat = k == n - 1; fuseLn = h_lam[h_it + 1]; }
-            if (int rc = launch_sweep(0, nullptr, k == n - 1, nullptr, true)) { carryTail = false; pendingFin = false; fuseReq = false; return fail_batch(rc); }
-            fuseReq = false;
-            DualArgs<T> a = dual_args();
-            hipEvent_t e2 = prof_begin(2);
-            if (!fuseDone) launch_dual_main(a, k == n - 1, false);
-            prof_end(e2);
-            // bookkeeping of this iteration: folded into the next iteration's k_cut_partial_sums; the last one of the
-            // batch gets a launch of its own
-            if (k == n - 1) {
-                hipEvent_t e3 = prof_begin(3);
-                hipLaunchKernelGGL(k_finalize_optimistic<T>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, main_partials(), d_state, d_cut + tail,
-                                   d_hist, d_histParts, histCap, -1.0, -1.0);
-                prof_end(e3);
-            } else pendingFin = true;
-            std::swap(p_xi, p_upd);
-            p_acc_view = p_acc; std::swap(p_acc, p_acc_other);
-            h_it++;
-        }
-        carryTail = false; inBatch = false;
-        if (n > 0) {   // the last iteration's distances: one 2-element all-reduce per BATCH
-            if (int rc = all_reduce(d_cut + tail, 2, sizeof(T) == 8, "ncclAllReduce(dist tail)")) return fail_batch(rc);
-            // one more all-reduce per BATCH (MAX): the ranks agree on the verdict (every rank takes the same replay decision even if
-            // an all-reduce algorithm ever delivered sums that differ in the last bit between ranks) and the batch's history
-            // entries become tree-global (vecPrimalInfs, SmpcController.cu:1521)
-            if (int rc = globalize_history(first, n, d_cut + tail)) return fail_batch(rc);
-        }
-        RN_HIP(hipGetLastError());
-        int violated = 0;
-        if (n > 0) {
-            double votes = 0;
-            RN_HIP(hipMemcpyAsync(&votes, d_histGlob, sizeof(double), hipMemcpyDeviceToHost, stream));
-            RN_HIP(hipStreamSynchronize(stream));
-            violated = votes > 0 ? 1 : 0;
-        } else RN_HIP(hipStreamSynchronize(stream));
-        if (transport == 1 && peerReady) { if (int rc = check_comm_fail()) return fail_batch(rc); }
-        if (violated) return replay_exact(saved, n, primalInfs);
-        if (primalInfs && n > 0) RN_HIP(hipMemcpy(primalInfs, d_hist + first, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-        return RN_OK;
-    }
     // The iterate state a batch starts from, as far as it is not in the checkpoint buffers (d_ck: y, y+, w -- written by batch_open):
     // which buffer plays which role, and the iteration count.  restore_iterates puts a context back there (the replay of a tripped batch;
     // the timing runs of the exchange auto-tuner).
@@ -1717,16 +1682,6 @@ struct Ctx : CtxBase {
         RN_HIP(hipStreamSynchronize(stream));   // (sv.it is the caller's)
         return RN_OK;
     }
-    // an optimistic batch whose verdict says "a threshold was exceeded": the same n iterations once more from the checkpoint, through the exact path
-    int replay_exact(const IterSave &sv, int n, double *primalInfs) {
-        fallbacks++;
-        if (int rc = restore_iterates(sv)) return fail_batch(rc);
-        const int keep = optimistic;
-        optimistic = 0; inReplay = true; optHold = RN_OPT_BACKOFF;
-        const int rc = apg_iterate(n, primalInfs);
-        optimistic = keep; inReplay = false;
-        return rc;
-    }
     int batch_open(T *tail) {
         const long long n = ntot();
         const int blocks = (int)std::max<long long>(1, std::min<long long>((n / (16 / (long long)sizeof(T)) + ELT_THREADS - 1) / ELT_THREADS, (long long)numCUs * 8));
@@ -1734,51 +1689,102 @@ struct Ctx : CtxBase {
         RN_HIP(hipGetLastError());   // a checkpoint that was not taken must not be replayed from
         return RN_OK;
     }
-    // Single GPU, optimistic bookkeeping: the same idea without a collective.  The fused dual update runs the prox as a
-    // pure projection; instead of a decision launch after every iteration (the 64-workgroup fix-up launch, ~5 us that
-    // almost always exits at once) the fold of its partials, the history entry and the distance check of iteration t ride
-    // in k_up_chain of iteration t+1 as one more workgroup.  If a threshold was exceeded anywhere in the batch, the batch
-    // is replayed from its checkpoint through the exact path -- the result is exact either way.
-    int apg_iterate_optimistic_local(int n, double *primalInfs) {
+    // One rn_apg_iterate batch of n iterations.  Exact: every iteration decides on the prox before it finishes its dual update -- single
+    // GPU in the small fix-up launch (decideHere), sharded after an all-reduce of the ranks' dist^2.  Optimistic: the prox runs as a pure
+    // projection (what happens unless a tree-global distance exceeds gamma/lambda, SmpcController.cu:793/811), and instead of a decision
+    // after every iteration the fold of its partials, its history entry and its distance check ride in the next iteration's first chain
+    // launch (single GPU) or cut launch (sharded: every rank's dist^2 rides in the tail of the cut payload -- ONE collective per iteration).
+    // If a threshold was exceeded anywhere in the batch, the batch is replayed from its checkpoint as an exact batch: the result is exact
+    // either way.
+    int run_batch(int n, double *primalInfs, bool optimistic) {
+        Batch b{};
+        b.optimistic = optimistic; b.sharded = has_comm() && cutStage > 0;
         const int first = h_it;
-        for (int i = 0; i < 3; i++) if (!d_ck[i]) { if (int rc = dalloc(&d_ck[i], (size_t)ntot())) return rc; }
+        if (b.optimistic) for (int i = 0; i < 3; i++) if (!d_ck[i]) { if (int rc = dalloc(&d_ck[i], (size_t)ntot())) return rc; }
         if (int rc = ensure_tables(h_it + n)) return rc;
-        if (int rc = batch_open(nullptr)) return fail_batch(rc);       // checkpoint of (y, y+, w) + the verdict flag cleared: one launch
-        const IterSave saved = save_iterates();
+        T *const tail = b.carry_tail() ? d_cut + cut_tail_offset() : nullptr;
+        IterSave saved{};
+        if (b.optimistic) {   // checkpoint of (y, y+, w), the payload's dist^2 tail (sharded) and the verdict flag cleared: one launch
+            if (int rc = batch_open(tail)) return fail_batch(rc);
+            saved = save_iterates();
+        }
         for (int k = 0; k < n; k++) {
-            if (!acc_ready) {
+            const bool last = k == n - 1;
+            if (!acc_ready) {   // re-derive w_t after manual buffer edits (SmpcController.cu:1514)
                 hipLaunchKernelGGL(k_extrapolate<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, p_acc, p_xi, p_upd, (T)h_lam[h_it], ntot());
                 acc_ready = true;
             }
-            fuseReq = fuse_want(); fuseDone = false;
-            if (fuseReq) { fuseArgs = dual_args(); fuseMat = k == n - 1; fuseLn = h_lam[h_it + 1]; }
-            if (int rc = launch_sweep(0, nullptr, k == n - 1, nullptr, true)) { pendingFin = false; fuseReq = false; return fail_batch(rc); }
-            fuseReq = false;
+            b.fuseReq = b.optimistic && fuse_want();
+            if (b.fuseReq) { b.fuseArgs = dual_args(); b.fuseMat = last; b.fuseLn = h_lam[h_it + 1]; }
+            if (int rc = launch_sweep(&b, 0, nullptr, last)) return fail_batch(rc);
+            b.fuseReq = false;
             DualArgs<T> a = dual_args();
             hipEvent_t e2 = prof_begin(2);
-            if (!fuseDone) launch_dual_main(a, k == n - 1, false);
+            // (the exact sharded path's fix-up pass and k_finalize fold eltBlocks partials: the flat kernel)
+            if (!std::exchange(b.fuseDone, false)) launch_dual_main(b, a, last, !b.optimistic && b.sharded);
             prof_end(e2);
-            if (k == n - 1) {   // the last iteration's bookkeeping gets a launch of its own
+            if (b.optimistic && !last) b.pendingFin = true;   // this iteration's bookkeeping rides in the next sweep
+            else {
                 hipEvent_t e3 = prof_begin(3);
-                hipLaunchKernelGGL(k_finalize_optimistic<T>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, main_partials(), d_state, (T *)nullptr,
-                                   d_hist, d_histParts, histCap, penX / stepSize, penXs / stepSize, h_verdict);
+                if (b.optimistic) {   // the batch's last bookkeeping gets a launch of its own
+                    hipLaunchKernelGGL(k_finalize_optimistic<T>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, main_partials(), d_state, tail, d_hist, d_histParts,
+                                       histCap, b.sharded ? -1.0 : penX / stepSize, b.sharded ? -1.0 : penXs / stepSize, b.sharded ? nullptr : h_verdict);
+                } else if (b.sharded) {   // tree-global distances: sum the ranks' dist^2 (2 doubles) before deciding
+                    hipLaunchKernelGGL(k_reduce_dist<>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, eltBlocks, d_dist2);
+                    if (int rc = all_reduce(d_dist2, 2, true, "ncclAllReduce(dist)")) return fail_batch(rc);
+                    hipLaunchKernelGGL(k_decide_from<>, dim3(1), dim3(1), 0, stream, d_dist2, d_state, a.thrX, a.thrS);
+                    if (last) hipLaunchKernelGGL((k_dual_fused<T, true, true>), dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, a);
+                    else hipLaunchKernelGGL((k_dual_fused<T, false, true>), dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, a);
+                    hipLaunchKernelGGL(k_finalize<>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, eltBlocks, d_state, d_hist, d_histParts, histCap);
+                } else {   // single GPU: the (small) fix-up launch also decides and does the bookkeeping (kernels.hpp, decideHere)
+                    a.finalizedEarly = 1;
+                    a.decideHere = 1; a.itHost = h_it; a.nMain = main_partials(); a.mainPartials = d_partials; a.partials = d_partials2;
+                    const int fixBlocks = std::min(eltBlocks, RN_FIXUP_BLOCKS);
+                    if (last) hipLaunchKernelGGL((k_dual_fused<T, true, true>), dim3(fixBlocks), dim3(ELT_THREADS), 0, stream, a);
+                    else hipLaunchKernelGGL((k_dual_fused<T, false, true>), dim3(fixBlocks), dim3(ELT_THREADS), 0, stream, a);
+                }
                 prof_end(e3);
-            } else pendingFin = true;
+            }
+            // rotate: y_t := y+_{t-1} (old upd), y+_t := buffer just written; w_{t+1} becomes the sweep input
             std::swap(p_xi, p_upd);
-            p_acc_view = p_acc; std::swap(p_acc, p_acc_other);
+            p_acc_view = p_acc;
+            std::swap(p_acc, p_acc_other);
             h_it++;
+        }
+        if (b.sharded && n > 0) {
+            // optimistic: the last iteration's distances, one 2-element all-reduce per BATCH.  Then one more all-reduce per batch (MAX): the
+            // batch's history entries become tree-global (vecPrimalInfs, SmpcController.cu:1521) and the ranks agree on the verdict (every
+            // rank takes the same replay decision even if an all-reduce algorithm ever delivered sums that differ in the last bit between ranks)
+            if (tail) { if (int rc = all_reduce(tail, 2, sizeof(T) == 8, "ncclAllReduce(dist tail)")) return fail_batch(rc); }
+            if (int rc = globalize_history(first, n, tail)) return fail_batch(rc);
         }
         RN_HIP(hipGetLastError());
         int violated = 0;
-        if (h_verdict && n > 0) {      // written by the batch's last launch (k_finalize_optimistic): no copy, one synchronisation
-            RN_HIP(hipStreamSynchronize(stream));
-            violated = *(volatile int *)h_verdict;
-        } else {
-            RN_HIP(hipMemcpyAsync(&violated, &d_state->violated, sizeof(int), hipMemcpyDeviceToHost, stream));
-            RN_HIP(hipStreamSynchronize(stream));
+        if (b.optimistic && n > 0) {
+            if (b.sharded) {
+                double votes = 0;
+                RN_HIP(hipMemcpyAsync(&votes, d_histGlob, sizeof(double), hipMemcpyDeviceToHost, stream));
+                RN_HIP(hipStreamSynchronize(stream));
+                violated = votes > 0 ? 1 : 0;
+            } else if (h_verdict) {   // written by the batch's last launch (k_finalize_optimistic): no copy, one synchronisation
+                RN_HIP(hipStreamSynchronize(stream));
+                violated = *(volatile int *)h_verdict;
+            } else {
+                RN_HIP(hipMemcpyAsync(&violated, &d_state->violated, sizeof(int), hipMemcpyDeviceToHost, stream));
+                RN_HIP(hipStreamSynchronize(stream));
+            }
         }
-        if (violated) return replay_exact(saved, n, primalInfs);
-        if (primalInfs && n > 0) RN_HIP(hipMemcpy(primalInfs, d_hist + first, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        if (b.sharded && n > 0 && transport == 1 && peerReady) { if (int rc = check_comm_fail()) return fail_batch(rc); }
+        if (violated) {   // the same n iterations once more from the checkpoint, as an exact batch; so are the next RN_OPT_BACKOFF batches
+            fallbacks++;
+            if (int rc = restore_iterates(saved)) return fail_batch(rc);
+            optHold = RN_OPT_BACKOFF;
+            return run_batch(n, primalInfs, false);
+        }
+        if (primalInfs && n > 0) {
+            if (!b.optimistic) RN_HIP(hipStreamSynchronize(stream));   // (an optimistic batch has synchronised for its verdict)
+            RN_HIP(hipMemcpy(primalInfs, d_hist + first, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+        }
         return RN_OK;
     }
     // SmpcController::allocateApgAlgorithm sizes its per-iteration storage by maxIterations once (SmpcController.cu:124-151):
@@ -1791,27 +1797,23 @@ struct Ctx : CtxBase {
     size_t inboxBytes = 0;
     PeerTable h_peer{};   // handed to the kernels by value (SweepArgs::peer)
     std::vector<void *> ipcOpened;
-    bool peerReady = false, inBatch = false;
+    bool peerReady = false;
     // Transport of the per-iteration exchange at the cut.  transportReq is what the caller asked for (RN_EXCHANGE_AUTO unless told:
     // rn_set_exchange_transport, $RAPIDNET_EXCHANGE), `transport` what the batches run: 0 = the communicator's all-reduce on the solver's
     // stream, 1 = one-shot peer writes.  AUTO is resolved by exchange_autotune -- by the first device-resident batch, or when the caller
     // asks (rn_exchange_autotune): both candidates run the context's own iterations, the ranks agree on the faster one.
     int transportReq = RN_EXCHANGE_AUTO, transport = 0;
-    bool tuned = false, inTune = false, oneShotBroken = false;
+    bool tuned = false, oneShotBroken = false;
     double tuneInfo[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // rn_exchange_autotune: {chosen, candidates, us/it collective (max over ranks), us/it one-shot (max), own collective, own one-shot, iterations, tunes run}
     double *d_tune = nullptr;    // 8 doubles: the ranks' agreement on the timings (allocated with the context: a control step never allocates)
     T *d_ckView = nullptr;       // the tuner's copy of the accelerated dual a getter would show (allocated when the one-shot transport becomes a candidate)
     // The forward walk and the dual update of the nodes it has walked in ONE launch (k_down_chain_dual): the optimistic batches ask for
-    // it per iteration (fuseReq + the dual update's arguments), the sweep says whether it happened.
+    // it per iteration (Batch::fuseReq + the dual update's arguments), the sweep says whether it happened (Batch::fuseDone).
     // Default (round 6): on, with the number of workgroups per chain BY SHAPE (fuse_split) -- one where the chains (nearly) fill the chip: the whole
     // 493-scenario tree -2.2 % per iteration dense, -5.6 % structured, a 1/2 shard -0.7 %; several on small trees and smaller shards (with one, the 62
     // workgroups of a 1/8 shard cannot keep as many bytes in flight as the stage-tiled kernel's grid: +2.7 %; profiles/r06_ab_fuse_by_shape.txt).  rn_set_fused_walk_dual(ctx, 0 / 1) or
     // $RAPIDNET_FUSE_DOWN_DUAL = 0 / 1 (read when the context runs its first batch) force it either way; while the per-launch profiling
     // of rn_profile_enable is on, the dual update always runs as a launch of its own (the kernel north_star's roofline target names).
-    bool fuseReq = false, fuseDone = false, fuseMat = false;
-    bool upDone = false;   // the chain walk of the NEXT plain sweep has been done by the last fused launch (k_down_chain_dual UPLIN): consumed by that sweep
-    DualArgs<T> fuseArgs{};
-    double fuseLn = 0.0;
     int fuseMode = -2;     // -2: not decided yet ($RAPIDNET_FUSE_DOWN_DUAL, else by shape), -1: by shape, 0 / 1: forced
     int set_fused_walk_dual(int on) override { RN_CHECK(on >= -1 && on <= 1, RN_E_ARG, "rn_set_fused_walk_dual: 0, 1 or -1 (by shape)"); fuseMode = on; return RN_OK; }
     bool fuse_by_shape() const {      // (profiles/r06_ab_fuse_by_shape.txt: 493 chains -2.2 % dense / -5.6 % structured, 247 chains of a 1/2 shard -0.7 %, 124 chains: a tie,
@@ -1977,10 +1979,12 @@ struct Ctx : CtxBase {
         tuneInfo[1] = 1.0 + (canOne ? 2.0 : 0.0); tuneInfo[6] = 0; tuneInfo[2] = tuneInfo[3] = tuneInfo[4] = tuneInfo[5] = 0.0;
         if (!canOne) { transport = 0; tuneInfo[0] = 0; return RN_OK; }     // one candidate: nothing to time
         for (int i = 0; i < 3; i++) if (!d_ck[i]) { if (int rc = dalloc(&d_ck[i], (size_t)ntot())) return rc; }
-        // what the timing runs must leave as they found it (the iterates themselves are in the batch's own checkpoint)
+        // what the timing runs must leave as they found it: the iterates, in a checkpoint taken here (each pass's own batch_open copies
+        // the same values over it again: the passes start from the restored state), ...
         const IterSave sv = save_iterates();
+        if (int rc = batch_open(nullptr)) return rc;
         const long kOpt = optBatches, kExact = exactBatches, kFall = fallbacks; const int kHold = optHold;
-        // ... and what RN_BUF_ACC_* shows: after a batch that is w_t, in the buffer the timing runs are about to reuse (the checkpoint holds w_{t+1}, the next input)
+        // ... the counters, and what RN_BUF_ACC_* shows: after a batch that is w_t, in the buffer the timing runs are about to reuse (the checkpoint holds w_{t+1}, the next input)
         T *const view = p_acc_view;
         const size_t vbytes = (size_t)ntot() * sizeof(T);
         if (view != sv.acc) {
@@ -1989,24 +1993,22 @@ struct Ctx : CtxBase {
         }
         double own[2] = {0, 0};
         int failed[2] = {0, 0};
-        inTune = true;
         for (int cand = 0; cand < 2; cand++) {
             transport = cand;
             for (int pass = 0; pass < 2 && !failed[cand]; pass++) {
                 const int n = pass == 0 ? std::max(iters / 2, 8) : iters;
                 optHold = 0;
                 const auto t0 = std::chrono::steady_clock::now();
-                const int rc = apg_iterate_optimistic(n, nullptr);     // ends with a synchronisation
+                const int rc = run_batch(n, nullptr, true);     // ends with a synchronisation
                 const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
                 if (rc != RN_OK) {      // (a one-shot reader's time-out is every rank's RN_E_COMM: all ranks come here together)
                     failed[cand] = 1; poisoned = false;
                     (void)hipMemsetAsync(&d_state->commFail, 0, sizeof(int), stream);
                 }
                 if (pass == 1 && rc == RN_OK) own[cand] = us / n;
-                if (int rc2 = restore_iterates(sv)) { inTune = false; return fail_batch(rc2); }
+                if (int rc2 = restore_iterates(sv)) return fail_batch(rc2);
             }
         }
-        inTune = false;
         optBatches = kOpt; exactBatches = kExact; fallbacks = kFall; optHold = kHold;
         if (view != sv.acc) { RN_HIP(hipMemcpyAsync(view, d_ckView, vbytes, hipMemcpyDeviceToDevice, stream)); p_acc_view = view; }
         if (knob[RN_KNOB_TUNE_BIAS_US] != -1) own[1] += (double)knob[RN_KNOB_TUNE_BIAS_US];      // test of the selection: this rank's one-shot time, biased
@@ -2065,60 +2067,14 @@ struct Ctx : CtxBase {
         const bool wantOptSharded = has_comm() && cutStage > 0 && optimistic && n > 0;
         // single GPU: worth a checkpoint (3 vector copies) and a read-back per batch once the batch is long enough
         const bool wantOptLocal = !has_comm() && cutStage <= 0 && optimistic && n >= RN_OPT_LOCAL_MIN;
-        if (wantOptSharded && transportReq == RN_EXCHANGE_AUTO && !tuned && !inTune && !inReplay) {   // the exchange chooses itself, once
+        if (wantOptSharded && transportReq == RN_EXCHANGE_AUTO && !tuned) {   // the exchange chooses itself, once
             if (int rc = exchange_autotune(std::min(std::max(n, 20), 100))) return rc;
         }
-        if ((wantOptSharded || wantOptLocal) && optHold > 0 && !inReplay) optHold--;
-        else if (wantOptSharded) { optBatches++; return apg_iterate_optimistic(n, primalInfs); }
-        else if (wantOptLocal) { optBatches++; return apg_iterate_optimistic_local(n, primalInfs); }
-        if (!inReplay && n > 0) exactBatches++;
-        const int first = h_it;
-        if (int rc = ensure_tables(h_it + n)) return rc;
-        inBatch = true;
-        for (int k = 0; k < n; k++) {
-            if (!acc_ready) {   // re-derive w_t after manual buffer edits (SmpcController.cu:1514)
-                hipLaunchKernelGGL(k_extrapolate<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, p_acc, p_xi, p_upd, (T)h_lam[h_it], ntot());
-                acc_ready = true;
-            }
-            const bool last = (k == n - 1);
-            if (int rc = launch_sweep(0, nullptr, last)) return fail_batch(rc);
-            DualArgs<T> a = dual_args();
-            hipEvent_t e2 = prof_begin(2);
-            const bool exactSharded = has_comm() && cutStage > 0;   // its fix-up pass and k_finalize fold eltBlocks partials: flat kernel
-            launch_dual_main(a, last, exactSharded);
-            prof_end(e2);
-            hipEvent_t e3 = prof_begin(3);
-            if (exactSharded) {   // tree-global distances: sum the ranks' dist^2 (2 doubles) before deciding
-                hipLaunchKernelGGL(k_reduce_dist<>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, eltBlocks, d_dist2);
-                if (int rc = all_reduce(d_dist2, 2, true, "ncclAllReduce(dist)")) return fail_batch(rc);
-                hipLaunchKernelGGL(k_decide_from<>, dim3(1), dim3(1), 0, stream, d_dist2, d_state, a.thrX, a.thrS);
-                if (last) hipLaunchKernelGGL((k_dual_fused<T, true, true>), dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, a);
-                else hipLaunchKernelGGL((k_dual_fused<T, false, true>), dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, a);
-                hipLaunchKernelGGL(k_finalize<>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, eltBlocks, d_state, d_hist, d_histParts, histCap);
-            } else {   // single GPU: the (small) fix-up launch also decides and does the bookkeeping (kernels.hpp, decideHere)
-                a.finalizedEarly = 1;
-                a.decideHere = 1; a.itHost = h_it; a.nMain = main_partials(); a.mainPartials = d_partials; a.partials = d_partials2;
-                const int fixBlocks = std::min(eltBlocks, RN_FIXUP_BLOCKS);
-                if (last) hipLaunchKernelGGL((k_dual_fused<T, true, true>), dim3(fixBlocks), dim3(ELT_THREADS), 0, stream, a);
-                else hipLaunchKernelGGL((k_dual_fused<T, false, true>), dim3(fixBlocks), dim3(ELT_THREADS), 0, stream, a);
-            }
-            prof_end(e3);
-            // rotate: y_t := y+_{t-1} (old upd), y+_t := buffer just written; w_{t+1} becomes the sweep input
-            std::swap(p_xi, p_upd);
-            p_acc_view = p_acc;
-            std::swap(p_acc, p_acc_other);
-            h_it++;
-        }
-        inBatch = false;
-        RN_HIP(hipGetLastError());
-        // sharded: the batch's history entries become tree-global (one MAX all-reduce per batch)
-        if (has_comm() && cutStage > 0 && n > 0) { if (int rc = globalize_history(first, n, nullptr)) return fail_batch(rc); }
-        if (transport == 1 && peerReady && has_comm() && cutStage > 0 && n > 0) { if (int rc = check_comm_fail()) return fail_batch(rc); }
-        if (primalInfs && n > 0) {
-            RN_HIP(hipStreamSynchronize(stream));
-            RN_HIP(hipMemcpy(primalInfs, d_hist + first, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
-        }
-        return RN_OK;
+        bool opt = wantOptSharded || wantOptLocal;
+        if (opt && optHold > 0) { optHold--; opt = false; }
+        if (opt) optBatches++;
+        else if (n > 0) exactBatches++;
+        return run_batch(n, primalInfs, opt);
     }
     // Sharded contexts, once per batch: vecPrimalInfs[first .. first + n) of this rank (arg-max over its own nodes) -> the
     // tree-global values, on every rank (SmpcController.cu:1480-1496, :1521); element 0 of the payload carries the ranks'
@@ -2140,7 +2096,7 @@ struct Ctx : CtxBase {
     // from an inconsistent accelerated dual.
     bool poisoned = false;
     int fail_batch(int rc) {
-        poisoned = true; carryTail = false; pendingFin = false; inBatch = false; hxUnscaled = false; upDone = false;
+        poisoned = true;
         err += " -- the batch was abandoned half-way: call rn_apg_reset before iterating again";
         return rc;
     }
@@ -2204,7 +2160,7 @@ struct Ctx : CtxBase {
         RN_CHECK(factored && affine_ready, RN_E_STATE, "rn_solve_step before the factor step / affine terms");
         RN_HIP(hipSetDevice(device));
         p_acc_view = p_acc;
-        return launch_sweep();
+        return launch_sweep(nullptr);
     }
     int prox() override {
         RN_CHECK(factored, RN_E_STATE, "rn_proximal_fun_g before the factor step");
@@ -2617,7 +2573,7 @@ struct Ctx : CtxBase {
         RN_CHECK(phase == 1 || phase == 2, RN_E_ARG, "rn_debug_sweep_phase: phase must be 1 or 2");
         RN_HIP(hipSetDevice(device));
         p_acc_view = p_acc;
-        return launch_sweep(phase);
+        return launch_sweep(nullptr, phase);
     }
     int cut_buffer(int write, double *host, size_t n) override {
         RN_CHECK(cutStage > 0, RN_E_STATE, "rn_debug_cut_buffer: no cut stage set");
