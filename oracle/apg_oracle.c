@@ -58,6 +58,10 @@
  *     the value of g at the prox point when the soft branch trips is gamma*dist(prox point, C) (the reference's
  *     :798-808 reads a partially filled scratch vector).
  *
+ * Block-free operator mode (oracle_config_lazy, Oracle(..., lazy_operators=True)): no per-node block is stored; the backward step
+ * applies them from L, Gtil = L'B', Rinv = (L'WL)^-1, the stage diagonals and p_i.  It exists to check trees whose blocks do not
+ * fit the host; see the comment at oracle_config_lazy.
+ *
  * Build: gcc -O3 -march=native -fPIC -shared [-DORACLE_REAL=float] -o liboracle_f64.so apg_oracle.c -lm
  */
 #include <math.h>
@@ -111,6 +115,12 @@ typedef struct {
     real *controlAction;       /* devControlAction, nu (SmpcController.cuh) */
     real *stateUpdate;         /* devStateUpdate, nx */
     real economicKpi, smoothKpi, safeKpi, networkKpi;   /* SmpcController.cu:103-106 (zeroed by the constructor) */
+    /* block-free operator mode (see oracle_config_lazy): no sysF/sysG/Omega/Theta/Phi/D/Psi/Ftil */
+    int lazy;
+    real *Rinv;                /* Rbar^-1 = (L'WL)^-1, nv x nv */
+    real *Lt;                  /* L', nv x nu (column-saxpy form of the L' products) */
+    real *dPre;                /* N x (nu | nx | nx): the stage diagonals d_u, d_x, d_xs */
+    real *sqrtP;               /* sqrt(p_i), nodes: F_i = sqrtP[i] [diag(d_x); diag(d_xs)], G_i = sqrtP[i] diag(d_u) */
 } oracle_t;
 
 static real *ralloc(size_t n) { real *p = (real *)calloc(n ? n : 1, sizeof(real)); return p; }
@@ -212,6 +222,19 @@ static int lu_inverse(int n, real *A, real *Ainv) {
 static int g_alias_operators = 1;
 void oracle_config_aliasing(int on) { g_alias_operators = on; }
 
+/* Block-free ("lazy") operator mode, read by oracle_create.  Every per-node block of the factor step is a shared matrix times
+ * a stage diagonal times a power of p_i (Engine.cu:721-745): F_i = sqrt(p_i) [diag(d_x); diag(d_xs)], G_i = sqrt(p_i) diag(d_u),
+ * Omega_a = (p_a Rbar)^-1, and Phi/D/Psi/Ftil/Theta are products of those with Gtil = L'B' and L'.  In this mode the oracle keeps
+ * only the shared matrices, the stage diagonals and the probabilities, and the backward step of node i applies the blocks
+ * without storing them (oracle_backward_node_lazy):
+ *     r_i = sigma_i + Gtil (q_i + F_i' xi_i) + L' (G_i psi_i),    v_i = -1/2 (1/p_a) Rinv r_i,    a = opIdx[i]
+ * which is what the stored path computes, in another order of summation (Rinv / p_a instead of (p_a Rbar)^-1).  Memory is
+ * O(nodes * (nv + 2nx + nu)) instead of O(nodes * nv * (nv + 2nx + nu)), so trees whose blocks do not fit the host (wide4096:
+ * ~160 GB of fp32 blocks) can be checked at full size.  Everything else -- forward walk, Hx, prox, residual, dual update, the
+ * cut-phase split -- is the same code as the stored path.  The FBE / NAMA direction oracle is not available in this mode. */
+static int g_lazy_operators = 0;
+void oracle_config_lazy(int on) { g_lazy_operators = on; }
+
 oracle_t *oracle_create(int nx, int nu, int nv, int nd, int N, int K, int nodes, int nNonLeaf,
                         const int *stages, const int *nodesPerStage, const int *nodesPerStageCumul,
                         const int *ancestor, const int *nChildren, const int *nChildrenCumul, const double *prob) {
@@ -230,6 +253,7 @@ oracle_t *oracle_create(int nx, int nu, int nv, int nd, int N, int K, int nodes,
     for (int i = 0; i < N - 1; i++)
         if (nodesPerStage[i] == nodesPerStage[i + 1]) { o->finalBranchNode = nodesPerStageCumul[i + 1]; break; }
     if (!g_alias_operators) o->finalBranchNode = nodes;
+    o->lazy = g_lazy_operators;
     int fb = o->finalBranchNode;
     /* operator aliasing, Engine.cu:210-221 */
     o->opIdx = (int *)malloc(nodes * sizeof(int));
@@ -240,12 +264,20 @@ oracle_t *oracle_create(int nx, int nu, int nv, int nd, int N, int K, int nodes,
     size_t n = nodes;
     o->B = ralloc((size_t)nx * nu); o->L = ralloc((size_t)nu * nv); o->Lhat = ralloc((size_t)nu * nd);
     o->Gd = ralloc((size_t)nx * nd); o->alpha1 = ralloc(nu); o->Wv = ralloc((size_t)nu * nv);
-    o->sysF = ralloc(n * 2 * nx * nx); o->sysG = ralloc(n * nu * nu);
+    if (o->lazy) {
+        o->Rinv = ralloc((size_t)nv * nv); o->Lt = ralloc((size_t)nv * nu);
+        o->dPre = ralloc((size_t)N * (2 * nx + nu)); o->sqrtP = ralloc(n);
+    } else {
+        o->sysF = ralloc(n * 2 * nx * nx); o->sysG = ralloc(n * nu * nu);
+    }
     o->xmin = ralloc(n * nx); o->xmax = ralloc(n * nx); o->xs = ralloc(n * nx);
     o->umin = ralloc(n * nu); o->umax = ralloc(n * nu);
-    o->Omega = ralloc((size_t)(fb > 0 ? fb : 1) * nv * nv); o->Theta = ralloc((size_t)(fb > 0 ? fb : 1) * nv * nx);
-    o->Phi = ralloc(n * nv * 2 * nx); o->D = ralloc(n * nv * 2 * nx);
-    o->Psi = ralloc(n * nv * nu); o->Ftil = ralloc(n * nv * nu); o->Gtil = ralloc((size_t)nv * nx);
+    if (!o->lazy) {
+        o->Omega = ralloc((size_t)(fb > 0 ? fb : 1) * nv * nv); o->Theta = ralloc((size_t)(fb > 0 ? fb : 1) * nv * nx);
+        o->Phi = ralloc(n * nv * 2 * nx); o->D = ralloc(n * nv * 2 * nx);
+        o->Psi = ralloc(n * nv * nu); o->Ftil = ralloc(n * nv * nu);
+    }
+    o->Gtil = ralloc((size_t)nv * nx);
     o->curX = ralloc(nx); o->prevU = ralloc(nu); o->prevUhat = ralloc(nu); o->prevD = ralloc(nd);
     o->uhat = ralloc(n * nu); o->e = ralloc(n * nx); o->beta = ralloc(n * nv); o->alpha = ralloc(n * nu);
     o->sigma = ralloc(n * nv);
@@ -270,7 +302,8 @@ void oracle_destroy(oracle_t *o) {
                     o->xs, o->umin, o->umax, o->Omega, o->Theta, o->Phi, o->D, o->Psi, o->Ftil, o->Gtil, o->curX,
                     o->prevU, o->prevUhat, o->prevD, o->uhat, o->e, o->beta, o->alpha, o->sigma, o->x, o->u, o->v,
                     o->xi, o->psi, o->accXi, o->accPsi, o->updXi, o->updPsi, o->primalXi, o->primalPsi, o->dualXi,
-                    o->dualPsi, o->resXi, o->resPsi, o->q, o->r, o->controlAction, o->stateUpdate};
+                    o->dualPsi, o->resXi, o->resPsi, o->q, o->r, o->controlAction, o->stateUpdate,
+                    o->Rinv, o->Lt, o->dPre, o->sqrtP};
     for (size_t i = 0; i < sizeof(ptrs) / sizeof(ptrs[0]); i++) free(ptrs[i]);
     free(o);
 }
@@ -297,17 +330,19 @@ int oracle_factor_step(oracle_t *o, const double *matB, const double *matL, cons
     gemm(0, 0, nu, nv, nu, 1, W, nu, o->L, nu, 0, o->Wv, nu);
     real *Rbar = ralloc((size_t)nv * nv);
     gemm(1, 0, nv, nv, nu, 1, o->L, nu, o->Wv, nu, 0, Rbar, nv);
-    memset(o->sysF, 0, (size_t)nodes * 2 * nx * nx * sizeof(real));
-    memset(o->sysG, 0, (size_t)nodes * nu * nu * sizeof(real));
+    if (!o->lazy) {
+        memset(o->sysF, 0, (size_t)nodes * 2 * nx * nx * sizeof(real));
+        memset(o->sysG, 0, (size_t)nodes * nu * nu * sizeof(real));
+    }
     /* per-node copies of the bounds and p_i*Rbar for the nodes that own an Omega (Engine.cu:421-437) */
-    real *costWnode = ralloc((size_t)(fb > 0 ? fb : 1) * nv * nv);
+    real *costWnode = o->lazy ? NULL : ralloc((size_t)(fb > 0 ? fb : 1) * nv * nv);
     for (int i = 0; i < nodes; i++) {
         for (int j = 0; j < nx; j++) {
             o->xmin[(size_t)i * nx + j] = (real)xmin[j]; o->xmax[(size_t)i * nx + j] = (real)xmax[j];
             o->xs[(size_t)i * nx + j] = (real)xsafe[j];
         }
         for (int j = 0; j < nu; j++) { o->umin[(size_t)i * nu + j] = (real)umin[j]; o->umax[(size_t)i * nu + j] = (real)umax[j]; }
-        if (i < fb)
+        if (i < fb && !o->lazy)
             for (int j = 0; j < nv * nv; j++) costWnode[(size_t)i * nv * nv + j] = o->prob[i] * Rbar[j];
     }
     /* preconditionSystem / preconditionConstraintU / preconditionConstraintX (Utilities.cu:33-58, 360-405);
@@ -318,12 +353,15 @@ int oracle_factor_step(oracle_t *o, const double *matB, const double *matL, cons
         for (int j = 0; j < o->nodesPerStage[k]; j++) {
             int i = cum + j;
             real sp = (real)sqrt((double)o->prob[i]);
-            real *G = o->sysG + (size_t)i * nu * nu;
-            real *F = o->sysF + (size_t)i * 2 * nx * nx;
-            for (int t = 0; t < nu; t++) G[(size_t)nu * t + t] = sp * (real)dk[t];
-            for (int t = 0; t < nx; t++) {
-                F[(size_t)2 * nx * t + t] = sp * (real)dk[nu + t];            /* rows 0..nx-1 : diag(d_x)  */
-                F[(size_t)2 * nx * t + nx + t] = sp * (real)dk[nu + nx + t];  /* rows nx..2nx-1: diag(d_xs) */
+            if (o->lazy) o->sqrtP[i] = sp;   /* the diagonals of F_i / G_i are formed as sp * (real)dk[t] where they are used */
+            else {
+                real *G = o->sysG + (size_t)i * nu * nu;
+                real *F = o->sysF + (size_t)i * 2 * nx * nx;
+                for (int t = 0; t < nu; t++) G[(size_t)nu * t + t] = sp * (real)dk[t];
+                for (int t = 0; t < nx; t++) {
+                    F[(size_t)2 * nx * t + t] = sp * (real)dk[nu + t];            /* rows 0..nx-1 : diag(d_x)  */
+                    F[(size_t)2 * nx * t + nx + t] = sp * (real)dk[nu + nx + t];  /* rows nx..2nx-1: diag(d_xs) */
+                }
             }
             for (int t = 0; t < nu; t++) {
                 real s = sp * (real)dk[t];
@@ -337,6 +375,14 @@ int oracle_factor_step(oracle_t *o, const double *matB, const double *matL, cons
     }
     /* factorStep: Bbar' = L'B' (nv x nx)  (Engine.cu:702-705) */
     gemm(1, 1, nv, nx, nu, 1, o->L, nu, o->B, nx, 0, o->Gtil, nv);
+    if (o->lazy) { /* block-free mode: Rinv = Rbar^-1 once, L' for the backward step, the stage diagonals */
+        for (size_t t = 0; t < (size_t)N * (2 * nx + nu); t++) o->dPre[t] = (real)diagPrecnd[t];
+        for (int t = 0; t < nv; t++)
+            for (int c = 0; c < nu; c++) o->Lt[t + (size_t)c * nv] = o->L[c + (size_t)t * nu];
+        int rc = lu_inverse(nv, Rbar, o->Rinv);
+        free(W); free(Rbar);
+        return rc ? 1 : 0;
+    }
     /* Omega = (p Rbar)^-1 for the owning nodes (Engine.cu:707-714) */
     for (int i = 0; i < fb; i++)
         if (lu_inverse(nv, costWnode + (size_t)i * nv * nv, o->Omega + (size_t)i * nv * nv)) {
@@ -470,13 +516,62 @@ static void sum_children(const oracle_t *o, const real *src, real *dst, int stag
     }
 }
 
+/* Y[:, c] += A X[:, c] for the nb columns of a block, A m x n col-major: A streams once per block, Y stays in cache */
+static void gemm_cols(int m, int n, const real *A, int lda, const real *X, int ldx, real *Y, int ldy, int nb) {
+    for (int p = 0; p < n; p++) {
+        const real *a = A + (size_t)p * lda;
+        for (int c = 0; c < nb; c++) {
+            real xp = X[p + (size_t)c * ldx];
+            real *y = Y + (size_t)c * ldy;
+            for (int i = 0; i < m; i++) y[i] += a[i] * xp;
+        }
+    }
+}
+
+#define LAZY_COLS 8
+/* the backward step of stage k in the block-free mode (see oracle_config_lazy), LAZY_COLS nodes at a time:
+ *   q_i <- F_i' xi_i (+ q_i),  r_i <- sigma_i (+ r_i) + Gtil q_i + L' (G_i psi_i),  v_i <- -1/2 (1/p_a) Rinv r_i
+ * gp is nu x LAZY_COLS scratch */
+static void backward_stage_lazy(oracle_t *o, int k, real *gp) {
+    int nx = o->nx, nu = o->nu, nv = o->nv, N = o->N;
+    int cum = o->nodesPerStageCumul[k], nk = o->nodesPerStage[k];
+    const real *du = o->dPre + (size_t)k * (2 * nx + nu), *dx = du + nu, *ds = du + nu + nx;
+    for (int j0 = 0; j0 < nk; j0 += LAZY_COLS) {
+        int nb = nk - j0 < LAZY_COLS ? nk - j0 : LAZY_COLS;
+        for (int c = 0; c < nb; c++) {
+            int j = j0 + c, i = cum + j;
+            real sp = o->sqrtP[i];
+            real *sig = o->sigma + (size_t)i * nv, *qj = o->q + (size_t)j * nx, *rj = o->r + (size_t)j * nv;
+            const real *xi = o->accXi + (size_t)i * 2 * nx, *psi = o->accPsi + (size_t)i * nu;
+            if (k < N - 1) for (int t = 0; t < nv; t++) sig[t] += rj[t];
+            for (int t = 0; t < nx; t++) {
+                real s = (sp * dx[t]) * xi[t] + (sp * ds[t]) * xi[nx + t];
+                qj[t] = (k < N - 1) ? s + qj[t] : s;
+            }
+            for (int t = 0; t < nu; t++) gp[(size_t)c * nu + t] = (sp * du[t]) * psi[t];
+            memcpy(rj, sig, nv * sizeof(real));
+        }
+        real *R = o->r + (size_t)j0 * nv, *V = o->v + (size_t)(cum + j0) * nv;
+        gemm_cols(nv, nx, o->Gtil, nv, o->q + (size_t)j0 * nx, nx, R, nv, nb);
+        gemm_cols(nv, nu, o->Lt, nv, gp, nu, R, nv, nb);
+        memset(V, 0, (size_t)nb * nv * sizeof(real));
+        gemm_cols(nv, nv, o->Rinv, nv, R, nv, V, nv, nb);
+        for (int c = 0; c < nb; c++) {
+            real sc = (real)-0.5 / o->prob[o->opIdx[cum + j0 + c]];
+            for (int t = 0; t < nv; t++) V[(size_t)c * nv + t] *= sc;
+        }
+    }
+}
+
 /* backward substitution of SmpcController::solveStep (SmpcController.cu:593-673) for stages kHi .. kLo */
 void oracle_backward_range(oracle_t *o, int kHi, int kLo) {
     int nx = o->nx, nu = o->nu, nv = o->nv, N = o->N, K = o->K;
     real *tmpQ = ralloc((size_t)K * nx), *tmpR = ralloc((size_t)K * nv);
+    real *gp = o->lazy ? ralloc((size_t)nu * LAZY_COLS) : NULL;
     for (int k = kHi; k >= kLo; k--) {
         int cum = o->nodesPerStageCumul[k], nk = o->nodesPerStage[k];
-        for (int j = 0; j < nk; j++) {
+        if (o->lazy) backward_stage_lazy(o, k, gp);
+        else for (int j = 0; j < nk; j++) {
             int i = cum + j;
             real *sig = o->sigma + (size_t)i * nv, *v = o->v + (size_t)i * nv;
             real *qj = o->q + (size_t)j * nx, *rj = o->r + (size_t)j * nv;
@@ -508,7 +603,7 @@ void oracle_backward_range(oracle_t *o, int kHi, int kLo) {
             }
         }
     }
-    free(tmpQ); free(tmpR);
+    free(tmpQ); free(tmpR); free(gp);
 }
 
 void oracle_forward(oracle_t *o);
@@ -577,13 +672,25 @@ void oracle_forward(oracle_t *o) {
         }
     }
     /* Hx  (:744-747) */
-    for (int i = 0; i < nodes; i++) {
-        const real *F = o->sysF + (size_t)i * 2 * nx * nx, *G = o->sysG + (size_t)i * nu * nu;
-        for (int t = 0; t < nx; t++) {
-            o->primalXi[(size_t)i * 2 * nx + t] = F[(size_t)2 * nx * t + t] * o->x[(size_t)i * nx + t];
-            o->primalXi[(size_t)i * 2 * nx + nx + t] = F[(size_t)2 * nx * t + nx + t] * o->x[(size_t)i * nx + t];
+    if (o->lazy) {
+        for (int i = 0; i < nodes; i++) {
+            const real *du = o->dPre + (size_t)o->stages[i] * (2 * nx + nu);
+            real sp = o->sqrtP[i];
+            for (int t = 0; t < nx; t++) {
+                o->primalXi[(size_t)i * 2 * nx + t] = (sp * du[nu + t]) * o->x[(size_t)i * nx + t];
+                o->primalXi[(size_t)i * 2 * nx + nx + t] = (sp * du[nu + nx + t]) * o->x[(size_t)i * nx + t];
+            }
+            for (int t = 0; t < nu; t++) o->primalPsi[(size_t)i * nu + t] = (sp * du[t]) * o->u[(size_t)i * nu + t];
         }
-        for (int t = 0; t < nu; t++) o->primalPsi[(size_t)i * nu + t] = G[(size_t)nu * t + t] * o->u[(size_t)i * nu + t];
+    } else {
+        for (int i = 0; i < nodes; i++) {
+            const real *F = o->sysF + (size_t)i * 2 * nx * nx, *G = o->sysG + (size_t)i * nu * nu;
+            for (int t = 0; t < nx; t++) {
+                o->primalXi[(size_t)i * 2 * nx + t] = F[(size_t)2 * nx * t + t] * o->x[(size_t)i * nx + t];
+                o->primalXi[(size_t)i * 2 * nx + nx + t] = F[(size_t)2 * nx * t + nx + t] * o->x[(size_t)i * nx + t];
+            }
+            for (int t = 0; t < nu; t++) o->primalPsi[(size_t)i * nu + t] = G[(size_t)nu * t + t] * o->u[(size_t)i * nu + t];
+        }
     }
     free(Lv);
 }
@@ -705,10 +812,12 @@ void oracle_apg_continue(oracle_t *o, int iters, double *theta01) {
  * reference's exact control flow; pinned by src/test/testDataFiles/{smpcFbeTest,smpcNamaTest}.json through
  * tests/test_oracle_fbe_nama.py (the Python twin of TestSmpcController.cu:403-1040).
  * ====================================================================================================== */
-void oracle_set_algorithm(oracle_t *o, int algorithm, int lbfgsBufferSize) {
+/* returns nonzero (and changes nothing) for FBE / NAMA in the block-free mode: their direction oracle reads the stored blocks */
+int oracle_set_algorithm(oracle_t *o, int algorithm, int lbfgsBufferSize) {
     size_t nxi = (size_t)o->nodes * 2 * o->nx, nps = (size_t)o->nodes * o->nu, n = nxi + nps;
+    if (algorithm != 0 && o->lazy) return 1;
     o->algorithm = algorithm;
-    if (algorithm == 0 || o->matS) return;
+    if (algorithm == 0 || o->matS) return 0;
     o->lbfgsSize = lbfgsBufferSize;
     o->prevXi = ralloc(nxi); o->prevPsi = ralloc(nps); o->gradXi = ralloc(nxi); o->gradPsi = ralloc(nps);
     o->prevGradXi = ralloc(nxi); o->prevGradPsi = ralloc(nps);
@@ -720,6 +829,7 @@ void oracle_set_algorithm(oracle_t *o, int algorithm, int lbfgsBufferSize) {
     o->matS = ralloc((size_t)(lbfgsBufferSize + 1) * n); o->matY = ralloc((size_t)(lbfgsBufferSize + 1) * n);
     o->rho = ralloc((size_t)lbfgsBufferSize + 1);
     o->lbfgsCol = 0; o->lbfgsMem = 0; o->lbfgsSkip = 0; o->lbfgsH = 1;
+    return 0;
 }
 
 /* SmpcController::initialiseAlgorithm (FBE / NAMA parts, :436-449) + initaliseLbfgBuffer (:453-468) */

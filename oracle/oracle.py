@@ -73,7 +73,9 @@ def _lib(precision, variant=""):
         lib.oracle_final_branch_node.argtypes = [C.c_void_p]
         lib.oracle_dist.restype = C.c_double
         lib.oracle_dist.argtypes = [C.c_void_p, C.c_int]
+        lib.oracle_set_algorithm.restype = C.c_int
         lib.oracle_set_algorithm.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        lib.oracle_config_lazy.argtypes = [C.c_int]
         for fn in ("oracle_fbe_reset", "oracle_hessian_oracle", "oracle_gradient_fbe", "oracle_nama_residual",
                    "oracle_lbfgs_direction"):
             getattr(lib, fn).argtypes = [C.c_void_p]
@@ -121,9 +123,13 @@ def forecast_at(forecast, sim_time):
 class Oracle:
     """CPU oracle for one (network, tree, config) triple."""
 
-    def __init__(self, network, tree, config, precision="f64", alias_operators=True, variant=""):
+    def __init__(self, network, tree, config, precision="f64", alias_operators=True, variant="", lazy_operators=False):
+        """lazy_operators: the block-free operator mode (oracle_config_lazy in apg_oracle.c): no per-node blocks are stored, the
+        backward step applies them from the shared matrices, the stage diagonals and p_i.  APG only (no FBE / NAMA)."""
         self.lib = _lib(precision, variant)
         self.lib.oracle_config_aliasing(1 if alias_operators else 0)
+        self.lib.oracle_config_lazy(1 if lazy_operators else 0)
+        self.lazy_operators = bool(lazy_operators)
         self.dtype = np.float64 if precision == "f64" else np.float32
         self.network, self.tree, self.config = network, tree, config
         self.nx, self.nu, self.nd = (int(_scalar(network, k)) for k in ("nx", "nu", "nd"))
@@ -226,17 +232,27 @@ class Oracle:
     def set_algorithm(self, name, lbfgs_buffer_size=None):
         if lbfgs_buffer_size is None:
             lbfgs_buffer_size = int(_scalar(self.config, "lbfgsBufferSize")) if "lbfgsBufferSize" in self.config else 5
-        self.algorithm = self.ALGORITHMS[name]
+        algorithm = self.ALGORITHMS[name]
+        if algorithm:
+            self._stored_blocks(name)
+        assert self.lib.oracle_set_algorithm(self.h, algorithm, int(lbfgs_buffer_size)) == 0
+        self.algorithm = algorithm
         self.lbfgs_size = int(lbfgs_buffer_size)
-        self.lib.oracle_set_algorithm(self.h, self.algorithm, self.lbfgs_size)
+
+    def _stored_blocks(self, what):
+        if self.lazy_operators:
+            raise RuntimeError("%s needs the stored operator blocks; this oracle was built with lazy_operators=True" % what)
 
     def fbe_reset(self):
+        self._stored_blocks("fbe_reset")
         self.lib.oracle_fbe_reset(self.h)
 
     def hessian_oracle(self):
+        self._stored_blocks("hessian_oracle")
         self.lib.oracle_hessian_oracle(self.h)
 
     def gradient_fbe(self):
+        self._stored_blocks("gradient_fbe")
         self.lib.oracle_gradient_fbe(self.h)
 
     def nama_residual(self):
@@ -249,9 +265,11 @@ class Oracle:
         return self.lib.oracle_value_fbe(self.h)
 
     def line_search_fbe(self, value_y):
+        self._stored_blocks("line_search_fbe")
         return self.lib.oracle_line_search_fbe(self.h, float(value_y))
 
     def line_search_ame(self, value_y):
+        self._stored_blocks("line_search_ame")
         return self.lib.oracle_line_search_ame(self.h, float(value_y))
 
     def lbfgs_state(self, col=None, mem=None, H=None):
@@ -262,6 +280,7 @@ class Oracle:
 
     def fbe_nama(self, iters=None):
         """algorithmGlobalFbe / algorithmNama: returns (vecPrimalInfs, vecValueFbe, vecTau)."""
+        self._stored_blocks("fbe_nama")
         iters = self.max_iterations if iters is None else int(iters)
         hist, val, tau = (np.zeros(max(iters, 1)) for _ in range(3))
         self.lib.oracle_fbe_nama(self.h, iters, hist.ctypes.data, val.ctypes.data, tau.ctypes.data)

@@ -3,22 +3,26 @@
 configs[3]: the 493-scenario Barcelona tree sharded by subtree over 8 ranks, cut below stage 2 (what `bench.py --gpus 8`
 runs).  A one-GPU box cannot host 8 RCCL ranks, so the 8 rank-local contexts live on ONE device and the per-iteration
 all-reduce of the cut parents' children sums is done by the test (rn_debug_sweep_phase / rn_debug_cut_buffer); the
-reassembled iterates must equal the unsharded HIP solve (1e-9 after 20 iterations) and the CPU oracle (2 iterations: the
-oracle needs ~25 s and ~6 GB for its factor step at this size).  The real ncclAllReduce path is run on the full tree with a
+reassembled iterates must equal the unsharded HIP solve (1e-9 after 20 iterations) and the block-free CPU oracle after every
+one of the 20 iterations, globally and per stage (tests/stagewise.py).  The real ncclAllReduce path is run on the full tree with a
 one-rank communicator in both exchange modes.
 
 configs[4]: the wide network (200 states, 360 inputs, nv = 306) on the 4 096-scenario tree in fp32, 160 GB of per-node
-blocks on one MI355X.  No CPU oracle can hold that, so (i) the same network is checked against the fp32 oracle on a
+blocks on one MI355X.  No CPU oracle with stored blocks can hold that: the block-free fp64 oracle (lazy_operators=True) checks
+three contexts at full size over 3 iterations, stage by stage, and (i) the same network is checked against the fp32 oracle on a
 16-scenario tree with a three-stage crown (same kernels and template instantiations: 3 slots per lane in k_stream_gemv,
 tile-kernel fallback of the shared products), and (ii) at full size the dense-block path and the structured path -- two
 independent implementations of the same operator -- must agree, the dual-gradient map must be affine in the dual, and a
 repeated sweep must be bitwise identical.
 """
+import threading
+
 import numpy as np
 import pytest
 
 from oracle.oracle import Oracle
 from rapidnet_amd import capi, partition, synth
+from stagewise import worst_by_buffer
 
 pytestmark = pytest.mark.gpu
 REL_TOL = 1e-9
@@ -53,7 +57,7 @@ VECS = ((capi.BUF_X, "x", "nx"), (capi.BUF_U, "u", "nu"), (capi.BUF_V, "v", "nv"
 
 def test_barcelona493_sharded_over_8_ranks(barcelona493):
     p, (dh, ah) = barcelona493
-    world, iters, oracle_iters = 8, 20, 2
+    world, iters = 8, 20
     cut = partition.default_cut_stage(p["tree"])
     assert cut == 2 and p["tree"]["nodesPerStage"][cut] == 493            # below stage 2: 493 subtrees, 61 or 62 per rank
     moments = partition.cut_children_moments(p["tree"], cut)
@@ -82,7 +86,14 @@ def test_barcelona493_sharded_over_8_ranks(barcelona493):
     def gathered(bid, dim):
         return partition.scatter_to_global([s.get(bid) for s in shards], ids, nodes, dim)
 
-    oracle_state = None
+    # the block-free oracle (no per-node blocks: ~0.1 s per iteration at this size) steps beside the ranks and is compared after
+    # every one of the 20 iterations, globally and stage by stage
+    o = Oracle(p["network"], p["tree"], p["config"], lazy_operators=True)
+    o.initialise(dh, ah)
+    for s in shards:   # beta of the replicated crown comes from the children moments
+        assert relmax(s.get(capi.BUF_BETA)[: crown * nv], o.get("beta")[: crown * nv]) < 1e-12
+    o.apg_reset()
+    th, worst = [1.0, 1.0], {}
     for it, lam in enumerate(lambdas(iters)):
         for s in shards:
             s.dualExtrapolationStep(lam)
@@ -92,16 +103,16 @@ def test_barcelona493_sharded_over_8_ranks(barcelona493):
             s.debugCutBuffer(n_cut, total)
             s.debugSweepPhase(2)
             s.proximalFunG(); s.computeFixedPointResidual(); s.dualUpdate()
-        if it + 1 == oracle_iters:
-            oracle_state = {nm: gathered(bid, dims[d]) for bid, nm, d in VECS}
-    # (1) against the CPU oracle after 2 iterations
-    o = Oracle(p["network"], p["tree"], p["config"])
-    o.initialise(dh, ah)
-    o.apg(oracle_iters)
-    for s in shards:   # beta of the replicated crown comes from the children moments
-        assert relmax(s.get(capi.BUF_BETA)[: crown * nv], o.get("beta")[: crown * nv]) < 1e-12
-    for _, nm, _ in VECS:
-        assert relmax(oracle_state[nm], o.get(nm)) < REL_TOL, ("oracle", nm)
+        # (1) against the CPU oracle after every iteration
+        th = o.apg_continue(1, th)
+        got = {nm: gathered(bid, dims[d]) for bid, nm, d in VECS}
+        ref = {nm: o.get(nm) for nm in list(got) + ["primalXi", "primalPsi"]}
+        for nm in got:
+            assert relmax(got[nm], ref[nm]) < REL_TOL, ("oracle", it, nm)
+        w = worst_by_buffer(got, ref, p["tree"], nx, nu, nv)
+        print("barcelona493 over 8 ranks, iteration %2d, worst per-stage error against the oracle: %s"
+              % (it + 1, {k: "%.1e" % v for k, v in w.items()}))
+        assert max(w.values()) <= REL_TOL, (it, w)
     del o
     # (2) against the unsharded device-resident solve after 20 iterations
     full.algorithmApg(iters)
@@ -138,7 +149,6 @@ def test_barcelona493_one_rank_rccl_exchange(barcelona493, optimistic):
 
 
 # ---- configs[4] --------------------------------------------------------------------------------------------------
-synth.CONFIGS.setdefault("wide16", (4, 200, 360, 280, 54, 24, [4, 2, 2]))   # the wide network, 16 scenarios, three-stage crown
 
 
 @pytest.mark.parametrize("structured", [False, True])
@@ -159,9 +169,49 @@ def test_wide_network_fp32_against_the_oracle(structured):
     s.close()
 
 
+WIDE_ITERS = 3
+WIDE_VECS = {"x": capi.BUF_X, "u": capi.BUF_U, "v": capi.BUF_V, "updXi": capi.BUF_UPD_XI, "updPsi": capi.BUF_UPD_PSI,
+             "primalXi": capi.BUF_PRIMAL_XI, "primalPsi": capi.BUF_PRIMAL_PSI, "dualXi": capi.BUF_DUAL_XI, "resPsi": capi.BUF_RES_PSI}
+
+
+def lazy_oracle_snapshots(p, iters, out):
+    """the block-free fp64 oracle on the full tree: out gets (buffers, primal infeasibility) after each of iters APG iterations"""
+    dh, ah = synth.forecast_at(p["forecast"], 0)
+    o = Oracle(p["network"], p["tree"], p["config"], lazy_operators=True)
+    o.initialise(dh, ah)
+    o.apg_reset()
+    th = [1.0, 1.0]
+    for _ in range(iters):
+        th = o.apg_continue(1, th)
+        out.append(({nm: o.get(nm) for nm in WIDE_VECS}, o.primal_infeasibility()))
+
+
+def stepwise(s, iters):
+    """(buffers, history entry) of a context after each of iters APG iterations from a reset"""
+    s.apgReset()
+    out = []
+    for _ in range(iters):
+        h = s.apgIterate(1)
+        out.append(({nm: s.get(bid) for nm, bid in WIDE_VECS.items()}, float(h[0])))
+    return out
+
+
 def test_wide4096_fp32_full_size():
+    """(o2) At full size against the block-free fp64 oracle (lazy_operators=True: no per-node blocks, ~6 GB of vectors), which
+    runs in a thread beside the GPU contexts: 3 iterations, compared stage by stage after each -- the fp32 dense and fp32
+    structured contexts at FP32_TOL, an fp64 structured context at 1e-9."""
     p = synth.make_problem("wide4096")
     dh, ah = synth.forecast_at(p["forecast"], 0)
+    oracle_out, oracle_err = [], []
+
+    def run_oracle():
+        try:
+            lazy_oracle_snapshots(p, WIDE_ITERS, oracle_out)
+        except BaseException as e:   # re-raised in the test's thread
+            oracle_err.append(e)
+
+    oracle_thread = threading.Thread(target=run_oracle, daemon=True)
+    oracle_thread.start()
     d = capi.Solver(p["network"], p["tree"], p["config"], precision="f32")              # 160 GB of per-node blocks
     d.initialiseSmpcController(dh, ah)
     assert d.nodes == 86289 and d.nx == 200 and d.K == 4096
@@ -192,6 +242,8 @@ def test_wide4096_fp32_full_size():
     del ne, a, b
     st = capi.Solver(p["network"], p["tree"], p["config"], precision="f32", structured=True)
     st.initialiseSmpcController(dh, ah)
+    runs = {"f32 dense": (d, stepwise(d, WIDE_ITERS)), "f32 structured": (st, stepwise(st, WIDE_ITERS))}
+    print("\nwide4096 kernelInfo: f32 dense %s, f32 structured %s" % (d.kernelInfo(), st.kernelInfo()))
     # (i) two implementations of the operator, 10 device-resident iterations
     hd, hs = d.algorithmApg(10), st.algorithmApg(10)
     for bid in (capi.BUF_X, capi.BUF_U, capi.BUF_V, capi.BUF_UPD_XI, capi.BUF_UPD_PSI, capi.BUF_PRIMAL_XI, capi.BUF_DUAL_XI, capi.BUF_RES_PSI):
@@ -218,3 +270,23 @@ def test_wide4096_fp32_full_size():
     assert relmax(hab, lin) < FP32_TOL
     assert np.array_equal(hx(cxi, cpsi), hab)
     d.close()
+    s64 = capi.Solver(p["network"], p["tree"], p["config"], precision="f64", structured=True)     # no per-node blocks: fits
+    s64.initialiseSmpcController(dh, ah)
+    print("wide4096 kernelInfo: f64 structured %s" % s64.kernelInfo())
+    runs["f64 structured"] = (None, stepwise(s64, WIDE_ITERS))
+    s64.close()
+    # (o2) every context against the lazy fp64 oracle, stage by stage, after each iteration
+    oracle_thread.join()
+    assert not oracle_err, oracle_err
+    assert len(oracle_out) == WIDE_ITERS
+    tol = {"f32 dense": FP32_TOL, "f32 structured": FP32_TOL, "f64 structured": REL_TOL}
+    failed = []
+    for tag, (_, snaps) in runs.items():
+        for it, ((got, h), (ref, oh)) in enumerate(zip(snaps, oracle_out)):
+            w = worst_by_buffer(got, ref, p["tree"], nx, nu, nv)
+            w["history"] = abs(h - oh) / abs(oh)
+            print("wide4096 %s, iteration %d, worst per-stage error against the lazy fp64 oracle: %s"
+                  % (tag, it + 1, {k: "%.1e" % v for k, v in w.items()}))
+            if max(w.values()) > tol[tag]:
+                failed.append((tag, it + 1, w))
+    assert not failed, failed
