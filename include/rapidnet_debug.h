@@ -70,6 +70,13 @@ enum {
 };
 int rn_debug_set_knob(rn_ctx *ctx, int knob, int value);
 
+/* What the launches of k_stream_gemv look like, for the tests of its split last round: info = {splitFirst, splitSpanHalf, twoPerCU, numCUs}.
+ * splitFirst: the first node whose block two workgroups share by columns (the second one's partials go to a buffer of their own); = nodes
+ * when the launch is not split, -1 before the factor step has decided (a re-factor by rn_set_operator decides again).  splitSpanHalf: the
+ * span at which the second workgroup starts (0 without a split).  twoPerCU: 1 = the instantiation that leaves room for two workgroups
+ * per CU.  numCUs: the device's compute units, valid from rn_create on.  Reads only: nothing that is computed changes. */
+int rn_debug_stream_info(rn_ctx *ctx, int info[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,7 @@ SYMBOLS = [
     "rn_get_range", "rn_set_range", "rn_get_kernel_info", "rn_default_cut_stage", "rn_partition_create", "rn_partition_destroy", "rn_create_sharded", "rn_shard_info", "rn_shard_global_nodes",
     "rn_debug_set_allreduce", "rn_debug_local_group_create", "rn_debug_local_group_join", "rn_debug_local_group_destroy",
     "rn_guard_check", "rn_device_memory_info", "rn_reserve_iterations", "rn_profile_read_collective", "rn_debug_inject_allocation", "rn_guard_report", "rn_debug_guard_poke",
-    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob",
+    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info",
 ]
 
 
@@ -216,6 +216,7 @@ def load():
     lib.rn_exchange_autotune.argtypes = [vp, ip, dp]
     lib.rn_set_fused_walk_dual.argtypes = [vp, ip]
     lib.rn_debug_set_knob.argtypes = [vp, ip, ip]
+    lib.rn_debug_stream_info.argtypes = [vp, dp]
     lib.rn_profile_read_collective.argtypes = [vp, dp, dp]
     _LIB = lib
     return lib
@@ -575,6 +576,14 @@ class Solver:
         knob: a KNOB_* id or its name without the prefix ("dual_trips", "vlv_wide", ...); value -1: the library's own choice"""
         k = KNOBS[knob.lower()] if isinstance(knob, str) else int(knob)
         self._check(self.lib.rn_debug_set_knob(self.h, k, int(value)))
+
+    def streamInfo(self):
+        """rn_debug_stream_info (include/rapidnet_debug.h): what the launches of k_stream_gemv look like.  splitFirst: first node of the
+        split last round (= nodes: not split; -1: the factor step has not decided yet), splitSpanHalf: the span the second workgroup of
+        a split block starts at, twoPerCU: which instantiation runs, numCUs: the device's compute units (valid before the factor step)."""
+        out = np.zeros(4, dtype=np.int32)
+        self._check(self.lib.rn_debug_stream_info(self.h, out.ctypes.data))
+        return dict(zip(("splitFirst", "splitSpanHalf", "twoPerCU", "numCUs"), (int(v) for v in out)))
 
     def debugGuardPoke(self, nbytes):
         self._check(self.lib.rn_debug_guard_poke(self.h, int(nbytes)))

@@ -220,6 +220,7 @@ struct CtxBase {
     virtual int exchange_prepare_api() = 0;
     virtual int set_fused_walk_dual(int) = 0;
     virtual int set_knob(int, int) = 0;
+    virtual int stream_info(int *) = 0;
     virtual int debug_peer_seq(unsigned int) = 0;
     virtual int fbe_counters(long *) = 0;
 };
@@ -2115,6 +2116,13 @@ struct Ctx : CtxBase {
         out[7] = v_lv_is_slab() ? 1 : 0;                 // 1: k_gemm_vlv (slab), 0: two k_gemm_shared launches
         return RN_OK;
     }
+    // rn_debug_stream_info (include/rapidnet_debug.h): what stream_split_setup() decided, for the tests of the split last round
+    int stream_info(int *out) override {
+        RN_CHECK(out, RN_E_ARG, "rn_debug_stream_info: null output");
+        out[0] = splitFirst; out[1] = splitFirst >= 0 && splitFirst < d.nodes ? splitSpanHalf : 0;
+        out[2] = streamTwoPerCU ? 1 : 0; out[3] = numCUs;
+        return RN_OK;
+    }
     int counters(long *out) override {
         RN_CHECK(out, RN_E_ARG, "rn_get_counters: null output");
         out[0] = optBatches; out[1] = exactBatches; out[2] = fallbacks; out[3] = optHold;
@@ -2838,6 +2846,7 @@ int rn_debug_local_group_destroy(void *group) { if (!group) return RN_E_ARG; del
 int rn_debug_inject_allocation(rn_ctx *ctx, size_t bytes) { RN_GUARD(ctx); return ctx->impl->inject_allocation(bytes); }
 int rn_debug_guard_poke(rn_ctx *ctx, int nbytes) { RN_GUARD(ctx); return ctx->impl->guard_poke(nbytes); }
 int rn_debug_set_knob(rn_ctx *ctx, int knob, int value) { RN_GUARD(ctx); return ctx->impl->set_knob(knob, value); }
+int rn_debug_stream_info(rn_ctx *ctx, int info[4]) { RN_GUARD(ctx); return ctx->impl->stream_info(info); }
 int rn_debug_peer_seq(rn_ctx *ctx, unsigned int seq) { RN_GUARD(ctx); return ctx->impl->debug_peer_seq(seq); }
 int rn_guard_report(long out[2]) { if (!out) return RN_E_ARG; out[0] = rn::g_guardContexts.load(); out[1] = rn::g_guardBadBytes.load(); return RN_OK; }
 int rn_peer_inbox_create(rn_ctx *ctx, void *ipcHandle64) { RN_GUARD(ctx); return ctx->impl->peer_inbox_create(ipcHandle64); }

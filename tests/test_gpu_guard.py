@@ -14,6 +14,7 @@ import pytest
 import test_gpu_fbe_nama as fbe
 import test_gpu_parity as par
 import test_gpu_sharded_batched as shb
+import test_gpu_stream_split as spl
 from rapidnet_amd import capi, synth
 
 pytestmark = pytest.mark.gpu
@@ -100,6 +101,20 @@ def test_fbe_nama_loops_under_guard(guard, alg):
     fbe.test_loop_matches_oracle("medium", True, alg)
     fbe.test_line_search_direction_rule(alg, "positive")
     guard["contexts"] = 4
+
+
+@pytest.mark.parametrize("cases", [(("b236", "three", "f64"), ("nv129", "two", "f64"))])
+def test_split_last_round_under_guard(guard, cases):
+    """k_stream_gemv's split last round: the second halves' partials in my2 (r * 2 nv values, indexed by node - splitFirst), the second
+    half's first group requested unconditionally and clamped into the block -- on the tree with an odd group count and a ragged last
+    span, and on the one with three slots per thread"""
+    spl.num_cus()            # (its throw-away context is not one of the two counted below)
+    before = capi.guard_report()[0]
+    for net, pos, precision in cases:
+        spl.test_split_round_matches_the_oracle(net, pos, precision)
+    gc.collect()
+    assert capi.guard_report()[0] - before == len(cases)
+    guard["contexts"] = len(cases)
 
 
 def test_barcelona31_under_guard(guard):
