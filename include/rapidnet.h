@@ -129,6 +129,20 @@ int rn_synchronize(rn_ctx *ctx);
 enum { RN_OPS_DENSE = 0, RN_OPS_STRUCTURED = 1, RN_OPS_AUTO = 2 };
 int rn_set_operator_mode(rn_ctx *ctx, int mode);
 int rn_get_operator_mode(rn_ctx *ctx, int *requested, int *active);
+/* Element type of the DENSE per-node blocks, to be chosen BEFORE rn_factor_step (afterwards: RN_E_STATE; an unknown value: RN_E_ARG).
+ *   RN_STORE_NATIVE (the default): the blocks are stored in the context's precision.
+ *   RN_STORE_F32: an RN_F64 context stores them in fp32 -- the reference's own element type (Configuration.h:31) and half the bytes the
+ *     dominant kernel streams -- while every vector stays fp64 and every sum over a block is accumulated in fp64: the iterates are the fp64
+ *     solution of the problem WITH THE ROUNDED BLOCKS (to 1e-9 against an fp64 oracle given the same blocks), and the problem itself is
+ *     perturbed by at most 2^-24 relative (6e-8) per block entry.  rn_get_operator returns the stored values (fp32-representable doubles);
+ *     rn_set_operator rounds the caller's block to nearest fp32 on upload.  On an RN_F32 context the value is accepted and changes nothing.
+ *     The quasi-Newton loops run their two Hessian sweeps one after the other in this mode (no shared pass over the blocks).
+ * The setting concerns the dense blocks only: under RN_OPS_STRUCTURED it is remembered and has no effect, under RN_OPS_AUTO it takes effect
+ * when the first rn_set_operator materialises the blocks.
+ * rn_get_operator_storage: *requested = what was asked for, *active = RN_STORE_F32 only while dense blocks exist in fp32. */
+enum { RN_STORE_NATIVE = 0, RN_STORE_F32 = 1 };
+int rn_set_operator_storage(rn_ctx *ctx, int storage);
+int rn_get_operator_storage(rn_ctx *ctx, int *requested, int *active);
 
 /* ---- Engine -------------------------------------------------------------------------------------- */
 /* Engine::factorStep (Engine.cu:671-774) incl. initialiseSystemDevice / preconditioning kernels. */
@@ -230,14 +244,14 @@ int rn_set(rn_ctx *ctx, int buffer_id, const double *host, size_t n);
  * RN_BUF_UMAX and the FBE vectors) are addressed in whole nodes (first and n multiples of the per-node dimension) */
 int rn_get_range(rn_ctx *ctx, int buffer_id, size_t first, size_t n, double *host);
 int rn_set_range(rn_ctx *ctx, int buffer_id, size_t first, size_t n, const double *host);
-/* one node's operator block, reference layout (col-major, ld = nv) */
+/* one node's operator block, reference layout (col-major, ld = nv): the values as stored (RN_STORE_F32: fp32-representable doubles) */
 int rn_get_operator(rn_ctx *ctx, int op_id, int node, double *host, size_t n);
 /* ... and its counterpart: a block handed in by the caller (the reference's Engine returns the device pointers of these arrays,
  * Engine.cuh:170-230 getMatPhi() ... getPtrMatF(), so its callers may overwrite any block).  RN_OP_PHI, _PSI, _D, _F of one node -- the
  * blocks solveStep multiplies with (SmpcController.cu:617-638); the next sweep uses them.  After rn_factor_step; a later rn_factor_step
  * recomputes every block.  RN_OPS_AUTO contexts switch to dense storage on the first call; RN_OPS_STRUCTURED contexts (no per-node
  * blocks by request): RN_E_STATE.  Omega_i, Theta_i, G_i are shared matrices scaled by p_i here (K identical copies in the reference,
- * Engine.cu:306-308): RN_E_ARG. */
+ * Engine.cu:306-308): RN_E_ARG.  A context with RN_STORE_F32 blocks rounds the caller's values to the nearest fp32 on upload. */
 int rn_set_operator(rn_ctx *ctx, int op_id, int node, const double *host, size_t n);
 /* The raw device pointer of a buffer that the library keeps in the reference's own layout -- the counterpart of the reference's raw
  * getters and protected device vectors for those arrays (Engine.cuh:108-318 getVecUhat / getVecBeta / getVecE / getPriceAlpha ...,
@@ -264,7 +278,8 @@ int rn_profile_read(rn_ctx *ctx, double ms[4], long launches[4]);
  * stand-in) since the last rn_profile_reset -- wire latency plus the wait for the slowest peer; these intervals lie INSIDE
  * class 1 of rn_profile_read. */
 int rn_profile_read_collective(rn_ctx *ctx, double *ms, long *launches);
-/* algorithmic HBM bytes of ONE launch of the dominant kernels, as defined in DESIGN.md */
+/* algorithmic HBM bytes of ONE launch of the dominant kernels, as defined in DESIGN.md (RN_STORE_F32 blocks under fp64 iterates: the
+ * block entries at 4 bytes, the vectors at 8) */
 int rn_algorithmic_bytes(const rn_ctx *ctx, double *backwardStageBytesTotal, double *dualUpdateBytes);
 /* which kernels an iteration of this context launches: info = {1 if k_dual_stage is the main pass of the fused dual update
  * (0: the flat k_dual_fused), its workgroups, vectors per thread, pipeline depth, k_stream_gemv columns per span, slots per

@@ -156,6 +156,7 @@ def hip_fingerprint():
 LIB_HOST = os.path.join(HERE, "librapidnet_host.so")
 BIN_DIR = os.path.join(HERE, "bin")
 TEST_HOST = os.path.join(BIN_DIR, "test_host")
+TEST_OPERATOR_STORAGE = os.path.join(BIN_DIR, "test_operator_storage")
 
 
 def build_host(force=False):
@@ -175,6 +176,11 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-pthread", "-o", TEST_HOST, test_src, "-L" + HERE, "-lrapidnet_host",
                                "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
         _stamp(TEST_HOST, [test_src] + deps + hdr)
+    test_src = os.path.join(ROOT, "tests", "cpp", "test_operator_storage.cpp")
+    if force or _stale(TEST_OPERATOR_STORAGE, [test_src] + deps + hdr):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_OPERATOR_STORAGE, test_src, "-L" + HERE, "-lrapidnet_host",
+                               "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
+        _stamp(TEST_OPERATOR_STORAGE, [test_src] + deps + hdr)
     return LIB_HOST
 
 

@@ -89,7 +89,7 @@
             d_S0 = d_S; d_Yv0 = d_Yv;
             h_rho.assign((size_t)bufferSize + 1, 0.0);
         }
-        if (alg == RN_ALG_NAMA && !d_myB && !structured) {
+        if (alg == RN_ALG_NAMA && !d_myB && !structured && !store32()) {      // (fp32 block storage has no paired pass: stream_pair_ok)
             const size_t n = (size_t)ntot(), N_ = d.nodes;
             bool want = true;
             if (knob[RN_KNOB_NAMA_PAIR] == 0) want = false;      // A/B runs, tests: the two sweeps one after the other

@@ -148,6 +148,14 @@ SmpcConfiguration::SmpcConfiguration(string pathToFile) {
         if (operatorMode != "auto" && operatorMode != "dense" && operatorMode != "structured")
             throw std::logic_error("controller configuration: operatorMode must be \"auto\", \"dense\" or \"structured\" (got \"" + operatorMode + "\")");
     }
+    // ... and in which element type it keeps the dense blocks (absent = "native": the engine's precision)
+    operatorStorage = "native";
+    if (doc.HasMember("operatorStorage")) {
+        _ASSERT(doc["operatorStorage"].IsString());
+        operatorStorage = doc["operatorStorage"].str;
+        if (operatorStorage != "native" && operatorStorage != "f32")
+            throw std::logic_error("controller configuration: operatorStorage must be \"native\" or \"f32\" (got \"" + operatorStorage + "\")");
+    }
     lbfgsBufferSize = scalarInt(doc, "lbfgsBufferSize");
     pathToConfiguration = pathToFile;
     // relative paths in the configuration are relative to the configuration file's directory when they do not

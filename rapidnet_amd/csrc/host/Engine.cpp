@@ -49,6 +49,12 @@ int Engine::getOperatorMode() {
     check(rn_get_operator_mode(ctx, nullptr, &active), "rn_get_operator_mode");
     return active;
 }
+void Engine::setOperatorStorage(int storage) { check(rn_set_operator_storage(ctx, storage), "rn_set_operator_storage"); }
+int Engine::getOperatorStorage() {
+    int active = RN_STORE_NATIVE;
+    check(rn_get_operator_storage(ctx, nullptr, &active), "rn_get_operator_storage");
+    return active;
+}
 void Engine::setOperator(int op, uint_t node, const real_t *host, size_t n) { check(rn_set_operator(ctx, op, node, host, n), "rn_set_operator"); }
 
 void Engine::create(int precision, int device, int operatorMode, int rank, int nranks, const void *id128, int cutStage) {
@@ -80,6 +86,7 @@ void Engine::create(int precision, int device, int operatorMode, int rank, int n
         operatorMode = m == "dense" ? RN_OPS_DENSE : (m == "structured" ? RN_OPS_STRUCTURED : RN_OPS_AUTO);
     }
     check(rn_set_operator_mode(ctx, operatorMode), "rn_set_operator_mode");
+    if (ptrMySmpcConfig->getOperatorStorage() == "f32") check(rn_set_operator_storage(ctx, RN_STORE_F32), "rn_set_operator_storage");
     // SmpcController::allocateApgAlgorithm (SmpcController.cu:124-151): per-iteration storage for maxIterations, allocated once
     check(rn_reserve_iterations(ctx, (int)ptrMySmpcConfig->getMaxIterations()), "rn_reserve_iterations");
     if (!apgFlag)   // SmpcController::allocateGlobalFbeAlgorithm / allocateNamaAlgorithm / allocateLbfgsBuffer (SmpcController.cu:234-330)

@@ -36,6 +36,11 @@ public:
            const void *ncclUniqueId128, int cutStage = 0, int operatorMode = -1);
     void setOperatorMode(int mode);                  // RN_OPS_AUTO / _DENSE / _STRUCTURED; before factorStep()
     int getOperatorMode();                           // what the engine runs: RN_OPS_DENSE or RN_OPS_STRUCTURED
+    // element type of the dense blocks (rapidnet.h, rn_set_operator_storage): RN_STORE_NATIVE or RN_STORE_F32 -- fp32 blocks under fp64 iterates,
+    // half the bytes per iteration, every sum in fp64.  The constructors take it from the configuration file's optional "operatorStorage" key
+    // ("native" | "f32"; absent: native).  Before factorStep().
+    void setOperatorStorage(int storage);
+    int getOperatorStorage();                        // RN_STORE_F32 while the engine holds dense blocks in fp32, else RN_STORE_NATIVE
     // a per-node block handed in by the caller (the reference: write through getMatPhi() / getPtrMatPhi()[node] ..., Engine.cuh:170-230);
     // RN_OP_PHI, _PSI, _D, _F, col-major nv x (2nx | nu); after factorStep()
     void setOperator(int opId, uint_t node, const real_t *host, size_t n);

@@ -30,20 +30,22 @@ __global__ void __launch_bounds__(256) k_bw_copy(const nat_d2 *src, nat_d2 *dst,
 //   Phi_i(:,c) = -T1(:,j) d_c / (2 sqrt p_i),  D_i(:,c)    = Bbt(:,j) sqrt(p_i) d_c     c = xi column of tank j
 //   Psi_i(:,c) = -T2(:,j) d_c / (2 sqrt p_i),  Ftil_i(:,c) = Lt(:,j)  sqrt(p_i) d_c     c = psi column of input j
 // with T1 = Rinv Bbt, T2 = Rinv L'.  One workgroup per (node, column); pure streaming store.
-template <typename T>
+// S: the element type the blocks are stored in (fp32 under fp64 iterates, rn_set_operator_storage: the formulas are evaluated in T and every
+// entry is rounded once, to nearest, on its way out; a.LD and a.strideA count entries of S)
+template <typename T, typename S = T>
 struct ExpandArgs {
     TreeDev<T> tr;
     int nx, nu, nv, ny, LD, nodes;
     size_t strideA;
     const T *T1, *T2, *Bbt, *Lt;
-    T *A;
+    S *A;
     // scaled bounds in y order
     int skipBlocks;       // structured operator mode: only the scaled bounds are produced
     const T *blo, *bhi;   // [ny] unscaled: xmin|xsafe|umin and xmax|+BIG|umax
     T *lo, *hi;           // [node][ny]
 };
-template <typename T>
-__global__ void k_expand_operators(ExpandArgs<T> a) {
+template <typename T, typename S = T>
+__global__ void k_expand_operators(ExpandArgs<T, S> a) {
     const int node = blockIdx.x;
     const int stage = a.tr.stageOf[node];
     const T sp = a.tr.sqrtp[node];
@@ -55,9 +57,9 @@ __global__ void k_expand_operators(ExpandArgs<T> a) {
         if (c < 2 * a.nx) { const int j = c % a.nx; m1 = a.T1 + (size_t)j * a.nv; m2 = a.Bbt + (size_t)j * a.nv; }
         else { const int j = c - 2 * a.nx; m1 = a.T2 + (size_t)j * a.nv; m2 = a.Lt + (size_t)j * a.nv; }
         if (!a.skipBlocks) {
-            T *col = a.A + (size_t)node * a.strideA + (size_t)c * a.LD;
+            S *col = a.A + (size_t)node * a.strideA + (size_t)c * a.LD;
             for (int r = threadIdx.x; r < a.LD; r += blockDim.x)
-                col[r] = r < a.nv ? s1 * m1[r] : (r < 2 * a.nv ? s2 * m2[r - a.nv] : (T)0);
+                col[r] = (S)(r < a.nv ? s1 * m1[r] : (r < 2 * a.nv ? s2 * m2[r - a.nv] : (T)0));
         }
         if (threadIdx.x == 0) {
             // bound scaling: preconditionConstraintX/U.  "+BIG" stays +BIG (no upper bound on the safety half)

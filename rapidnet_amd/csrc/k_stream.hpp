@@ -204,6 +204,141 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// The same launch for an fp64 context whose blocks are STORED in fp32 (rn_set_operator_storage(RN_STORE_F32)):
+// half the bytes of the only large thing in HBM, every sum still formed in fp64.  a.A points at floats here: a.LD is 2nv rounded up
+// to four floats, a.strideA counts floats (whole lines of 32), G and NL are the host's choice for 4-byte elements (Ctx::stream_shape)
+// -- the block is walked exactly as the fp32 context walks its own: 16-byte slots of FOUR floats, every wave-load one contiguous
+// kilobyte, spans of whole 128-byte lines, non-temporal, double-buffered in groups of D spans.  What differs from k_stream_gemv<float>
+// is everything behind the load: the lane converts its four floats (exact) and accumulates part[NL][4] in double against the double
+// sh_y; the fold over the span's columns and the outputs my / my2 / qa are double and go where k_stream_gemv<double> puts them, so no
+// consumer knows about the storage.  The order in which a row meets its columns is that of the fp32 context's kernel (same G).
+// Prologue order, the clamp of the first group and the branch-free steady state: as above, for the reasons given there.
+// One right-hand side only: with fp32 storage the quasi-Newton loops' two Hessian sweeps run one after the other (Ctx::stream_pair_ok).
+// LDS: (ny + G * LD) doubles.  HBM bytes per node: LD*ny*4 + (ny + 2nv + nx)*8.
+// Registers (hipcc's resource report, SPLIT = false | true): NL = 1: 72 | 70 VGPRs, NL = 2: 154 | 146, NL = 3: 156 | 156, NL = 4: 208 | 210; no scratch --
+// three waves per SIMD at NL = 2, like k_stream_gemv<float, 2, *> (146 | 130).
+template <int NL, bool SPLIT>
+__global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_mixed(SweepArgs<double> a, int G, int node0, StreamSplit<double> sp) {
+    typedef double T;
+    typedef nat_f4 VT;
+    constexpr int VPL = 4, D = NL <= 2 ? RN_STREAM_D : RN_STREAM_D_WIDE;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    T *sh_y = reinterpret_cast<T *>(smem_raw);          // ny
+    T *sh_red = sh_y + ((a.ny + 3) & ~3);               // G * LD
+    const int tid = threadIdx.x;
+    const bool split = SPLIT && (int)blockIdx.x >= sp.first;
+    const int node = split ? sp.first + (((int)blockIdx.x - sp.first) >> 1) : (int)blockIdx.x;
+    const bool second = split && ((((int)blockIdx.x - sp.first) & 1) != 0);
+    const int nx = a.nx, nv = a.nv, ny = a.ny, LD = a.LD;
+    const int SPC = LD / VPL, spanSlots = G * SPC;
+    const long long blockSlots = (long long)ny * SPC;
+    const VT *__restrict__ Ab = reinterpret_cast<const VT *>(reinterpret_cast<const float *>(a.A) + (size_t)node * a.strideA);
+    const int spansAll = (ny + G - 1) / G;
+    const int span0 = SPLIT ? (second ? sp.spanHalf : 0) : 0, span1 = (split && !second) ? sp.spanHalf : spansAll;
+    int off[NL], cj[NL];
+    T msk[NL];
+#pragma unroll
+    for (int j = 0; j < NL; j++) {
+        const int q = tid + STREAM_THREADS * j;
+        const bool ok = q < spanSlots;
+        off[j] = ok ? q : spanSlots - 1;          // idle slots re-read the last slot of the span and multiply by zero
+        cj[j] = off[j] / SPC;
+        msk[j] = ok ? (T)1 : (T)0;
+    }
+    T part[NL][VPL];
+#pragma unroll
+    for (int j = 0; j < NL; j++)
+#pragma unroll
+        for (int e = 0; e < VPL; e++) part[j][e] = 0;
+    const int nFull = (ny / G < span1 ? ny / G : span1) - span0;   // spans of this workgroup made of G whole columns
+    const int nGroups = nFull / D;
+    VT bufA[D][NL], bufB[D][NL];
+#define RN_LOADG(buf, g_)                                                                                              \
+    _Pragma("unroll") for (int d = 0; d < D; d++)                                                                      \
+        _Pragma("unroll") for (int j = 0; j < NL; j++)                                                                 \
+            buf[d][j] = __builtin_nontemporal_load(Ab + (size_t)(span0 + (g_) * D + d) * spanSlots + off[j]);
+#define RN_USEG(buf, g_)                                                                                               \
+    _Pragma("unroll") for (int d = 0; d < D; d++)                                                                      \
+        _Pragma("unroll") for (int j = 0; j < NL; j++) {                                                               \
+            const T yc = sh_y[(span0 + (g_) * D + d) * G + cj[j]] * msk[j];                                            \
+            _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] += (T)buf[d][j][e] * yc;                        \
+        }
+    const bool has0 = tid < ny;
+    const size_t i0 = (size_t)node * ny + (has0 ? tid : 0);
+    const int stage = node >= node0 ? a.chainStage + (node - node0) / a.K : a.tr.stageOf[node];
+    const T *dyRow = a.tr.dy + (size_t)stage * ny;
+    const T spn = a.tr.sqrtp[node];
+    const int tq = tid < nx ? tid : 0;
+    const T dq0 = dyRow[tq], dq1 = dyRow[nx + tq];    // for a_i below
+    const T w0a = a.w[i0];      // the y column: the accelerated dual the sweep is evaluated at
+    asm volatile("" ::: "memory");   // keep the request order: the small loads first, the group right behind them
+    {
+        const int lastSlot = (int)blockSlots - 1;
+#pragma unroll
+        for (int d = 0; d < D; d++)
+#pragma unroll
+            for (int j = 0; j < NL; j++) {
+                const int sl = (span0 + d) * spanSlots + off[j];
+                bufA[d][j] = __builtin_nontemporal_load(Ab + (sl < lastSlot ? sl : lastSlot));   // clamped into the block: never behind its last slot
+            }
+    }
+    asm volatile("" ::: "memory");
+    T qa0 = 0;      // a_i is stored at the end of the kernel (stores count in the loads' in-order counter)
+    if (has0) sh_y[tid] = w0a;
+    for (int c = tid + STREAM_THREADS; c < ny; c += STREAM_THREADS) sh_y[c] = a.w[(size_t)node * ny + c];
+    __syncthreads();
+    // a_i = F_i' xi_i = sqrt(p_i) (d_x o xi_box + d_xs o xi_safe)      (a split block: written by its first half)
+    if (tid < nx) qa0 = stream_qa_elem(spn, dq0, sh_y[tid], dq1, sh_y[nx + tid]);
+    if (!second) for (int t = tid + STREAM_THREADS; t < nx; t += STREAM_THREADS)
+        a.qa[(size_t)node * nx + t] = stream_qa_elem(spn, dyRow[t], sh_y[t], dyRow[nx + t], sh_y[nx + t]);
+    if (nGroups > 0) {
+        int g = 0;
+        for (; g + 2 < nGroups; g += 2) {      // no branch inside: exact vmcnt waits, group g+1 (then g+2) in flight while g is consumed
+            RN_LOADG(bufB, g + 1)
+            RN_USEG(bufA, g)
+            RN_LOADG(bufA, g + 2)
+            RN_USEG(bufB, g + 1)
+        }
+        if (g + 1 < nGroups) {
+            RN_LOADG(bufB, g + 1)
+            RN_USEG(bufA, g)
+            RN_USEG(bufB, g + 1)
+        } else {
+            RN_USEG(bufA, g)
+        }
+    }
+#undef RN_LOADG
+#undef RN_USEG
+    // remaining whole spans and the last, partial one (ny % G columns): guarded
+    for (int s = span0 + nGroups * D; s < span1; s++) {
+#pragma unroll
+        for (int j = 0; j < NL; j++) {
+            const int c = s * G + cj[j];
+            const long long slot = (long long)s * spanSlots + off[j];
+            const bool live = msk[j] != (T)0 && c < ny && slot < blockSlots;
+            const VT v = __builtin_nontemporal_load(Ab + (live ? slot : 0));
+            const T yc = live ? sh_y[c] : (T)0;
+#pragma unroll
+            for (int e = 0; e < VPL; e++) part[j][e] += (T)v[e] * yc;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < NL; j++)
+        if (msk[j] != (T)0) {
+#pragma unroll
+            for (int e = 0; e < VPL; e++) sh_red[(size_t)off[j] * VPL + e] = part[j][e];
+        }
+    if (tid < nx && !second) stream_out(qa0, a.qa + (size_t)node * nx + tid);
+    __syncthreads();
+    T *const myOut = second ? sp.my2 + (size_t)(node - sp.first) * 2 * nv : a.my + (size_t)node * 2 * nv;
+    for (int r = tid; r < 2 * nv; r += STREAM_THREADS) {    // slot q of a span = column q / SPC, rows (q % SPC) * VPL ...
+        T s = sh_red[r];
+        for (int k = 1; k < G; k++) s += sh_red[(size_t)k * LD + r];
+        stream_out(s, myOut + r);
+    }
+}
+
 // Structured operator mode ("shared-operator model"): every per-node block of the factor step
 // is (shared matrix) x (stage diagonal) x (power of p_i)  --  D_i = Bbt F_i', Ftil_i = L' G_i', Phi_i = -Omega_i D_i / 2,
 // Psi_i = -Omega_i Ftil_i / 2 (Engine.cu:721-745) with F_i, G_i diagonal (Utilities.cu:33-58).  Hence

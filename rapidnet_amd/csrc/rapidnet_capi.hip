@@ -223,6 +223,8 @@ struct CtxBase {
     virtual int stream_info(int *) = 0;
     virtual int debug_peer_seq(unsigned int) = 0;
     virtual int fbe_counters(long *) = 0;
+    virtual int set_operator_storage(int) = 0;
+    virtual int get_operator_storage(int *, int *) = 0;
 };
 
 // ---- in-process stand-in for the communicator (rn_debug_local_group_*): `n` contexts of one process, one host thread each ----
@@ -349,6 +351,19 @@ struct Ctx : CtxBase {
     // (the default) is structured for as long as every block is the factor step's own -- block = shared matrix x stage diagonal x power
     // of p_i, Engine.cu:721-745 -- and becomes dense the moment a caller hands in a block of its own (rn_set_operator: materialise_dense)
     int opsMode = RN_OPS_AUTO, structured = 1, warmStart = 0;
+    // Element type of the dense blocks (rn_set_operator_storage).  RN_STORE_F32 on an fp64 context: the blocks live in d_A32 as floats -- LD,
+    // strideA and the streaming kernel's span follow the 4-byte element -- and k_stream_gemv_mixed accumulates them in fp64; every other buffer
+    // and every other kernel is the fp64 context's.  On an fp32 context the request changes nothing (its blocks are floats already).
+    int storeReq = RN_STORE_NATIVE;
+    float *d_A32 = nullptr;
+    bool store32() const { return sizeof(T) == 8 && storeReq == RN_STORE_F32; }
+    int block_elem() const { return store32() ? 4 : (int)sizeof(T); }      // bytes of one stored block entry
+    void block_layout() {   // columns are whole 16-byte slots, node blocks whole 128-byte lines (k_stream_gemv walks a block in slots and
+                            // its spans are only line-aligned if the block is)
+        const int vps = 16 / block_elem(), vpl = 128 / block_elem();
+        LD = (2 * d.nv + vps - 1) / vps * vps;
+        strideA = ((size_t)ny * LD + vpl - 1) / vpl * vpl;
+    }
     struct SavedSystem { std::vector<double> B, Gd, L, Lhat, W, diag, xmin, xmax, xsafe, umin, umax, alpha1; } h_sys;   // the factor step's inputs (AUTO: for the dense re-factor)
     int optimistic = 1;      // multi-GPU: 1 = one collective per iteration + verification, 0 = exact two-collective path
     // What one iteration of an rn_apg_iterate batch hands to the next: run_batch owns it, launch_sweep and launch_dual_main read and consume
@@ -567,6 +582,25 @@ struct Ctx : CtxBase {
         for (size_t i = 0; i < n; i++) dst[i] = (double)tmp[i];
         return RN_OK;
     }
+    // one node's block [ny][LD] in the element type it is stored in (fp32 storage: rounded to nearest on the way in)
+    int upload_block(int node, const double *src) {
+        const size_t n = (size_t)ny * LD;
+        if (!store32()) return upload(d_A + (size_t)node * strideA, src, n);
+        std::vector<float> tmp(n);
+        for (size_t i = 0; i < n; i++) tmp[i] = (float)src[i];
+        RN_HIP(hipMemcpyAsync(d_A32 + (size_t)node * strideA, tmp.data(), n * sizeof(float), hipMemcpyHostToDevice, stream));
+        RN_HIP(hipStreamSynchronize(stream));
+        return RN_OK;
+    }
+    int download_block(int node, double *dst) {
+        const size_t n = (size_t)ny * LD;
+        if (!store32()) return download(dst, d_A + (size_t)node * strideA, n);
+        std::vector<float> tmp(n);
+        RN_HIP(hipMemcpyAsync(tmp.data(), d_A32 + (size_t)node * strideA, n * sizeof(float), hipMemcpyDeviceToHost, stream));
+        RN_HIP(hipStreamSynchronize(stream));
+        for (size_t i = 0; i < n; i++) dst[i] = (double)tmp[i];
+        return RN_OK;
+    }
     int upload_int(int *dst, const std::vector<int> &v) {
         RN_HIP(hipMemcpy(dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice));
         return RN_OK;
@@ -639,7 +673,7 @@ struct Ctx : CtxBase {
         a.cutStage = cutStage;
         a.chainStage = a.cutSums ? std::max(chainStage, cutStage) : chainStage;
         a.K = h_stageCum[a.chainStage + 1] - h_stageCum[a.chainStage];
-        a.A = d_A; a.RT = d_RTp; a.L = d_L; a.B = d_B; a.structured = structured; a.ab = d_ab;
+        a.A = store32() ? reinterpret_cast<const T *>(d_A32) : d_A; a.RT = d_RTp; a.L = d_L; a.B = d_B; a.structured = structured; a.ab = d_ab;
         a.lin = (lin_on() && cutStage <= 0) ? 1 : 0; a.sk2 = d_sk2; a.rkq2 = d_rkq2;
         a.beta = d_beta; a.uhat = d_uhat; a.e = d_e; a.curX = d_curX; a.prevU = d_prevU; a.prevUhat = d_prevUhat;
         a.w = p_acc;
@@ -697,12 +731,7 @@ struct Ctx : CtxBase {
         RN_CHECK(d.nx > 0 && d.nu > 0 && d.nv > 0 && d.nd > 0 && d.N > 0 && d.K > 0 && d.nodes > 0, RN_E_ARG, "rn_create: non-positive dimension");
         RN_CHECK(d.nv <= d.nu, RN_E_ARG, "rn_create: nv must not exceed nu");
         ny = 2 * d.nx + d.nu;
-        {   // columns are whole 16-byte slots, node blocks whole 128-byte lines (k_stream_gemv walks a block in slots and
-            // its spans are only line-aligned if the block is)
-            const int vps = 16 / (int)sizeof(T), vpl = 128 / (int)sizeof(T);
-            LD = (2 * d.nv + vps - 1) / vps * vps;
-            strideA = ((size_t)ny * LD + vpl - 1) / vpl * vpl;
-        }
+        block_layout();
         RN_HIP(hipSetDevice(device));
         RN_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cu > 0) numCUs = cu; }
@@ -906,15 +935,26 @@ struct Ctx : CtxBase {
 #undef UP
         if (d_Wp) { if (int rc = upload_padded(d_Wp, s->costW, nu, nu)) return rc; }   // k_value_mfma's copy of W (rn_set_algorithm may come before the factor step)
         if (int rc = stream_split_setup()) return rc;
-        if (!structured && !d_A) {   // the dense per-node blocks are only allocated when they are used
-            if (int rc = dalloc(&d_A, (size_t)d.nodes * strideA)) return rc;
+        if (!structured && !d_A && !d_A32) {   // the dense per-node blocks are only allocated when they are used
+            if (store32()) { if (int rc = dalloc(&d_A32, (size_t)d.nodes * strideA)) return rc; }
+            else if (int rc = dalloc(&d_A, (size_t)d.nodes * strideA)) return rc;
         }
         RN_HIP(hipMemsetAsync(d_my, 0, (size_t)d.nodes * 2 * nv * sizeof(T), stream));   // structured mode never writes m1
         ExpandArgs<T> ea{};
         ea.tr = tree_dev(); ea.nx = nx; ea.nu = nu; ea.nv = nv; ea.ny = ny; ea.LD = LD; ea.strideA = strideA; ea.nodes = d.nodes;
         ea.T1 = d_T1; ea.T2 = d_T2; ea.Bbt = d_Bbt; ea.Lt = d_Lt; ea.A = d_A; ea.skipBlocks = structured; ea.blo = d_blo; ea.bhi = d_bhi; ea.lo = d_lo; ea.hi = d_hi;
         const int colChunks = std::min(ny, 8);
-        hipLaunchKernelGGL(k_expand_operators<T>, dim3(d.nodes, colChunks), dim3(LD >= 192 ? 256 : (LD >= 96 ? 128 : 64)), 0, stream, ea);
+        bool expanded = false;
+        if constexpr (sizeof(T) == 8) {
+            if (store32() && !structured) {   // the same formulas evaluated in double, every entry rounded once on its way into the fp32 block
+                ExpandArgs<double, float> ef{};
+                ef.tr = ea.tr; ef.nx = nx; ef.nu = nu; ef.nv = nv; ef.ny = ny; ef.LD = LD; ef.strideA = strideA; ef.nodes = d.nodes;
+                ef.T1 = d_T1; ef.T2 = d_T2; ef.Bbt = d_Bbt; ef.Lt = d_Lt; ef.A = d_A32; ef.skipBlocks = structured; ef.blo = d_blo; ef.bhi = d_bhi; ef.lo = d_lo; ef.hi = d_hi;
+                hipLaunchKernelGGL((k_expand_operators<double, float>), dim3(d.nodes, colChunks), dim3(LD >= 192 ? 256 : (LD >= 96 ? 128 : 64)), 0, stream, ef);
+                expanded = true;
+            }
+        }
+        if (!expanded) hipLaunchKernelGGL(k_expand_operators<T>, dim3(d.nodes, colChunks), dim3(LD >= 192 ? 256 : (LD >= 96 ? 128 : 64)), 0, stream, ea);
         RN_HIP(hipGetLastError());
         factored = true;
         if (int rc = refresh_bounds_copies()) return rc;
@@ -1016,8 +1056,9 @@ struct Ctx : CtxBase {
     }
     int algorithmic_bytes(double *bwd, double *dual) const override {
         // k_stream_gemv, one launch = the whole tree: A_i (2nv x ny, unpadded) read once + y_i read + m1,m2,a_i written
-        const double s = sizeof(T), n = d.nodes;
-        if (bwd) *bwd = structured ? 0.0 : n * ((double)2 * d.nv * ny + ny + 2.0 * d.nv + d.nx) * s;
+        // (fp32 storage under fp64 iterates: the block at 4 bytes per entry, the vectors at 8)
+        const double s = sizeof(T), n = d.nodes, sa = block_elem();
+        if (bwd) *bwd = structured ? 0.0 : n * ((double)2 * d.nv * ny * sa + (ny + 2.0 * d.nv + d.nx) * s);
         // fused dual update: Hx, w, y+prev read, y+, w_next written (+ the two scaled-bound streams unless they are regenerated)
         if (dual) *dual = (RN_DUAL_REGEN ? 5.0 : 7.0) * (double)ntot() * s;
         return RN_OK;
@@ -1033,7 +1074,7 @@ struct Ctx : CtxBase {
     // -- with at most 2 slots per thread, then the best lane utilisation, then the larger span.  Without a line-aligned
     // candidate: the G that fills a multiple of STREAM_THREADS slots best.
     void stream_shape(int *G, int *NL) const {
-        const int SPC = LD * (int)sizeof(T) / 16;
+        const int SPC = LD * block_elem() / 16;      // (LD counts entries of the storage type)
         int bestG = 0, bestNL = 0, bestClass = -1; double bestU = -1;
         for (int g = 1; g <= std::min(ny, 64); g++) {
             const int slots = g * SPC, nl = (slots + STREAM_THREADS - 1) / STREAM_THREADS;
@@ -1072,7 +1113,7 @@ struct Ctx : CtxBase {
         // CU, ms per iteration: fp64 whole tree (42 rounds) 0.6733 | 0.6854, 1/2 shard 0.3712 | 0.3736, 1/4 shard (10.7 rounds)
         // 0.2101 | 0.2119, 1/8 shard (5.4 rounds) 0.1352 | 0.1318; fp32 whole tree 0.3838 | 0.3752 (the streaming kernel 313 -> 303 us
         // = 0.84 of the HBM peak).  So: fp32 always, fp64 for launches of fewer than 8 rounds.
-        streamTwoPerCU = sizeof(T) == 4 || d.nodes < 8 * numCUs;
+        streamTwoPerCU = sizeof(T) == 4 || store32() || d.nodes < 8 * numCUs;      // (fp32 storage: the fp32 context's block bytes, its rule)
         if (knob[RN_KNOB_STREAM_TWO_PER_CU] >= 0) streamTwoPerCU = knob[RN_KNOB_STREAM_TWO_PER_CU] != 0;
         if (!mode || !streamTwoPerCU || structured || d.nodes <= numCUs || r == 0 || 2 * r > numCUs || groups < 2) return RN_OK;
         if (d.N - cs < STREAM_SPLIT_STAGES || r > STREAM_SPLIT_STAGES * K) return RN_OK;     // (the cut never moves the chain region's END)
@@ -1087,6 +1128,10 @@ struct Ctx : CtxBase {
             for (const void *fn : {(const void *)k_stream_gemv<T, 1, false>, (const void *)k_stream_gemv<T, 2, false>, (const void *)k_stream_gemv<T, 3, false>, (const void *)k_stream_gemv<T, 4, false>,
                                    (const void *)k_stream_gemv<T, 1, true>, (const void *)k_stream_gemv<T, 2, true>, (const void *)k_stream_gemv<T, 3, true>, (const void *)k_stream_gemv<T, 4, true>})
                 all = all && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+            if constexpr (sizeof(T) == 8)
+                for (const void *fn : {(const void *)k_stream_gemv_mixed<1, false>, (const void *)k_stream_gemv_mixed<2, false>, (const void *)k_stream_gemv_mixed<3, false>, (const void *)k_stream_gemv_mixed<4, false>,
+                                       (const void *)k_stream_gemv_mixed<1, true>, (const void *)k_stream_gemv_mixed<2, true>, (const void *)k_stream_gemv_mixed<3, true>, (const void *)k_stream_gemv_mixed<4, true>})
+                    all = all && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
             return all;
         }();
         return ok;
@@ -1102,6 +1147,27 @@ struct Ctx : CtxBase {
         const StreamSplit<T> sp{a.splitFirst, splitSpanHalf, d_my2};
         const int grid = d.nodes + (d.nodes - a.splitFirst);      // two workgroups for every block of the split round
         const StreamRhs2<T> none{nullptr, nullptr, nullptr};
+        if constexpr (sizeof(T) == 8) {
+            if (store32()) {   // fp32 blocks under fp64 iterates (k_stream_gemv_mixed): one right-hand side, split or not
+                RN_CHECK(!second, RN_E_STATE, "k_stream_gemv_mixed: one right-hand side only");
+                if (streamTwoPerCU) {
+                    switch (NL) {
+                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
+                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
+                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
+                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
+                    }
+                } else {
+                    switch (NL) {
+                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
+                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
+                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
+                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
+                    }
+                }
+                return RN_OK;
+            }
+        }
         if (second) {
             RN_CHECK(a.splitFirst >= d.nodes && 2 * lds <= 64 * 1024, RN_E_STATE, "k_stream_gemv with two right-hand sides: unsplit launches only");
             switch (NL) {
@@ -1127,11 +1193,12 @@ struct Ctx : CtxBase {
         }
         return RN_OK;
     }
-    // two right-hand sides in one streaming pass are possible for: dense per-node blocks, no split last round, both LDS sets in 64 KB
+    // two right-hand sides in one streaming pass are possible for: dense per-node blocks in the context's own type (k_stream_gemv_mixed has no
+    // NR = 2 form: with fp32 storage the pair runs as two sweeps), no split last round, both LDS sets in 64 KB
     bool stream_pair_ok() const {
         int G, NL;
         stream_shape(&G, &NL);
-        return !structured && !(splitFirst >= 0 && splitFirst < d.nodes) && 2 * stream_lds(G) <= 64 * 1024;
+        return !structured && !store32() && !(splitFirst >= 0 && splitFirst < d.nodes) && 2 * stream_lds(G) <= 64 * 1024;
     }
     static int slab_stride(int kp) { return (kp + 59) / 64 * 64 + 4; }   // >= kp, = 4 (mod 64): conflict-free MFMA B reads
     // waves per slab workgroup.  Many slabs (more workgroups than CUs): the count in {4, 6, 8} that wastes the least SIMD
@@ -2445,7 +2512,7 @@ struct Ctx : CtxBase {
             return RN_OK;
         }
         std::vector<double> blk((size_t)ny * LD);
-        if (int rc = download(blk.data(), d_A + (size_t)node * strideA, (size_t)ny * LD)) return rc;
+        if (int rc = download_block(node, blk.data())) return rc;
         for (int c = 0; c < cols; c++) for (int r = 0; r < nv; r++) host[r + (size_t)c * nv] = blk[(size_t)(c0 + c) * LD + r0 + r];
         return RN_OK;
     }
@@ -2634,6 +2701,18 @@ struct Ctx : CtxBase {
         if (active) *active = structured ? RN_OPS_STRUCTURED : RN_OPS_DENSE;
         return RN_OK;
     }
+    int set_operator_storage(int storage) override {
+        RN_CHECK(storage == RN_STORE_NATIVE || storage == RN_STORE_F32, RN_E_ARG, "rn_set_operator_storage: RN_STORE_NATIVE or RN_STORE_F32");
+        RN_CHECK(!factored, RN_E_STATE, "rn_set_operator_storage must precede rn_factor_step");
+        storeReq = storage;
+        block_layout();
+        return RN_OK;
+    }
+    int get_operator_storage(int *requested, int *active) override {
+        if (requested) *requested = storeReq;
+        if (active) *active = (!structured && (d_A32 != nullptr || (sizeof(T) == 4 && d_A != nullptr))) ? RN_STORE_F32 : RN_STORE_NATIVE;
+        return RN_OK;
+    }
     // RN_OPS_AUTO, a caller hands in a block of its own: from here on the context runs on dense per-node blocks -- the factor step once
     // more on the saved inputs, this time expanding every block (Engine.cu:721-745) into d_A
     int materialise_dense() {
@@ -2663,9 +2742,9 @@ struct Ctx : CtxBase {
         RN_HIP(hipSetDevice(device));
         if (structured) { if (int rc = materialise_dense()) return rc; }
         std::vector<double> blk((size_t)ny * LD);
-        if (int rc = download(blk.data(), d_A + (size_t)node * strideA, (size_t)ny * LD)) return rc;
+        if (int rc = download_block(node, blk.data())) return rc;
         for (int c = 0; c < cols; c++) for (int r = 0; r < nv; r++) blk[(size_t)(c0 + c) * LD + r0 + r] = host[r + (size_t)c * nv];
-        return upload(d_A + (size_t)node * strideA, blk.data(), (size_t)ny * LD);
+        return upload_block(node, blk.data());      // (fp32 storage: the caller's values rounded to nearest)
     }
     int set_cut_moments(const double *E, const double *P, size_t nParents) override {
         RN_CHECK(cutStage > 0, RN_E_STATE, "rn_set_cut_children_moments: set the cut stage first");
@@ -2762,6 +2841,8 @@ int rn_get_counters(rn_ctx *ctx, long out[4]) { RN_GUARD(ctx); return ctx->impl-
 int rn_set_cut_children_moments(rn_ctx *ctx, const double *E, const double *P, size_t n) { RN_GUARD(ctx); return ctx->impl->set_cut_moments(E, P, n); }
 int rn_set_operator_mode(rn_ctx *ctx, int mode) { RN_GUARD(ctx); return ctx->impl->set_operator_mode(mode); }
 int rn_get_operator_mode(rn_ctx *ctx, int *requested, int *active) { RN_GUARD(ctx); return ctx->impl->get_operator_mode(requested, active); }
+int rn_set_operator_storage(rn_ctx *ctx, int storage) { RN_GUARD(ctx); return ctx->impl->set_operator_storage(storage); }
+int rn_get_operator_storage(rn_ctx *ctx, int *requested, int *active) { RN_GUARD(ctx); return ctx->impl->get_operator_storage(requested, active); }
 int rn_set_operator(rn_ctx *ctx, int op, int node, const double *h, size_t n) { RN_GUARD(ctx); return ctx->impl->set_operator(op, node, h, n); }
 int rn_set_warm_start(rn_ctx *ctx, int on) { RN_GUARD(ctx); return ctx->impl->set_warm_start(on); }
 int rn_set_exchange_mode(rn_ctx *ctx, int mode) { RN_GUARD(ctx); return ctx->impl->set_exchange_mode(mode); }
