@@ -136,13 +136,29 @@ int rn_get_operator_mode(rn_ctx *ctx, int *requested, int *active);
  *     solution of the problem WITH THE ROUNDED BLOCKS (to 1e-9 against an fp64 oracle given the same blocks), and the problem itself is
  *     perturbed by at most 2^-24 relative (6e-8) per block entry.  rn_get_operator returns the stored values (fp32-representable doubles);
  *     rn_set_operator rounds the caller's block to nearest fp32 on upload.  On an RN_F32 context the value is accepted and changes nothing.
- *     The quasi-Newton loops run their two Hessian sweeps one after the other in this mode (no shared pass over the blocks).
+ *     The quasi-Newton loops run their two Hessian sweeps one after the other in this mode unless rn_set_sweep_pairing(RN_PAIR_ON) asks for
+ *     the shared pass over the blocks (below).
  * The setting concerns the dense blocks only: under RN_OPS_STRUCTURED it is remembered and has no effect, under RN_OPS_AUTO it takes effect
  * when the first rn_set_operator materialises the blocks.
  * rn_get_operator_storage: *requested = what was asked for, *active = RN_STORE_F32 only while dense blocks exist in fp32. */
 enum { RN_STORE_NATIVE = 0, RN_STORE_F32 = 1 };
 int rn_set_operator_storage(rn_ctx *ctx, int storage);
 int rn_get_operator_storage(rn_ctx *ctx, int *requested, int *active);
+/* NAMA's two Hessian oracles of a line search (SmpcController.cu:1331 on the residual, :1341-1345 on the corrected direction) do not feed each
+ * other, so one pass over the DENSE per-node blocks can serve both (two right-hand sides in the streaming kernel): a NAMA iteration then
+ * streams the blocks twice instead of three times.  Bitwise the results of the two sweeps run one after the other.
+ *   RN_PAIR_AUTO (the default of a new context): blocks in the context's own type pair whenever the streaming launch has no split last round
+ *     and both right-hand sides' LDS sets fit 64 KB; RN_STORE_F32 blocks under fp64 iterates do not pair.
+ *   RN_PAIR_ON: AUTO plus RN_STORE_F32 blocks, a context whose streaming launch has a split last round included (the pair sweep alone runs
+ *     unsplit; every other sweep keeps its split); their two LDS sets (doubles) may take the CU's 160 KB.  Opt-in because its gain has not been measured on an MI355X yet.
+ *   RN_PAIR_OFF: the two sweeps always run one after the other.
+ * Valid at any time (an unknown value: RN_E_ARG).  The pair needs buffers of its own: allocated by this call when RN_ALG_NAMA is already
+ * selected, by the next rn_set_algorithm(RN_ALG_NAMA) otherwise.  Sharded contexts (rn_set_cut_stage, a communicator) never pair.
+ * rn_get_sweep_pairing: *requested = what was asked for; *active = 1 when the context as it stands would pair its next NAMA line search
+ * (RN_ALG_NAMA selected, dense blocks, the pair buffers present, both LDS sets fit, not sharded), else 0.  rn_fbe_counters out[3] counts the pairs. */
+enum { RN_PAIR_OFF = 0, RN_PAIR_ON = 1, RN_PAIR_AUTO = 2 };
+int rn_set_sweep_pairing(rn_ctx *ctx, int mode);
+int rn_get_sweep_pairing(rn_ctx *ctx, int *requested, int *active);
 
 /* ---- Engine -------------------------------------------------------------------------------------- */
 /* Engine::factorStep (Engine.cu:671-774) incl. initialiseSystemDevice / preconditioning kernels. */

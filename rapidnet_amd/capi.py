@@ -23,6 +23,8 @@ OPS_DENSE, OPS_STRUCTURED, OPS_AUTO = 0, 1, 2
 OPS_MODES = {"dense": OPS_DENSE, "structured": OPS_STRUCTURED, "auto": OPS_AUTO}
 STORE_NATIVE, STORE_F32 = 0, 1
 STORAGES = {"native": STORE_NATIVE, "f32": STORE_F32}
+PAIR_OFF, PAIR_ON, PAIR_AUTO = 0, 1, 2
+PAIRINGS = {"off": PAIR_OFF, "on": PAIR_ON, "auto": PAIR_AUTO}
 # include/rapidnet_debug.h, RN_KNOB_*
 KNOBS = {k: i for i, k in enumerate(("dual_trips", "dual_pipe", "vlv_wide", "slab_pipe", "slab_frag", "unscaled_walk", "stream_two_per_cu",
                                      "stream_split", "nama_pair", "ls_sequential", "value_mfma", "tune_bias_us", "struct_linear", "fuse_split"))}
@@ -37,7 +39,7 @@ SYMBOLS = [
     "rn_update_primal_infeasibility", "rn_get_prox_distances", "rn_buffer_size", "rn_get", "rn_set", "rn_get_operator",
     "rn_device_pointer", "rn_profile_enable", "rn_profile_reset", "rn_profile_read", "rn_algorithmic_bytes", "rn_stream",
     "rn_comm_unique_id", "rn_comm_init", "rn_comm_init_timeout", "rn_comm_check", "rn_comm_library", "rn_set_cut_stage", "rn_get_history_parts", "rn_get_counters", "rn_debug_sweep_phase",
-    "rn_debug_cut_buffer", "rn_set_cut_children_moments", "rn_set_operator_mode", "rn_get_operator_mode", "rn_set_operator_storage", "rn_get_operator_storage", "rn_set_operator", "rn_set_warm_start", "rn_set_exchange_mode",
+    "rn_debug_cut_buffer", "rn_set_cut_children_moments", "rn_set_operator_mode", "rn_get_operator_mode", "rn_set_operator_storage", "rn_get_operator_storage", "rn_set_sweep_pairing", "rn_get_sweep_pairing", "rn_set_operator", "rn_set_warm_start", "rn_set_exchange_mode",
     "rn_measure_hbm", "rn_set_algorithm", "rn_fbe_reset", "rn_algorithm_fbe_nama", "rn_compute_hessian_oracle", "rn_compute_gradient_fbe",
     "rn_update_fixed_point_residual_nama", "rn_compute_lbfgs_direction", "rn_update_lbfgs_buffer", "rn_two_loop_recursion_lbfgs", "rn_compute_value_fbe",
     "rn_line_search_lbfgs_update", "rn_line_search_ame_lbfgs_update", "rn_lbfgs_state", "rn_lbfgs_column",
@@ -178,6 +180,8 @@ def load():
     lib.rn_get_operator_mode.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.rn_set_operator_storage.argtypes = [vp, ip]
     lib.rn_get_operator_storage.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    lib.rn_set_sweep_pairing.argtypes = [vp, ip]
+    lib.rn_get_sweep_pairing.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.rn_set_operator.argtypes = [vp, ip, ip, dp, C.c_size_t]
     lib.rn_set_warm_start.argtypes = [vp, ip]
     lib.rn_set_exchange_mode.argtypes = [vp, ip]
@@ -251,14 +255,16 @@ class Solver:
     """
 
     def __init__(self, network, tree, config, precision="f64", device=0, structured=False, rank=0, nranks=1, cut_stage=0,
-                 unique_id=None, knobs=None, operator_mode=None, operator_storage="native"):
+                 unique_id=None, knobs=None, operator_mode=None, operator_storage="native", sweep_pairing="auto"):
         """nranks > 1: `tree` is the FULL scenario tree and the context is rank `rank`'s shard of it (rn_create_sharded:
         partition, communicator from `unique_id` -- None = none, the exchange is a test's job --, cut stage, children
         moments); self.nodes is then the LOCAL node count and self.global_nodes maps local -> full-tree node ids.
         operator_mode: "dense" | "structured" | "auto" (rn_set_operator_mode); None: `structured` decides between the first two --
         the tests and bench.py always say which storage they measure; the C-ABI's own default is auto.
         operator_storage: "native" | "f32" (rn_set_operator_storage): the element type of the dense blocks; "f32" on an f64 context
-        streams half the bytes and accumulates in fp64."""
+        streams half the bytes and accumulates in fp64.
+        sweep_pairing: "auto" | "on" | "off" (rn_set_sweep_pairing): NAMA's two Hessian sweeps in one pass over the dense blocks; "on" adds
+        fp32-stored blocks to what "auto" pairs."""
         self.lib = load()
         self.structured = bool(structured)
         self.network, self.tree, self.config = network, tree, config
@@ -295,6 +301,8 @@ class Solver:
         self.structured = mode != OPS_DENSE
         if operator_storage != "native":      # (a context that never asks for it makes exactly the calls it always made)
             self._check(self.lib.rn_set_operator_storage(self.h, STORAGES[operator_storage]))
+        if sweep_pairing != "auto":
+            self._check(self.lib.rn_set_sweep_pairing(self.h, PAIRINGS[sweep_pairing]))
         for k, v in (knobs or {}).items():
             self.debugSetKnob(k, v)
 
@@ -526,6 +534,12 @@ class Solver:
         self._check(self.lib.rn_get_operator_storage(self.h, C.byref(r), C.byref(a)))
         names = {v: k for k, v in STORAGES.items()}
         return names[r.value], names[a.value]
+
+    def sweepPairing(self):
+        """(requested as "auto" | "on" | "off", active): active is 1 when the context as it stands would pair its next NAMA line search"""
+        r, a = C.c_int(0), C.c_int(0)
+        self._check(self.lib.rn_get_sweep_pairing(self.h, C.byref(r), C.byref(a)))
+        return {v: k for k, v in PAIRINGS.items()}[r.value], a.value
 
     def synchronize(self):
         self._check(self.lib.rn_synchronize(self.h))

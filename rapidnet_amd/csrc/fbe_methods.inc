@@ -89,31 +89,33 @@
             d_S0 = d_S; d_Yv0 = d_Yv;
             h_rho.assign((size_t)bufferSize + 1, 0.0);
         }
-        if (alg == RN_ALG_NAMA && !d_myB && !structured && !store32()) {      // (fp32 block storage has no paired pass: stream_pair_ok)
-            const size_t n = (size_t)ntot(), N_ = d.nodes;
-            bool want = true;
-            if (knob[RN_KNOB_NAMA_PAIR] == 0) want = false;      // A/B runs, tests: the two sweeps one after the other
-            if (want) {
-                if (int rc = dalloc(&d_myB, N_ * 2 * d.nv)) return rc;
-                if (int rc = dalloc(&d_qaB, N_ * d.nx)) return rc;
-                if (int rc = dalloc(&d_xdirB, N_ * d.nx)) return rc;
-                if (int rc = dalloc(&d_udirB, N_ * d.nu)) return rc;
-                if (int rc = dalloc(&d_hxDirB, n)) return rc;
-                {
-                    if (int rc = dalloc(&d_skB, N_ * (d.nv + d.nx))) return rc;
-                    if (int rc = dalloc(&d_rkqB, N_ * (d.nv + 2 * d.nx))) return rc;
-                    if (int rc = dalloc(&d_vB, N_ * d.nv)) return rc;
-                    if (int rc = dalloc(&d_lvbB, N_ * (d.nu + d.nx))) return rc;
-                    if (int rc = dalloc(&d_bwB, N_ * d.nx)) return rc;
-                    RN_HIP(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
-                    RN_HIP(hipEventCreateWithFlags(&evFork, hipEventDisableTiming));
-                    RN_HIP(hipEventCreateWithFlags(&evJoin, hipEventDisableTiming));
-                }
-            }
-        }
+        if (alg == RN_ALG_NAMA) { if (int rc = ensure_pair_buffers()) return rc; }
         algorithm = alg;
         return fbe_reset();
     }
+    // NAMA's pair buffers, the second helper chain's scratch set, its stream and the events: allocated once, when the context could pair (dense
+    // blocks; fp32-stored ones behind RN_PAIR_ON only -- rn_set_sweep_pairing) and RN_KNOB_NAMA_PAIR does not force the sequential path
+    int ensure_pair_buffers() {
+        if (d_myB || structured || pairReq == RN_PAIR_OFF || (store32() && pairReq != RN_PAIR_ON) || knob[RN_KNOB_NAMA_PAIR] == 0) return RN_OK;
+        const size_t n = (size_t)ntot(), N_ = d.nodes;
+        if (int rc = dalloc(&d_qaB, N_ * d.nx)) return rc;
+        if (int rc = dalloc(&d_xdirB, N_ * d.nx)) return rc;
+        if (int rc = dalloc(&d_udirB, N_ * d.nu)) return rc;
+        if (int rc = dalloc(&d_hxDirB, n)) return rc;
+        if (int rc = dalloc(&d_skB, N_ * (d.nv + d.nx))) return rc;
+        if (int rc = dalloc(&d_rkqB, N_ * (d.nv + 2 * d.nx))) return rc;
+        if (int rc = dalloc(&d_vB, N_ * d.nv)) return rc;
+        if (int rc = dalloc(&d_lvbB, N_ * (d.nu + d.nx))) return rc;
+        if (int rc = dalloc(&d_bwB, N_ * d.nx)) return rc;
+        if (!stream2) RN_HIP(hipStreamCreateWithFlags(&stream2, hipStreamNonBlocking));
+        if (!evFork) RN_HIP(hipEventCreateWithFlags(&evFork, hipEventDisableTiming));
+        if (!evJoin) RN_HIP(hipEventCreateWithFlags(&evJoin, hipEventDisableTiming));
+        return dalloc(&d_myB, N_ * 2 * d.nv);      // (last: d_myB != nullptr says the whole set is there)
+    }
+    // the context as it stands pairs the two Hessian sweeps of its next NAMA line search
+    // (cutStage <= 0: a cut context -- even one without a communicator, which RN_FBE_READY allows -- keeps ONE cut buffer d_cut, and the two
+    //  helper chains of the pair would both write and read it)
+    bool pair_active() const { return d_myB && stream_pair_ok() && !fbe_sharded() && cutStage <= 0; }
     // SmpcController::initialiseAlgorithm (FBE / NAMA part, :436-449) + initaliseLbfgBuffer (:453-468)
     int fbe_reset() override {
         RN_CHECK(algorithm != RN_ALG_APG && d_matS, RN_E_STATE, "rn_fbe_reset: select RN_ALG_GLOBAL_FBE or RN_ALG_NAMA first");
@@ -536,9 +538,7 @@
         T tau = 1;
         const long long n = ntot();
         if (int rc = launch_dots({{d_res, d_dir}})) return rc;                                 // valueDirection = -<res, dir>, read with the search's first batch
-        // (cutStage <= 0: a cut context -- even one without a communicator, which RN_FBE_READY allows -- keeps ONE cut buffer d_cut, and the two
-        //  helper chains of the pair would both write and read it)
-        if (d_myB && stream_pair_ok() && !fbe_sharded() && cutStage <= 0) {
+        if (pair_active()) {
             // the reference's two Hessian oracles (:1331 on the residual, :1341-1345 on the corrected direction) do not feed each other:
             // the direction's correction (:1338-1340) only needs the residual.  So the correction comes first and both sweeps share one
             // pass over the operator blocks -- a third of the iteration's HBM traffic; same values as the sequence below.

@@ -156,6 +156,14 @@ SmpcConfiguration::SmpcConfiguration(string pathToFile) {
         if (operatorStorage != "native" && operatorStorage != "f32")
             throw std::logic_error("controller configuration: operatorStorage must be \"native\" or \"f32\" (got \"" + operatorStorage + "\")");
     }
+    // ... and whether NAMA's two Hessian sweeps share one pass over the dense blocks (absent = "auto": rapidnet.h, rn_set_sweep_pairing)
+    sweepPairing = "auto";
+    if (doc.HasMember("sweepPairing")) {
+        _ASSERT(doc["sweepPairing"].IsString());
+        sweepPairing = doc["sweepPairing"].str;
+        if (sweepPairing != "auto" && sweepPairing != "on" && sweepPairing != "off")
+            throw std::logic_error("controller configuration: sweepPairing must be \"auto\", \"on\" or \"off\" (got \"" + sweepPairing + "\")");
+    }
     lbfgsBufferSize = scalarInt(doc, "lbfgsBufferSize");
     pathToConfiguration = pathToFile;
     // relative paths in the configuration are relative to the configuration file's directory when they do not

@@ -122,6 +122,8 @@ public:
     string getOperatorMode() { return operatorMode; }
     // "operatorStorage" (optional key, not in the reference's files): "native" (default) or "f32" -- Engine.hpp, setOperatorStorage
     string getOperatorStorage() { return operatorStorage; }
+    // "sweepPairing" (optional key, not in the reference's files): "auto" (default), "on" or "off" -- Engine.hpp, setSweepPairing
+    string getSweepPairing() { return sweepPairing; }
     void setCurrentState();     // re-read from the configuration file (SmpcConfiguration.cu:240-256)
     void setPreviousControl();  // :261-277
     void setPreviousDemand();   // :283-299
@@ -134,7 +136,7 @@ private:
     uint_t NX, NU, ND, NV, lbfgsBufferSize, maxIteration;
     std::vector<real_t> matL, matLhat, matCostW, matDiagPrecnd, currentX, prevU, prevDemand;
     real_t penaltyStateX, penaltySafetyX, stepSize, weightPrice, weightSmooth, weightSafety;
-    string pathToConfiguration, pathToNetwork, pathToScenarioTree, pathToForecaster, algorithmName, operatorMode, operatorStorage;
+    string pathToConfiguration, pathToNetwork, pathToScenarioTree, pathToForecaster, algorithmName, operatorMode, operatorStorage, sweepPairing;
 };
 
 #endif

@@ -55,6 +55,12 @@ int Engine::getOperatorStorage() {
     check(rn_get_operator_storage(ctx, nullptr, &active), "rn_get_operator_storage");
     return active;
 }
+void Engine::setSweepPairing(int mode) { check(rn_set_sweep_pairing(ctx, mode), "rn_set_sweep_pairing"); }
+int Engine::getSweepPairing(int *active) {
+    int requested = RN_PAIR_AUTO;
+    check(rn_get_sweep_pairing(ctx, &requested, active), "rn_get_sweep_pairing");
+    return requested;
+}
 void Engine::setOperator(int op, uint_t node, const real_t *host, size_t n) { check(rn_set_operator(ctx, op, node, host, n), "rn_set_operator"); }
 
 void Engine::create(int precision, int device, int operatorMode, int rank, int nranks, const void *id128, int cutStage) {
@@ -87,6 +93,10 @@ void Engine::create(int precision, int device, int operatorMode, int rank, int n
     }
     check(rn_set_operator_mode(ctx, operatorMode), "rn_set_operator_mode");
     if (ptrMySmpcConfig->getOperatorStorage() == "f32") check(rn_set_operator_storage(ctx, RN_STORE_F32), "rn_set_operator_storage");
+    {
+        const string m = ptrMySmpcConfig->getSweepPairing();
+        if (m != "auto") check(rn_set_sweep_pairing(ctx, m == "on" ? RN_PAIR_ON : RN_PAIR_OFF), "rn_set_sweep_pairing");
+    }
     // SmpcController::allocateApgAlgorithm (SmpcController.cu:124-151): per-iteration storage for maxIterations, allocated once
     check(rn_reserve_iterations(ctx, (int)ptrMySmpcConfig->getMaxIterations()), "rn_reserve_iterations");
     if (!apgFlag)   // SmpcController::allocateGlobalFbeAlgorithm / allocateNamaAlgorithm / allocateLbfgsBuffer (SmpcController.cu:234-330)

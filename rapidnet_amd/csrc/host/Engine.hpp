@@ -41,6 +41,11 @@ public:
     // ("native" | "f32"; absent: native).  Before factorStep().
     void setOperatorStorage(int storage);
     int getOperatorStorage();                        // RN_STORE_F32 while the engine holds dense blocks in fp32, else RN_STORE_NATIVE
+    // NAMA's two Hessian sweeps in one pass over the dense blocks (rapidnet.h, rn_set_sweep_pairing): RN_PAIR_AUTO / _ON / _OFF; _ON adds fp32-stored
+    // blocks to what _AUTO pairs.  The constructors take it from the configuration file's optional "sweepPairing" key ("auto" | "on" | "off";
+    // absent: auto).  At any time.
+    void setSweepPairing(int mode);
+    int getSweepPairing(int *active = nullptr);      // what was asked for; *active: 1 when the next NAMA line search would run the pair
     // a per-node block handed in by the caller (the reference: write through getMatPhi() / getPtrMatPhi()[node] ..., Engine.cuh:170-230);
     // RN_OP_PHI, _PSI, _D, _F, col-major nv x (2nx | nu); after factorStep()
     void setOperator(int opId, uint_t node, const real_t *host, size_t n);

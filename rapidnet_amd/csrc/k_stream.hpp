@@ -214,18 +214,28 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
 // sh_y; the fold over the span's columns and the outputs my / my2 / qa are double and go where k_stream_gemv<double> puts them, so no
 // consumer knows about the storage.  The order in which a row meets its columns is that of the fp32 context's kernel (same G).
 // Prologue order, the clamp of the first group and the branch-free steady state: as above, for the reasons given there.
-// One right-hand side only: with fp32 storage the quasi-Newton loops' two Hessian sweeps run one after the other (Ctx::stream_pair_ok).
-// LDS: (ny + G * LD) doubles.  HBM bytes per node: LD*ny*4 + (ny + 2nv + nx)*8.
+// NR = 2 (unsplit only): the quasi-Newton loops' two Hessian sweeps in one pass over the fp32 blocks, as k_stream_gemv NR = 2 does for native
+// blocks -- behind rn_set_sweep_pairing(RN_PAIR_ON) (Ctx::stream_pair_ok); not measured on an MI355X yet.  The second accelerated dual r2.w is
+// requested with the small loads in front of the first group and kept in a second LDS set (sh_y2 / sh_red2, doubles); the lane converts its
+// four floats once and accumulates part and part2 in double; r2.qa is stored at the end like a.qa; the epilogue folds both partial sets in one
+// walk into a.my and r2.my.  Each right-hand side's sums are formed exactly as the NR = 1, SPLIT = false kernel forms them (same column order,
+// same fold over k): bitwise the results of two unsplit launches.  NL >= 3 runs groups one span shorter (D = 2) to stay inside the registers;
+// the depth does not change the order in which a thread meets its columns.
+// LDS: NR * (ny + G * LD) doubles (NR = 2: up to the CU's 160 KB, Ctx::launch_stream).  HBM bytes per node: LD*ny*4 + NR*(ny + 2nv + nx)*8.
 // Registers (hipcc's resource report, SPLIT = false | true): NL = 1: 72 | 70 VGPRs, NL = 2: 154 | 146, NL = 3: 156 | 156, NL = 4: 208 | 210; no scratch --
-// three waves per SIMD at NL = 2, like k_stream_gemv<float, 2, *> (146 | 130).
-template <int NL, bool SPLIT>
-__global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_mixed(SweepArgs<double> a, int G, int node0, StreamSplit<double> sp) {
+// three waves per SIMD at NL = 2, like k_stream_gemv<float, 2, *> (146 | 130).  NR = 2 (SPLIT = false): NL = 1: 108, NL = 2: 198, NL = 3: 208,
+// NL = 4: 232; no scratch, two waves per SIMD from NL = 2 on (one workgroup per CU).
+template <int NL, bool SPLIT, int NR = 1>
+__global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_mixed(SweepArgs<double> a, int G, int node0, StreamSplit<double> sp, StreamRhs2<double> r2) {
+    static_assert(NR == 1 || !SPLIT, "two right-hand sides: unsplit launches only");
     typedef double T;
     typedef nat_f4 VT;
-    constexpr int VPL = 4, D = NL <= 2 ? RN_STREAM_D : RN_STREAM_D_WIDE;
+    constexpr int VPL = 4, D0 = NL <= 2 ? RN_STREAM_D : RN_STREAM_D_WIDE, D = (NR == 2 && NL >= 3) ? D0 - 1 : D0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *sh_y = reinterpret_cast<T *>(smem_raw);          // ny
     T *sh_red = sh_y + ((a.ny + 3) & ~3);               // G * LD
+    T *sh_y2 = sh_red + (size_t)G * a.LD;               // NR = 2: the same pair again for the second right-hand side
+    T *sh_red2 = sh_y2 + ((a.ny + 3) & ~3);
     const int tid = threadIdx.x;
     const bool split = SPLIT && (int)blockIdx.x >= sp.first;
     const int node = split ? sp.first + (((int)blockIdx.x - sp.first) >> 1) : (int)blockIdx.x;
@@ -246,11 +256,11 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
         cj[j] = off[j] / SPC;
         msk[j] = ok ? (T)1 : (T)0;
     }
-    T part[NL][VPL];
+    T part[NL][VPL], part2[NR == 2 ? NL : 1][VPL];
 #pragma unroll
     for (int j = 0; j < NL; j++)
 #pragma unroll
-        for (int e = 0; e < VPL; e++) part[j][e] = 0;
+        for (int e = 0; e < VPL; e++) { part[j][e] = 0; if (NR == 2) part2[j][e] = 0; }
     const int nFull = (ny / G < span1 ? ny / G : span1) - span0;   // spans of this workgroup made of G whole columns
     const int nGroups = nFull / D;
     VT bufA[D][NL], bufB[D][NL];
@@ -263,6 +273,10 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
         _Pragma("unroll") for (int j = 0; j < NL; j++) {                                                               \
             const T yc = sh_y[(span0 + (g_) * D + d) * G + cj[j]] * msk[j];                                            \
             _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] += (T)buf[d][j][e] * yc;                        \
+            if (NR == 2) {      /* the lane's four floats are converted once and meet both columns */                  \
+                const T yc2 = sh_y2[(span0 + (g_) * D + d) * G + cj[j]] * msk[j];                                      \
+                _Pragma("unroll") for (int e = 0; e < VPL; e++) part2[j][e] += (T)buf[d][j][e] * yc2;                  \
+            }                                                                                                          \
         }
     const bool has0 = tid < ny;
     const size_t i0 = (size_t)node * ny + (has0 ? tid : 0);
@@ -272,6 +286,8 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
     const int tq = tid < nx ? tid : 0;
     const T dq0 = dyRow[tq], dq1 = dyRow[nx + tq];    // for a_i below
     const T w0a = a.w[i0];      // the y column: the accelerated dual the sweep is evaluated at
+    T w20 = 0;
+    if (NR == 2) w20 = r2.w[i0];      // the second right-hand side: with the small loads, in front of the first group
     asm volatile("" ::: "memory");   // keep the request order: the small loads first, the group right behind them
     {
         const int lastSlot = (int)blockSlots - 1;
@@ -284,14 +300,23 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
             }
     }
     asm volatile("" ::: "memory");
-    T qa0 = 0;      // a_i is stored at the end of the kernel (stores count in the loads' in-order counter)
+    T qa0 = 0, qa02 = 0;      // a_i is stored at the end of the kernel (stores count in the loads' in-order counter)
     if (has0) sh_y[tid] = w0a;
     for (int c = tid + STREAM_THREADS; c < ny; c += STREAM_THREADS) sh_y[c] = a.w[(size_t)node * ny + c];
+    if (NR == 2) {
+        if (has0) sh_y2[tid] = w20;
+        for (int c = tid + STREAM_THREADS; c < ny; c += STREAM_THREADS) sh_y2[c] = r2.w[(size_t)node * ny + c];
+    }
     __syncthreads();
     // a_i = F_i' xi_i = sqrt(p_i) (d_x o xi_box + d_xs o xi_safe)      (a split block: written by its first half)
     if (tid < nx) qa0 = stream_qa_elem(spn, dq0, sh_y[tid], dq1, sh_y[nx + tid]);
     if (!second) for (int t = tid + STREAM_THREADS; t < nx; t += STREAM_THREADS)
         a.qa[(size_t)node * nx + t] = stream_qa_elem(spn, dyRow[t], sh_y[t], dyRow[nx + t], sh_y[nx + t]);
+    if (NR == 2) {
+        if (tid < nx) qa02 = stream_qa_elem(spn, dq0, sh_y2[tid], dq1, sh_y2[nx + tid]);
+        for (int t = tid + STREAM_THREADS; t < nx; t += STREAM_THREADS)
+            r2.qa[(size_t)node * nx + t] = stream_qa_elem(spn, dyRow[t], sh_y2[t], dyRow[nx + t], sh_y2[nx + t]);
+    }
     if (nGroups > 0) {
         int g = 0;
         for (; g + 2 < nGroups; g += 2) {      // no branch inside: exact vmcnt waits, group g+1 (then g+2) in flight while g is consumed
@@ -321,17 +346,33 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
             const T yc = live ? sh_y[c] : (T)0;
 #pragma unroll
             for (int e = 0; e < VPL; e++) part[j][e] += (T)v[e] * yc;
+            if (NR == 2) {
+                const T yc2 = live ? sh_y2[c] : (T)0;
+#pragma unroll
+                for (int e = 0; e < VPL; e++) part2[j][e] += (T)v[e] * yc2;
+            }
         }
     }
 #pragma unroll
     for (int j = 0; j < NL; j++)
         if (msk[j] != (T)0) {
 #pragma unroll
-            for (int e = 0; e < VPL; e++) sh_red[(size_t)off[j] * VPL + e] = part[j][e];
+            for (int e = 0; e < VPL; e++) { sh_red[(size_t)off[j] * VPL + e] = part[j][e]; if (NR == 2) sh_red2[(size_t)off[j] * VPL + e] = part2[j][e]; }
         }
     if (tid < nx && !second) stream_out(qa0, a.qa + (size_t)node * nx + tid);
+    if (NR == 2 && tid < nx) stream_out(qa02, r2.qa + (size_t)node * nx + tid);
     __syncthreads();
     T *const myOut = second ? sp.my2 + (size_t)(node - sp.first) * 2 * nv : a.my + (size_t)node * 2 * nv;
+    if (NR == 2) {      // both right-hand sides' partials folded in one walk, each in the order of the one-vector kernel
+        T *const myOut2 = r2.my + (size_t)node * 2 * nv;
+        for (int r = tid; r < 2 * nv; r += STREAM_THREADS) {
+            T s = sh_red[r], s2 = sh_red2[r];
+            for (int k = 1; k < G; k++) { s += sh_red[(size_t)k * LD + r]; s2 += sh_red2[(size_t)k * LD + r]; }
+            stream_out(s, myOut + r);
+            stream_out(s2, myOut2 + r);
+        }
+        return;
+    }
     for (int r = tid; r < 2 * nv; r += STREAM_THREADS) {    // slot q of a span = column q / SPC, rows (q % SPC) * VPL ...
         T s = sh_red[r];
         for (int k = 1; k < G; k++) s += sh_red[(size_t)k * LD + r];

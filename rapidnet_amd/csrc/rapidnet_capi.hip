@@ -225,6 +225,8 @@ struct CtxBase {
     virtual int fbe_counters(long *) = 0;
     virtual int set_operator_storage(int) = 0;
     virtual int get_operator_storage(int *, int *) = 0;
+    virtual int set_sweep_pairing(int) = 0;
+    virtual int get_sweep_pairing(int *, int *) = 0;
 };
 
 // ---- in-process stand-in for the communicator (rn_debug_local_group_*): `n` contexts of one process, one host thread each ----
@@ -1130,13 +1132,14 @@ struct Ctx : CtxBase {
                 all = all && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
             if constexpr (sizeof(T) == 8)
                 for (const void *fn : {(const void *)k_stream_gemv_mixed<1, false>, (const void *)k_stream_gemv_mixed<2, false>, (const void *)k_stream_gemv_mixed<3, false>, (const void *)k_stream_gemv_mixed<4, false>,
-                                       (const void *)k_stream_gemv_mixed<1, true>, (const void *)k_stream_gemv_mixed<2, true>, (const void *)k_stream_gemv_mixed<3, true>, (const void *)k_stream_gemv_mixed<4, true>})
+                                       (const void *)k_stream_gemv_mixed<1, true>, (const void *)k_stream_gemv_mixed<2, true>, (const void *)k_stream_gemv_mixed<3, true>, (const void *)k_stream_gemv_mixed<4, true>,
+                                       (const void *)k_stream_gemv_mixed<1, false, 2>, (const void *)k_stream_gemv_mixed<2, false, 2>, (const void *)k_stream_gemv_mixed<3, false, 2>, (const void *)k_stream_gemv_mixed<4, false, 2>})
                     all = all && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
             return all;
         }();
         return ok;
     }
-    // second != nullptr: two right-hand sides in one pass (k_stream_gemv NR = 2; see stream_pair_ok)
+    // second != nullptr: two right-hand sides in one pass (k_stream_gemv / k_stream_gemv_mixed NR = 2; see stream_pair_ok)
     int launch_stream(const SweepArgs<T> &a, const StreamRhs2<T> *second = nullptr) {
         int G, NL;
         stream_shape(&G, &NL);
@@ -1148,21 +1151,31 @@ struct Ctx : CtxBase {
         const int grid = d.nodes + (d.nodes - a.splitFirst);      // two workgroups for every block of the split round
         const StreamRhs2<T> none{nullptr, nullptr, nullptr};
         if constexpr (sizeof(T) == 8) {
-            if (store32()) {   // fp32 blocks under fp64 iterates (k_stream_gemv_mixed): one right-hand side, split or not
-                RN_CHECK(!second, RN_E_STATE, "k_stream_gemv_mixed: one right-hand side only");
-                if (streamTwoPerCU) {
+            if (store32()) {   // fp32 blocks under fp64 iterates (k_stream_gemv_mixed): one right-hand side, split or not, or two, unsplit
+                if (second) {
+                    // (both sets are doubles over a span chosen for 4-byte entries: twice the native pair's LDS for the same operator width, so
+                    //  past 64 KB the launch takes the function attribute like the one-vector launch does)
+                    RN_CHECK(a.splitFirst >= d.nodes, RN_E_STATE, "k_stream_gemv_mixed with two right-hand sides: unsplit launches only");
+                    RN_CHECK(2 * lds <= 64 * 1024 || (2 * lds <= 160 * 1024 && ensure_stream_lds()), RN_E_ARG, "k_stream_gemv_mixed with two right-hand sides: the two LDS sets do not fit the CU's LDS");
                     switch (NL) {
-                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
-                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
-                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
-                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
+                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
+                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
+                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
+                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
+                    }
+                } else if (streamTwoPerCU) {
+                    switch (NL) {
+                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
+                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
+                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
+                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
                     }
                 } else {
                     switch (NL) {
-                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
-                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
-                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
-                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp); break;
+                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
+                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
+                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
+                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
                     }
                 }
                 return RN_OK;
@@ -1193,12 +1206,20 @@ struct Ctx : CtxBase {
         }
         return RN_OK;
     }
-    // two right-hand sides in one streaming pass are possible for: dense per-node blocks in the context's own type (k_stream_gemv_mixed has no
-    // NR = 2 form: with fp32 storage the pair runs as two sweeps), no split last round, both LDS sets in 64 KB
+    // rn_set_sweep_pairing: RN_PAIR_AUTO (default), RN_PAIR_ON (AUTO plus fp32-stored blocks), RN_PAIR_OFF (never)
+    int pairReq = RN_PAIR_AUTO;
+    // two right-hand sides in one streaming pass are possible for dense per-node blocks, and
+    //   blocks in the context's own type (k_stream_gemv NR = 2): both LDS sets in 64 KB, no split last round;
+    //   fp32-stored blocks (k_stream_gemv_mixed NR = 2; bitwise the two sweeps, its gain not measured yet): behind RN_PAIR_ON only, a split
+    //   last round included -- the pair sweep then runs unsplit (launch_sweep), the context's other sweeps keep their split.  Its LDS sets
+    //   are doubles over a span chosen for 4-byte entries (twice the columns): twice the native pair's bytes at the same operator width, so
+    //   they may take the CU's whole 160 KB (ensure_stream_lds, at the launch) -- at 64 KB nv = 32 with ny = 80 would already not pair
     bool stream_pair_ok() const {
+        if (structured || pairReq == RN_PAIR_OFF) return false;
         int G, NL;
         stream_shape(&G, &NL);
-        return !structured && !store32() && !(splitFirst >= 0 && splitFirst < d.nodes) && 2 * stream_lds(G) <= 64 * 1024;
+        if (store32()) return pairReq == RN_PAIR_ON && 2 * stream_lds(G) <= 160 * 1024;
+        return !(splitFirst >= 0 && splitFirst < d.nodes) && 2 * stream_lds(G) <= 64 * 1024;
     }
     static int slab_stride(int kp) { return (kp + 59) / 64 * 64 + 4; }   // >= kp, = 4 (mod 64): conflict-free MFMA B reads
     // waves per slab workgroup.  Many slabs (more workgroups than CUs): the count in {4, 6, 8} that wastes the least SIMD
@@ -1224,9 +1245,11 @@ struct Ctx : CtxBase {
         return best;
     }
     template <int EPI>
-    void launch_gemm(const T *Mp, int m, int k, const T *in, int ldin, T *out, int ldout, const T *aux, int ldaux) {
+    // sweepSplit: the splitFirst of the sweep whose m1 `aux` holds (SweepArgs; -1: the context's own -- a pair sweep runs unsplit on a split context)
+    void launch_gemm(const T *Mp, int m, int k, const T *in, int ldin, T *out, int ldout, const T *aux, int ldaux, int sweepSplit = -1) {
         GemmArgs<T> g{Mp, m, k, pad16(m), pad4(k), in, ldin, out, ldout, aux, ldaux, d_prob, d.nodes};
-        if (EPI == EPI_V && !structured && splitFirst >= 0 && splitFirst < d.nodes) { g.aux2 = d_my2; g.auxSplit = splitFirst; }   // k_stream_gemv's split last round
+        const int sf = sweepSplit >= 0 ? sweepSplit : splitFirst;
+        if (EPI == EPI_V && !structured && sf >= 0 && sf < d.nodes) { g.aux2 = d_my2; g.auxSplit = sf; }   // k_stream_gemv's split last round
 #if RN_GEMM_SLAB
         const int SB = slab_stride(g.kp);
         const size_t lds = (size_t)16 * SB * sizeof(T);
@@ -1381,7 +1404,7 @@ struct Ctx : CtxBase {
             return;
         }
 #endif
-        launch_gemm<EPI_V>(d_RTp, nv, nv + nx, a.sk, nv + nx, a.v, nv, a.my, 2 * nv);
+        launch_gemm<EPI_V>(d_RTp, nv, nv + nx, a.sk, nv + nx, a.v, nv, a.my, 2 * nv, a.splitFirst);
         launch_gemm<EPI_LV>(d_LBLp, nu + nx, nv, a.v, nv, a.lvb, nu + nx, nullptr, 0);   // [L v_i ; B L v_i]
     }
     // crown handling of the forward sweep: 0 = crown launches of their own; 1 = every chain workgroup walks its crown path and
@@ -1405,6 +1428,8 @@ struct Ctx : CtxBase {
     // hessianInput != nullptr: SmpcController::computeHessianOracalGlobalFbe (SmpcController.cu:884-1055) -- the same
     // sweep evaluated at `hessianInput` with sigma = 0 and every affine term zero, writing xdir / udir / H * dir
     // primalOut = false (inner iterations of a batch): x, u and v are not stored, only Hx (what the dual update reads)
+    // (fp32-stored blocks on a context whose streaming launch has a split last round: THIS sweep runs unsplit -- a.splitFirst = nodes, which
+    // every consumer of my2 follows: k_up_chain's selection, the v product's second partial -- and leaves d_my2 and the context's split alone)
     // hessianInput2 (with hessianInput; stream_pair_ok()): TWO Hessian sweeps whose inputs do not depend on each other's results share
     // ONE pass over the operator blocks (k_stream_gemv NR = 2); the vector recursions and shared-operator products then run once per
     // right-hand side.  The first sweep's results go to the pair buffers (d_xdirB, d_udirB, d_hxDirB), the second's where a Hessian
@@ -1425,8 +1450,9 @@ struct Ctx : CtxBase {
         }
         const bool pair = hessianInput2 != nullptr;
         if (pair) {
-            RN_CHECK(hessianInput && phase == 0 && d_myB && stream_pair_ok(), RN_E_STATE, "launch_sweep: a pair of sweeps needs two Hessian inputs, the pair buffers and an unsplit dense launch");
+            RN_CHECK(hessianInput && phase == 0 && d_myB && stream_pair_ok(), RN_E_STATE, "launch_sweep: a pair of sweeps needs two Hessian inputs, the pair buffers and a dense launch that can run unsplit");
             a.x = d_xdirB; a.u = d_udirB; a.hx = d_hxDirB;
+            if (store32()) a.splitFirst = d.nodes;
         }
         RN_CHECK(phase == 0 || a.cutSums, RN_E_STATE, "rn_debug_sweep_phase needs rn_set_cut_stage and nranks > 1");
         // one-shot exchange (inside rn_apg_iterate batches only): the launch that produces the cut parents' local sums pushes them
@@ -2708,6 +2734,17 @@ struct Ctx : CtxBase {
         block_layout();
         return RN_OK;
     }
+    int set_sweep_pairing(int mode) override {
+        RN_CHECK(mode == RN_PAIR_OFF || mode == RN_PAIR_ON || mode == RN_PAIR_AUTO, RN_E_ARG, "rn_set_sweep_pairing: RN_PAIR_OFF, RN_PAIR_ON or RN_PAIR_AUTO");
+        pairReq = mode;
+        if (algorithm == RN_ALG_NAMA) { RN_HIP(hipSetDevice(device)); return ensure_pair_buffers(); }
+        return RN_OK;
+    }
+    int get_sweep_pairing(int *requested, int *active) override {
+        if (requested) *requested = pairReq;
+        if (active) *active = (algorithm == RN_ALG_NAMA && pair_active()) ? 1 : 0;
+        return RN_OK;
+    }
     int get_operator_storage(int *requested, int *active) override {
         if (requested) *requested = storeReq;
         if (active) *active = (!structured && (d_A32 != nullptr || (sizeof(T) == 4 && d_A != nullptr))) ? RN_STORE_F32 : RN_STORE_NATIVE;
@@ -2843,6 +2880,8 @@ int rn_set_operator_mode(rn_ctx *ctx, int mode) { RN_GUARD(ctx); return ctx->imp
 int rn_get_operator_mode(rn_ctx *ctx, int *requested, int *active) { RN_GUARD(ctx); return ctx->impl->get_operator_mode(requested, active); }
 int rn_set_operator_storage(rn_ctx *ctx, int storage) { RN_GUARD(ctx); return ctx->impl->set_operator_storage(storage); }
 int rn_get_operator_storage(rn_ctx *ctx, int *requested, int *active) { RN_GUARD(ctx); return ctx->impl->get_operator_storage(requested, active); }
+int rn_set_sweep_pairing(rn_ctx *ctx, int mode) { RN_GUARD(ctx); return ctx->impl->set_sweep_pairing(mode); }
+int rn_get_sweep_pairing(rn_ctx *ctx, int *requested, int *active) { RN_GUARD(ctx); return ctx->impl->get_sweep_pairing(requested, active); }
 int rn_set_operator(rn_ctx *ctx, int op, int node, const double *h, size_t n) { RN_GUARD(ctx); return ctx->impl->set_operator(op, node, h, n); }
 int rn_set_warm_start(rn_ctx *ctx, int on) { RN_GUARD(ctx); return ctx->impl->set_warm_start(on); }
 int rn_set_exchange_mode(rn_ctx *ctx, int mode) { RN_GUARD(ctx); return ctx->impl->set_exchange_mode(mode); }
