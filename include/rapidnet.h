@@ -269,6 +269,30 @@ int rn_get_operator(rn_ctx *ctx, int op_id, int node, double *host, size_t n);
  * blocks by request): RN_E_STATE.  Omega_i, Theta_i, G_i are shared matrices scaled by p_i here (K identical copies in the reference,
  * Engine.cu:306-308): RN_E_ARG.  A context with RN_STORE_F32 blocks rounds the caller's values to the nearest fp32 on upload. */
 int rn_set_operator(rn_ctx *ctx, int op_id, int node, const double *host, size_t n);
+/* ALL per-node blocks in one call, as the reference's four arrays (Engine.cuh getMatPhi(), getMatPsi(), getMatD(), getMatF(): devMatPhi
+ * and devMatD are [node][2nx columns][nv], devMatPsi and devMatF [node][nu columns][nv], col-major, ld = nv, Engine.cu:166-205) -- for
+ * a caller whose blocks change with every control step: rn_set_operator costs two blocking copies of a whole block per call, these
+ * one kernel (k_pack_operators) that re-strides the arrays into (or out of) the interleaved block layout with the storage type's rounding
+ * (RN_STORE_F32: to nearest fp32, the bits rn_set_operator stores).  Any of the four pointers may be NULL: on a set that operator's rows
+ * keep their bits, on a get it is skipped; all four NULL: RN_E_ARG.  `nodes` must be the context's node count (the LOCAL one of a sharded
+ * context, rows in the order of rn_shard_global_nodes): otherwise RN_E_ARG.  State rules are rn_set_operator's: before rn_factor_step
+ * RN_E_STATE; a set on an RN_OPS_STRUCTURED context RN_E_STATE; an RN_OPS_AUTO context becomes dense on its first set (that one call
+ * allocates the blocks and synchronises); a later rn_factor_step recomputes every block.  The get forms read stored blocks: a context
+ * that runs the structured form has none -- RN_E_STATE, rn_get_operator evaluates one node's block there.
+ *   rn_set_operators / rn_get_operators: host arrays of doubles.  The kernel runs behind a device staging buffer of at most 64 MiB (one
+ *     node's arrays if they are larger), whole nodes per chunk, allocated and freed inside the call -- rn_device_memory_info's info[2] is
+ *     the same before and after.  They synchronise, as rn_set / rn_get do.
+ *   rn_set_operators_device / rn_get_operators_device (Engine.cuh getMatPhi() ... getMatF() written or read by a kernel of the caller's):
+ *     arrays in device memory, elements of type `precision` (RN_F32 floats, RN_F64 doubles, whatever the context's own precision and
+ *     storage are; any other value: RN_E_ARG).  One launch on the context's stream, no host synchronisation, no allocation: the next
+ *     sweep on that stream uses the new blocks, and the caller orders its own producer (or consumer) against the stream exactly as
+ *     rn_device_pointer describes (rn_stream).  Every non-NULL pointer is checked with hipPointerGetAttributes before anything is
+ *     launched: memory of the context's device, aligned to its element type and, where the runtime knows the allocation, long enough --
+ *     otherwise RN_E_ARG; a host pointer never reaches the kernel. */
+int rn_set_operators(rn_ctx *ctx, size_t nodes, const double *phi, const double *psi, const double *D, const double *F);
+int rn_get_operators(rn_ctx *ctx, size_t nodes, double *phi, double *psi, double *D, double *F);
+int rn_set_operators_device(rn_ctx *ctx, size_t nodes, int precision, const void *phi, const void *psi, const void *D, const void *F);
+int rn_get_operators_device(rn_ctx *ctx, size_t nodes, int precision, void *phi, void *psi, void *D, void *F);
 /* The raw device pointer of a buffer that the library keeps in the reference's own layout -- the counterpart of the reference's raw
  * getters and protected device vectors for those arrays (Engine.cuh:108-318 getVecUhat / getVecBeta / getVecE / getPriceAlpha ...,
  * SmpcController.cuh:336-462 devVecX / devVecU / devVecV): RN_BUF_X, _U, _V, _UHAT, _E, _BETA, _ALPHA, _XDIR, _UDIR, node-major

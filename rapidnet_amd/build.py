@@ -158,6 +158,7 @@ BIN_DIR = os.path.join(HERE, "bin")
 TEST_HOST = os.path.join(BIN_DIR, "test_host")
 TEST_OPERATOR_STORAGE = os.path.join(BIN_DIR, "test_operator_storage")
 TEST_SWEEP_PAIRING = os.path.join(BIN_DIR, "test_sweep_pairing")
+TEST_OPERATOR_BULK = os.path.join(BIN_DIR, "test_operator_bulk")
 
 
 def build_host(force=False):
@@ -187,6 +188,11 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_SWEEP_PAIRING, test_src, "-L" + HERE, "-lrapidnet_host",
                                "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
         _stamp(TEST_SWEEP_PAIRING, [test_src] + deps + hdr)
+    test_src = os.path.join(ROOT, "tests", "cpp", "test_operator_bulk.cpp")
+    if force or _stale(TEST_OPERATOR_BULK, [test_src] + deps + hdr):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_OPERATOR_BULK, test_src, "-L" + HERE, "-lrapidnet_host",
+                               "-lrapidnet_hip", "-ldl", "-Wl,-rpath,$ORIGIN/.."])
+        _stamp(TEST_OPERATOR_BULK, [test_src] + deps + hdr)
     return LIB_HOST
 
 

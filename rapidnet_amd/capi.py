@@ -39,7 +39,7 @@ SYMBOLS = [
     "rn_update_primal_infeasibility", "rn_get_prox_distances", "rn_buffer_size", "rn_get", "rn_set", "rn_get_operator",
     "rn_device_pointer", "rn_profile_enable", "rn_profile_reset", "rn_profile_read", "rn_algorithmic_bytes", "rn_stream",
     "rn_comm_unique_id", "rn_comm_init", "rn_comm_init_timeout", "rn_comm_check", "rn_comm_library", "rn_set_cut_stage", "rn_get_history_parts", "rn_get_counters", "rn_debug_sweep_phase",
-    "rn_debug_cut_buffer", "rn_set_cut_children_moments", "rn_set_operator_mode", "rn_get_operator_mode", "rn_set_operator_storage", "rn_get_operator_storage", "rn_set_sweep_pairing", "rn_get_sweep_pairing", "rn_set_operator", "rn_set_warm_start", "rn_set_exchange_mode",
+    "rn_debug_cut_buffer", "rn_set_cut_children_moments", "rn_set_operator_mode", "rn_get_operator_mode", "rn_set_operator_storage", "rn_get_operator_storage", "rn_set_sweep_pairing", "rn_get_sweep_pairing", "rn_set_operator", "rn_set_operators", "rn_get_operators", "rn_set_operators_device", "rn_get_operators_device", "rn_set_warm_start", "rn_set_exchange_mode",
     "rn_measure_hbm", "rn_set_algorithm", "rn_fbe_reset", "rn_algorithm_fbe_nama", "rn_compute_hessian_oracle", "rn_compute_gradient_fbe",
     "rn_update_fixed_point_residual_nama", "rn_compute_lbfgs_direction", "rn_update_lbfgs_buffer", "rn_two_loop_recursion_lbfgs", "rn_compute_value_fbe",
     "rn_line_search_lbfgs_update", "rn_line_search_ame_lbfgs_update", "rn_lbfgs_state", "rn_lbfgs_column",
@@ -183,6 +183,10 @@ def load():
     lib.rn_set_sweep_pairing.argtypes = [vp, ip]
     lib.rn_get_sweep_pairing.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     lib.rn_set_operator.argtypes = [vp, ip, ip, dp, C.c_size_t]
+    lib.rn_set_operators.argtypes = [vp, C.c_size_t, dp, dp, dp, dp]
+    lib.rn_get_operators.argtypes = [vp, C.c_size_t, dp, dp, dp, dp]
+    lib.rn_set_operators_device.argtypes = [vp, C.c_size_t, ip, vp, vp, vp, vp]
+    lib.rn_get_operators_device.argtypes = [vp, C.c_size_t, ip, vp, vp, vp, vp]
     lib.rn_set_warm_start.argtypes = [vp, ip]
     lib.rn_set_exchange_mode.argtypes = [vp, ip]
     lib.rn_debug_sweep_phase.argtypes = [vp, ip]
@@ -520,6 +524,37 @@ class Solver:
         """hand in one node's block (OP_PHI, OP_PSI, OP_D, OP_F; col-major nv x (2nx | nu)); an auto context becomes dense"""
         v = _f64(values)
         self._check(self.lib.rn_set_operator(self.h, int(op), int(node), v.ctypes.data, v.size))
+
+    def _opDims(self):
+        return {"Phi": self.nv * 2 * self.nx, "Psi": self.nv * self.nu, "D": self.nv * 2 * self.nx, "Ftil": self.nv * self.nu}
+
+    def setOperators(self, phi=None, psi=None, D=None, F=None):
+        """rn_set_operators: every node's blocks at once from numpy arrays in the reference's layout ([nodes][2nx | nu columns][nv]); None: that
+        operator stays as it is.  An auto context becomes dense."""
+        dims = self._opDims()
+        arrs = [None if v is None else _f64(v) for v in (phi, psi, D, F)]
+        for a, nm in zip(arrs, ("Phi", "Psi", "D", "Ftil")):
+            if a is not None and a.size != self.nodes * dims[nm]:
+                raise ValueError("setOperators: %s needs %d x %d values, got %d" % (nm, self.nodes, dims[nm], a.size))
+        self._check(self.lib.rn_set_operators(self.h, self.nodes, *[None if a is None else a.ctypes.data for a in arrs]))
+
+    def getOperators(self, ops=("Phi", "Psi", "D", "Ftil")):
+        """rn_get_operators: {name: [nodes][dim]} the stored blocks of the named operators (a context with dense blocks)"""
+        dims = self._opDims()
+        out = {nm: np.zeros((self.nodes, dims[nm])) for nm in ops}
+        self._check(self.lib.rn_get_operators(self.h, self.nodes, *[out[nm].ctypes.data if nm in out else None for nm in ("Phi", "Psi", "D", "Ftil")]))
+        return out
+
+    def setOperatorsDevice(self, precision, phi=0, psi=0, D=0, F=0, nodes=None):
+        """rn_set_operators_device: integer device addresses (0: not given) of arrays of `precision` ("f64" | "f32" or an RN_F* value)
+        elements; one launch on the context's stream, nothing is waited for"""
+        prec = {"f64": RN_F64, "f32": RN_F32}.get(precision, precision)
+        self._check(self.lib.rn_set_operators_device(self.h, self.nodes if nodes is None else int(nodes), int(prec), *[int(p) or None for p in (phi, psi, D, F)]))
+
+    def getOperatorsDevice(self, precision, phi=0, psi=0, D=0, F=0, nodes=None):
+        """rn_get_operators_device: the stored blocks into the caller's device arrays (0: skipped); stream-ordered, not waited for"""
+        prec = {"f64": RN_F64, "f32": RN_F32}.get(precision, precision)
+        self._check(self.lib.rn_get_operators_device(self.h, self.nodes if nodes is None else int(nodes), int(prec), *[int(p) or None for p in (phi, psi, D, F)]))
 
     def operatorMode(self):
         """(requested, active) as "dense" | "structured" | "auto" """

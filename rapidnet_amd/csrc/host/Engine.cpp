@@ -63,6 +63,17 @@ int Engine::getSweepPairing(int *active) {
 }
 void Engine::setOperator(int op, uint_t node, const real_t *host, size_t n) { check(rn_set_operator(ctx, op, node, host, n), "rn_set_operator"); }
 
+void Engine::setOperators(const real_t *phi, const real_t *psi, const real_t *D, const real_t *F) {
+    check(rn_set_operators(ctx, getNumLocalNodes(), phi, psi, D, F), "rn_set_operators");
+}
+void Engine::getOperators(real_t *phi, real_t *psi, real_t *D, real_t *F) { check(rn_get_operators(ctx, getNumLocalNodes(), phi, psi, D, F), "rn_get_operators"); }
+void Engine::setOperatorsDevice(int precision, const void *phi, const void *psi, const void *D, const void *F) {
+    check(rn_set_operators_device(ctx, getNumLocalNodes(), precision, phi, psi, D, F), "rn_set_operators_device");
+}
+void Engine::getOperatorsDevice(int precision, void *phi, void *psi, void *D, void *F) {
+    check(rn_get_operators_device(ctx, getNumLocalNodes(), precision, phi, psi, D, F), "rn_get_operators_device");
+}
+
 void Engine::create(int precision, int device, int operatorMode, int rank, int nranks, const void *id128, int cutStage) {
     myRank = rank; numRanks = nranks;
     priceUncertaintyFlag = true; demandUncertaintyFlag = true;

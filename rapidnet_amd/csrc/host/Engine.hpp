@@ -7,6 +7,7 @@
 //                                                       reference's name: getVecUhat(), getVecBeta(), getVecE(), getPriceAlpha()
 //                                                       (element type = the engine's precision: getDevicePrecision())
 //   getMatPhi() / getPtrMatPhi()[node] ...              getOperator(RN_OP_PHI, node, host) ...  (the blocks are stored interleaved: DESIGN.md section 4)
+//   getMatPhi() ... getMatF() as whole arrays           setOperators / getOperators (host arrays), setOperatorsDevice / getOperatorsDevice (device arrays)
 #ifndef RAPIDNET_ENGINE_HPP_
 #define RAPIDNET_ENGINE_HPP_
 
@@ -49,6 +50,15 @@ public:
     // a per-node block handed in by the caller (the reference: write through getMatPhi() / getPtrMatPhi()[node] ..., Engine.cuh:170-230);
     // RN_OP_PHI, _PSI, _D, _F, col-major nv x (2nx | nu); after factorStep()
     void setOperator(int opId, uint_t node, const real_t *host, size_t n);
+    // ... and all of them at once, as the reference's whole arrays (getMatPhi(), getMatPsi(), getMatD(), getMatF(), Engine.cuh:170-230: [node][2nx | nu
+    // columns][nv]; getNumLocalNodes() nodes): rapidnet.h, rn_set_operators.  A null pointer leaves that operator as it is (set) or out (get).
+    // Host arrays (these synchronise) ...
+    void setOperators(const real_t *phi, const real_t *psi, const real_t *D, const real_t *F);
+    void getOperators(real_t *phi, real_t *psi, real_t *D, real_t *F);
+    // ... or device arrays of RN_F32 / RN_F64 elements, filled or read by the caller's own kernels: one launch on the engine's stream
+    // (rn_stream(getContext())), nothing is waited for
+    void setOperatorsDevice(int precision, const void *phi, const void *psi, const void *D, const void *F);
+    void getOperatorsDevice(int precision, void *phi, void *psi, void *D, void *F);
     int getRank() { return myRank; }
     int getNumRanks() { return numRanks; }
     uint_t getNumLocalNodes();                       // nodes this rank holds (= the tree's node count on one GPU)

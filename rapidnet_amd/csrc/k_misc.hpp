@@ -72,6 +72,104 @@ __global__ void k_expand_operators(ExpandArgs<T, S> a) {
 }
 
 // ------------------------------------------------------------------------------------------------------
+// All per-node blocks at once, to or from the caller's four arrays in the reference's layout (rn_set_operators / rn_get_operators and their
+// _device forms; Engine.cuh getMatPhi() ... getMatF(): Phi, D [node][2nx columns][nv], Psi, F [node][nu columns][nv], dense, ld = nv).  The
+// block layout is k_expand_operators' above: column c of a node at A + node * strideA + c * LD, rows [0, nv) Phi | Psi, [nv, 2nv) D | Ftil,
+// [2nv, LD) padding.
+// TO_BLOCKS: a lane owns one 16-byte slot of a block column (2 doubles or 4 floats; LD is whole slots), gathers its entries from the one or
+// two arrays they come from -- a slot straddles the Phi / D boundary or reaches into the padding whenever nv is no multiple of the slot
+// width --, converts each with a plain cast (the only rounding: fp64 -> fp32 to nearest, what Ctx::upload_block does on the host) and stores
+// the slot once.  Where a slot holds entries that are not the caller's -- padding rows, rows of an array that was not given (nullptr) -- the
+// lane reads the slot first and replaces only the given ones; a slot with none is not touched.  Every slot has one owner: no races, and
+// neither the padding rows nor the tail of strideA change.  The other direction reads slots and scatters entry by entry.
+// Consecutive lanes own consecutive slots of a node's block (columns are adjacent), so the block side is one flat 16-B-per-lane stream and
+// the caller's side is contiguous per array; it is read 16 B wide where a slot's entries lie in one array at a 16-byte boundary, entry by
+// entry otherwise (still coalesced).  Non-temporal both ways, as k_bw_copy.  Launch: blockIdx.x strides the slots of one node, blockIdx.y
+// the nodes -- numCUs * 4 workgroups in all, the shape rn_measure_hbm found best for a read + write stream.
+// The element types arrive as flags and not as template parameters: the four (caller, stored) pairs in two directions would be eight
+// kernels; the branch is uniform over the grid.
+struct PackOpsArgs {
+    void *A;              // the blocks, doubles or floats (storedF64), first node of the range
+    size_t strideA;       // in stored entries
+    void *op[4];          // caller's phi, psi, D, F: doubles or floats (callerF64), first node of the range; nullptr: not given
+    int LD, nv, nx2, nu, nodes;
+    int callerF64, storedF64;
+};
+constexpr int PACK_THREADS = 256;
+typedef float nat_f2 __attribute__((ext_vector_type(2)));
+// the N entries of a slot that lie behind one another at p, which is aligned to min(16, N * sizeof(C)) bytes
+__device__ __forceinline__ nat_d2 pack_load_run(const double *p, nat_d2) { return __builtin_nontemporal_load(reinterpret_cast<const nat_d2 *>(p)); }
+__device__ __forceinline__ nat_f4 pack_load_run(const float *p, nat_f4) { return __builtin_nontemporal_load(reinterpret_cast<const nat_f4 *>(p)); }
+__device__ __forceinline__ nat_f4 pack_load_run(const double *p, nat_f4) {
+    const nat_d2 a = __builtin_nontemporal_load(reinterpret_cast<const nat_d2 *>(p)), b = __builtin_nontemporal_load(reinterpret_cast<const nat_d2 *>(p) + 1);
+    nat_f4 v; v[0] = (float)a[0]; v[1] = (float)a[1]; v[2] = (float)b[0]; v[3] = (float)b[1];
+    return v;
+}
+__device__ __forceinline__ nat_d2 pack_load_run(const float *p, nat_d2) {
+    const nat_f2 a = __builtin_nontemporal_load(reinterpret_cast<const nat_f2 *>(p));
+    nat_d2 v; v[0] = (double)a[0]; v[1] = (double)a[1];
+    return v;
+}
+template <typename C, typename S, bool TO_BLOCKS>
+__device__ __forceinline__ void pack_operators_body(const PackOpsArgs &a) {
+    typedef typename Slot<S>::type slot_t;
+    constexpr int VPS = Slot<S>::N;
+    constexpr unsigned RUN_ALIGN = VPS * sizeof(C) < 16 ? VPS * sizeof(C) : 16;
+    const int nv = a.nv, spc = a.LD / VPS, perNode = (a.nx2 + a.nu) * spc;
+    C *const phi = static_cast<C *>(a.op[0]), *const psi = static_cast<C *>(a.op[1]), *const D = static_cast<C *>(a.op[2]), *const F = static_cast<C *>(a.op[3]);
+    for (int node = blockIdx.y; node < a.nodes; node += gridDim.y) {
+        S *const blk = static_cast<S *>(a.A) + (size_t)node * a.strideA;
+        for (int j = blockIdx.x * PACK_THREADS + threadIdx.x; j < perNode; j += gridDim.x * PACK_THREADS) {
+            const int c = j / spc, r0 = (j - c * spc) * VPS;
+            const bool xi = c < a.nx2;
+            C *const top = xi ? phi : psi, *const bot = xi ? D : F;
+            if (!top && !bot) continue;
+            const size_t off = ((size_t)node * (xi ? a.nx2 : a.nu) + (xi ? c : c - a.nx2)) * nv;   // this column in either array
+            slot_t *const slot = reinterpret_cast<slot_t *>(blk + (size_t)c * a.LD + r0);
+            if (TO_BLOCKS) {
+                bool all = true, any = false;
+#pragma unroll
+                for (int k = 0; k < VPS; k++) {
+                    const int r = r0 + k;
+                    const bool given = r < nv ? top != nullptr : (r < 2 * nv && bot != nullptr);
+                    all = all && given; any = any || given;
+                }
+                if (!any) continue;
+                const C *run = nullptr;   // the slot's entries lie in one array
+                if (r0 + VPS <= nv) run = top + off + r0;
+                else if (r0 >= nv && r0 + VPS <= 2 * nv) run = bot + off + (r0 - nv);
+                slot_t v;
+                if (run && (reinterpret_cast<uintptr_t>(run) & (RUN_ALIGN - 1)) == 0) v = pack_load_run(run, slot_t());
+                else {
+                    if (!all) v = __builtin_nontemporal_load(slot);
+#pragma unroll
+                    for (int k = 0; k < VPS; k++) {
+                        const int r = r0 + k;
+                        if (r < nv) { if (top) v[k] = (S)__builtin_nontemporal_load(top + off + r); }
+                        else if (r < 2 * nv) { if (bot) v[k] = (S)__builtin_nontemporal_load(bot + off + (r - nv)); }
+                    }
+                }
+                __builtin_nontemporal_store(v, slot);
+            } else {
+                if (r0 >= 2 * nv) continue;
+                const slot_t v = __builtin_nontemporal_load(slot);
+#pragma unroll
+                for (int k = 0; k < VPS; k++) {
+                    const int r = r0 + k;
+                    if (r < nv) { if (top) __builtin_nontemporal_store((C)v[k], top + off + r); }
+                    else if (r < 2 * nv) { if (bot) __builtin_nontemporal_store((C)v[k], bot + off + (r - nv)); }
+                }
+            }
+        }
+    }
+}
+template <bool TO_BLOCKS>
+__global__ void __launch_bounds__(PACK_THREADS) k_pack_operators(PackOpsArgs a) {
+    if (a.callerF64) { if (a.storedF64) pack_operators_body<double, double, TO_BLOCKS>(a); else pack_operators_body<double, float, TO_BLOCKS>(a); }
+    else { if (a.storedF64) pack_operators_body<float, double, TO_BLOCKS>(a); else pack_operators_body<float, float, TO_BLOCKS>(a); }
+}
+
+// ------------------------------------------------------------------------------------------------------
 // Per-control-step affine terms (Engine::eliminateInputDistubanceCoupling Engine.cu:1147-1298), two kernels,
 // one workgroup per node:
 //   k_affine_demand: d_i = errD_i + dhat[stage]; e_i = Gd d_i; uhat_i = Lhat d_i;

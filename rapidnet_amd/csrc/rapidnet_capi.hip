@@ -178,6 +178,8 @@ struct CtxBase {
     virtual int set_operator_mode(int) = 0;
     virtual int get_operator_mode(int *, int *) = 0;
     virtual int set_operator(int, int, const double *, size_t) = 0;
+    virtual int set_operators(size_t, int, bool, const void *const *) = 0;
+    virtual int get_operators(size_t, int, bool, void *const *) = 0;
     virtual int set_warm_start(int) = 0;
     virtual int set_exchange_mode(int) = 0;
     virtual int set_cut_moments(const double *, const double *, size_t) = 0;
@@ -2783,6 +2785,108 @@ struct Ctx : CtxBase {
         for (int c = 0; c < cols; c++) for (int r = 0; r < nv; r++) blk[(size_t)(c0 + c) * LD + r0 + r] = host[r + (size_t)c * nv];
         return upload_block(node, blk.data());      // (fp32 storage: the caller's values rounded to nearest)
     }
+    // ---- all blocks at once (rn_set_operators / rn_get_operators and their _device forms; k_pack_operators, k_misc.hpp) ----
+    static constexpr size_t PACK_STAGING_BYTES = (size_t)64 << 20;   // the host forms' device staging buffer (rapidnet.h says so)
+    size_t op_cols(int i) const { return i == 0 || i == 2 ? 2 * (size_t)d.nx : (size_t)d.nu; }   // columns of phi, psi, D, F
+    // `count` nodes from `node0` on, to or from caller arrays that START at node0; one launch on the context's stream
+    void pack_launch(bool toBlocks, bool callerF64, void *const op[4], int node0, int count) {
+        PackOpsArgs a{};
+        a.A = store32() ? (void *)(d_A32 + (size_t)node0 * strideA) : (void *)(d_A + (size_t)node0 * strideA);
+        a.strideA = strideA; a.LD = LD; a.nv = d.nv; a.nx2 = 2 * d.nx; a.nu = d.nu; a.nodes = count;
+        for (int i = 0; i < 4; i++) a.op[i] = op[i];
+        a.callerF64 = callerF64 ? 1 : 0; a.storedF64 = block_elem() == 8 ? 1 : 0;
+        const long long perNode = (long long)ny * (LD / (16 / block_elem()));
+        const int gx = (int)std::min<long long>((perNode + PACK_THREADS - 1) / PACK_THREADS, (long long)numCUs * 4);
+        const int gy = std::max(1, std::min(count, numCUs * 4 / gx));
+        if (toBlocks) hipLaunchKernelGGL(k_pack_operators<true>, dim3(gx, gy), dim3(PACK_THREADS), 0, stream, a);
+        else hipLaunchKernelGGL(k_pack_operators<false>, dim3(gx, gy), dim3(PACK_THREADS), 0, stream, a);
+    }
+    // a caller's device array: memory of this context's device (hipPointerGetAttributes) that holds `bytes` bytes from p on.  Anything
+    // else -- a host pointer above all -- is refused here, before a kernel could see it
+    int check_device_array(const void *p, size_t bytes, size_t elem, const std::string &what) {
+        RN_CHECK(((uintptr_t)p & (elem - 1)) == 0, RN_E_ARG, what + ": a pointer is not aligned to its element type");
+        hipPointerAttribute_t at;
+        std::memset(&at, 0, sizeof at);
+        if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); err = what + ": a pointer is not device memory"; return RN_E_ARG; }
+        RN_CHECK(at.type == hipMemoryTypeDevice, RN_E_ARG, what + ": a pointer is not device memory");
+        RN_CHECK(at.device == device, RN_E_ARG, what + ": a pointer is memory of another device than the context's");
+        hipDeviceptr_t base = nullptr; size_t len = 0;
+        if (hipMemGetAddressRange(&base, &len, (hipDeviceptr_t)p) == hipSuccess)
+            RN_CHECK((const char *)p >= (const char *)base && (size_t)((const char *)p - (const char *)base) + bytes <= len, RN_E_ARG,
+                     what + ": an array is shorter than nodes x nv x columns elements");
+        else (void)hipGetLastError();
+        return RN_OK;
+    }
+    int pack_args_ok(const char *what, size_t nodes, int callerPrec, bool dev, const void *const *op) {
+        RN_CHECK(factored, RN_E_STATE, std::string(what) + " before rn_factor_step");
+        RN_CHECK(nodes == (size_t)d.nodes, RN_E_ARG, std::string(what) + ": nodes must be the context's (local) node count");
+        RN_CHECK(callerPrec == RN_F64 || callerPrec == RN_F32, RN_E_ARG, std::string(what) + ": precision is RN_F32 or RN_F64");
+        RN_CHECK(op[0] || op[1] || op[2] || op[3], RN_E_ARG, std::string(what) + ": all four arrays are NULL");
+        (void)dev;
+        return RN_OK;
+    }
+    int set_operators(size_t nodes, int callerPrec, bool dev, const void *const *op) override {
+        const char *what = dev ? "rn_set_operators_device" : "rn_set_operators";
+        if (int rc = pack_args_ok(what, nodes, callerPrec, dev, op)) return rc;
+        RN_CHECK(opsMode != RN_OPS_STRUCTURED, RN_E_STATE, std::string(what) + ": the context was created with RN_OPS_STRUCTURED (no per-node blocks); use RN_OPS_AUTO or RN_OPS_DENSE");
+        RN_HIP(hipSetDevice(device));
+        const size_t elem = callerPrec == RN_F64 ? 8 : 4;
+        if (dev) for (int i = 0; i < 4; i++)
+            if (op[i]) { if (int rc = check_device_array(op[i], nodes * op_cols(i) * d.nv * elem, elem, what)) return rc; }
+        if (structured) { if (int rc = materialise_dense()) return rc; }     // (RN_OPS_AUTO, first block of the caller's: allocates and synchronises, once)
+        void *p[4] = {const_cast<void *>(op[0]), const_cast<void *>(op[1]), const_cast<void *>(op[2]), const_cast<void *>(op[3])};   // (read only: TO_BLOCKS)
+        if (!dev) return pack_staged(true, p);
+        pack_launch(true, callerPrec == RN_F64, p, 0, d.nodes);
+        RN_HIP(hipGetLastError());
+        return RN_OK;
+    }
+    int get_operators(size_t nodes, int callerPrec, bool dev, void *const *op) override {
+        const char *what = dev ? "rn_get_operators_device" : "rn_get_operators";
+        if (int rc = pack_args_ok(what, nodes, callerPrec, dev, op)) return rc;
+        RN_CHECK(!structured, RN_E_STATE, std::string(what) + ": the context holds no dense blocks (structured operator mode); rn_get_operator evaluates one node's block");
+        RN_HIP(hipSetDevice(device));
+        const size_t elem = callerPrec == RN_F64 ? 8 : 4;
+        if (dev) {
+            for (int i = 0; i < 4; i++)
+                if (op[i]) { if (int rc = check_device_array(op[i], nodes * op_cols(i) * d.nv * elem, elem, what)) return rc; }
+            pack_launch(false, callerPrec == RN_F64, op, 0, d.nodes);
+            RN_HIP(hipGetLastError());
+            return RN_OK;
+        }
+        return pack_staged(false, op);
+    }
+    // the host forms: the same kernel behind a device staging buffer of at most PACK_STAGING_BYTES (one node's arrays if those are larger),
+    // whole nodes per chunk; the buffer lives inside the call and is not one of the context's allocations
+    int pack_staged(bool toBlocks, void *const *host) {
+        size_t perNode = 0;
+        for (int i = 0; i < 4; i++) if (host[i]) perNode += op_cols(i) * d.nv * sizeof(double);
+        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)d.nodes, PACK_STAGING_BYTES / perNode));
+        char *stage = nullptr;
+        RN_HIP(hipMalloc((void **)&stage, (size_t)chunk * perNode));
+        hipError_t e = hipSuccess;
+        for (int n0 = 0; n0 < d.nodes && e == hipSuccess; n0 += chunk) {
+            const int cnt = std::min(chunk, d.nodes - n0);
+            void *dv[4] = {nullptr, nullptr, nullptr, nullptr};
+            size_t at = 0;
+            for (int i = 0; i < 4; i++) if (host[i]) { dv[i] = stage + at; at += (size_t)chunk * op_cols(i) * d.nv * sizeof(double); }
+            if (toBlocks)
+                for (int i = 0; i < 4 && e == hipSuccess; i++) if (host[i]) {
+                    const size_t per = op_cols(i) * d.nv * sizeof(double);
+                    e = hipMemcpyAsync(dv[i], (const char *)host[i] + (size_t)n0 * per, (size_t)cnt * per, hipMemcpyHostToDevice, stream);
+                }
+            if (e == hipSuccess) { pack_launch(toBlocks, true, dv, n0, cnt); e = hipGetLastError(); }
+            if (!toBlocks)
+                for (int i = 0; i < 4 && e == hipSuccess; i++) if (host[i]) {
+                    const size_t per = op_cols(i) * d.nv * sizeof(double);
+                    e = hipMemcpyAsync((char *)host[i] + (size_t)n0 * per, dv[i], (size_t)cnt * per, hipMemcpyDeviceToHost, stream);
+                }
+        }
+        const hipError_t es = hipStreamSynchronize(stream);    // (before the buffer goes: everything that uses it is on this stream)
+        (void)hipFree(stage);
+        RN_HIP(e);
+        RN_HIP(es);
+        return RN_OK;
+    }
     int set_cut_moments(const double *E, const double *P, size_t nParents) override {
         RN_CHECK(cutStage > 0, RN_E_STATE, "rn_set_cut_children_moments: set the cut stage first");
         RN_CHECK(E && P && nParents == (size_t)(h_stageCum[cutStage] - h_stageCum[cutStage - 1]), RN_E_ARG, "rn_set_cut_children_moments: one row per cut parent expected");
@@ -2883,6 +2987,18 @@ int rn_get_operator_storage(rn_ctx *ctx, int *requested, int *active) { RN_GUARD
 int rn_set_sweep_pairing(rn_ctx *ctx, int mode) { RN_GUARD(ctx); return ctx->impl->set_sweep_pairing(mode); }
 int rn_get_sweep_pairing(rn_ctx *ctx, int *requested, int *active) { RN_GUARD(ctx); return ctx->impl->get_sweep_pairing(requested, active); }
 int rn_set_operator(rn_ctx *ctx, int op, int node, const double *h, size_t n) { RN_GUARD(ctx); return ctx->impl->set_operator(op, node, h, n); }
+int rn_set_operators(rn_ctx *ctx, size_t nodes, const double *phi, const double *psi, const double *D, const double *F) {
+    RN_GUARD(ctx); const void *op[4] = {phi, psi, D, F}; return ctx->impl->set_operators(nodes, RN_F64, false, op);
+}
+int rn_get_operators(rn_ctx *ctx, size_t nodes, double *phi, double *psi, double *D, double *F) {
+    RN_GUARD(ctx); void *op[4] = {phi, psi, D, F}; return ctx->impl->get_operators(nodes, RN_F64, false, op);
+}
+int rn_set_operators_device(rn_ctx *ctx, size_t nodes, int precision, const void *phi, const void *psi, const void *D, const void *F) {
+    RN_GUARD(ctx); const void *op[4] = {phi, psi, D, F}; return ctx->impl->set_operators(nodes, precision, true, op);
+}
+int rn_get_operators_device(rn_ctx *ctx, size_t nodes, int precision, void *phi, void *psi, void *D, void *F) {
+    RN_GUARD(ctx); void *op[4] = {phi, psi, D, F}; return ctx->impl->get_operators(nodes, precision, true, op);
+}
 int rn_set_warm_start(rn_ctx *ctx, int on) { RN_GUARD(ctx); return ctx->impl->set_warm_start(on); }
 int rn_set_exchange_mode(rn_ctx *ctx, int mode) { RN_GUARD(ctx); return ctx->impl->set_exchange_mode(mode); }
 int rn_measure_hbm(rn_ctx *ctx, size_t bytes, int reps, double *r, double *c) { RN_GUARD(ctx); return ctx->impl->measure_hbm(bytes, reps, r, c); }
