@@ -185,6 +185,29 @@ int rn_apg_reset(rn_ctx *ctx);
 int rn_apg_iterate(rn_ctx *ctx, int n, double *primalInfs);
 /* SmpcController::algorithmApg (SmpcController.cu:1500-1525) = rn_apg_reset + rn_apg_iterate(maxIterations) */
 int rn_algorithm_apg(rn_ctx *ctx, int maxIterations, double *primalInfs);
+/* Extension: SmpcController::algorithmApg runs maxIterations whatever the residual (SmpcController.cu:1500-1525), although it records the
+ * primal infeasibility of every iteration (updatePrimalInfeasibity, :1480-1496, into vecPrimalInfs, :1521).  rn_apg_solve = rn_apg_reset, then
+ * batches of checkEvery iterations (the last one shorter when maxIterations is no multiple) exactly as rn_apg_iterate(checkEvery) runs them;
+ * after each batch the solve ends if the residual of that batch's LAST iteration -- the entry rn_apg_iterate returns in primalInfs -- is <= tol.
+ * The iterates are therefore bit for bit those of rn_apg_reset followed by the same sequence of rn_apg_iterate calls; a batch that was replayed
+ * through the exact path is judged on the replay.  The decision is the host's, taken behind the synchronisation that closes a batch; the
+ * launch that closes the batch publishes what it needs.  On a sharded context every rank calls it and every rank stops at the same count.
+ * maxIterations as rn_algorithm_apg; tol >= 0 (0: never stops early); checkEvery <= 0: the library's default (20); values below 16 run the
+ * exact path, as rn_apg_iterate with that n does.  *iterationsRun (required) = iterations run; primalInfs (may be NULL, maxIterations entries)
+ * receives the first *iterationsRun entries of vecPrimalInfs.  tol negative, NaN or infinite, maxIterations < 0, iterationsRun NULL: RN_E_ARG;
+ * before the factor step or the affine terms: RN_E_STATE.  Within rn_reserve_iterations no device memory is allocated. */
+int rn_apg_solve(rn_ctx *ctx, int maxIterations, double tol, int checkEvery, int *iterationsRun, double *primalInfs);
+/* Extension (SmpcController.cu:1500-1525, :1480-1496 as above): what rn_control_action and rn_algorithm_apg then do -- with tol > 0 they run the
+ * loop of rn_apg_solve in place of their one batch of maxIterations (rn_control_action after its own reset or warm start, rn_set_warm_start).
+ * The default, tol = 0, is the fixed iteration count of the reference, bit for bit.  checkEvery <= 0: the library's default (20).  The
+ * quasi-Newton loops (rn_algorithm_fbe_nama) ignore the setting. */
+int rn_set_stop_tolerance(rn_ctx *ctx, double tol, int checkEvery);
+/* the setting of rn_set_stop_tolerance (SmpcController.cu:1500-1525, :1480-1496); either pointer may be NULL */
+int rn_get_stop_tolerance(rn_ctx *ctx, double *tol, int *checkEvery);
+/* Of the last rn_apg_solve / rn_algorithm_apg / rn_control_action (the count the reference fixes in advance, SmpcController.cu:1500-1525; the
+ * residuals of :1480-1496): out = {iterations it ran, 1 if it stopped on the tolerance, first iteration (0-based, within that solve) whose
+ * residual was <= tol or -1 (also -1 when no tolerance was set), batches run}. */
+int rn_get_last_solve(rn_ctx *ctx, long out[4]);
 /* SmpcController::controlAction(real_t*) (SmpcController.cu:1607-1625): update state, eliminate, APG, copy u of the root node
  * (nu reals) to the host.  The reference's leak check around these calls (cudaMemGetInfo before and after, :1612-1623) is the
  * caller's, with rn_device_memory_info below -- the host class SmpcController::controlAction does exactly that. */

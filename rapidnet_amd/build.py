@@ -159,6 +159,7 @@ TEST_HOST = os.path.join(BIN_DIR, "test_host")
 TEST_OPERATOR_STORAGE = os.path.join(BIN_DIR, "test_operator_storage")
 TEST_SWEEP_PAIRING = os.path.join(BIN_DIR, "test_sweep_pairing")
 TEST_OPERATOR_BULK = os.path.join(BIN_DIR, "test_operator_bulk")
+TEST_STOP_TOLERANCE = os.path.join(BIN_DIR, "test_stop_tolerance")
 
 
 def build_host(force=False):
@@ -193,6 +194,11 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_OPERATOR_BULK, test_src, "-L" + HERE, "-lrapidnet_host",
                                "-lrapidnet_hip", "-ldl", "-Wl,-rpath,$ORIGIN/.."])
         _stamp(TEST_OPERATOR_BULK, [test_src] + deps + hdr)
+    test_src = os.path.join(ROOT, "tests", "cpp", "test_stop_tolerance.cpp")
+    if force or _stale(TEST_STOP_TOLERANCE, [test_src] + deps + hdr):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_STOP_TOLERANCE, test_src, "-L" + HERE, "-lrapidnet_host",
+                               "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
+        _stamp(TEST_STOP_TOLERANCE, [test_src] + deps + hdr)
     return LIB_HOST
 
 

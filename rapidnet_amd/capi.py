@@ -34,7 +34,7 @@ EXCHANGE_COLLECTIVE, EXCHANGE_ONESHOT, EXCHANGE_AUTO = 0, 1, 2
 SYMBOLS = [
     "rn_create", "rn_destroy", "rn_last_error", "rn_synchronize", "rn_factor_step", "rn_set_tree_errors",
     "rn_set_uncertainty", "rn_update_state_control", "rn_eliminate_input_disturbance_coupling", "rn_set_parameters",
-    "rn_apg_reset", "rn_apg_iterate", "rn_algorithm_apg", "rn_control_action", "rn_dual_extrapolation_step",
+    "rn_apg_reset", "rn_apg_iterate", "rn_algorithm_apg", "rn_apg_solve", "rn_set_stop_tolerance", "rn_get_stop_tolerance", "rn_get_last_solve", "rn_control_action", "rn_dual_extrapolation_step",
     "rn_solve_step", "rn_proximal_fun_g", "rn_compute_fixed_point_residual", "rn_dual_update",
     "rn_update_primal_infeasibility", "rn_get_prox_distances", "rn_buffer_size", "rn_get", "rn_set", "rn_get_operator",
     "rn_device_pointer", "rn_profile_enable", "rn_profile_reset", "rn_profile_read", "rn_algorithmic_bytes", "rn_stream",
@@ -146,6 +146,10 @@ def load():
     lib.rn_apg_reset.argtypes = [vp]
     lib.rn_apg_iterate.argtypes = [vp, ip, dp]
     lib.rn_algorithm_apg.argtypes = [vp, ip, dp]
+    lib.rn_apg_solve.argtypes = [vp, ip, C.c_double, ip, C.POINTER(C.c_int), dp]
+    lib.rn_set_stop_tolerance.argtypes = [vp, C.c_double, ip]
+    lib.rn_get_stop_tolerance.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    lib.rn_get_last_solve.argtypes = [vp, dp]
     lib.rn_control_action.argtypes = [vp, dp, dp, dp, dp, dp, ip, ip, dp]
     lib.rn_dual_extrapolation_step.argtypes = [vp, C.c_double]
     for f in ("rn_solve_step", "rn_proximal_fun_g", "rn_compute_fixed_point_residual", "rn_dual_update"):
@@ -259,7 +263,8 @@ class Solver:
     """
 
     def __init__(self, network, tree, config, precision="f64", device=0, structured=False, rank=0, nranks=1, cut_stage=0,
-                 unique_id=None, knobs=None, operator_mode=None, operator_storage="native", sweep_pairing="auto"):
+                 unique_id=None, knobs=None, operator_mode=None, operator_storage="native", sweep_pairing="auto", stop_tolerance=0.0,
+                 stop_check_every=0):
         """nranks > 1: `tree` is the FULL scenario tree and the context is rank `rank`'s shard of it (rn_create_sharded:
         partition, communicator from `unique_id` -- None = none, the exchange is a test's job --, cut stage, children
         moments); self.nodes is then the LOCAL node count and self.global_nodes maps local -> full-tree node ids.
@@ -268,7 +273,9 @@ class Solver:
         operator_storage: "native" | "f32" (rn_set_operator_storage): the element type of the dense blocks; "f32" on an f64 context
         streams half the bytes and accumulates in fp64.
         sweep_pairing: "auto" | "on" | "off" (rn_set_sweep_pairing): NAMA's two Hessian sweeps in one pass over the dense blocks; "on" adds
-        fp32-stored blocks to what "auto" pairs."""
+        fp32-stored blocks to what "auto" pairs.
+        stop_tolerance, stop_check_every (rn_set_stop_tolerance): with a tolerance > 0 controlAction and algorithmApg end once the residual of
+        the last iteration of a batch of stop_check_every iterations (0: the library's default, 20) is <= stop_tolerance; 0: fixed count."""
         self.lib = load()
         self.structured = bool(structured)
         self.network, self.tree, self.config = network, tree, config
@@ -307,6 +314,8 @@ class Solver:
             self._check(self.lib.rn_set_operator_storage(self.h, STORAGES[operator_storage]))
         if sweep_pairing != "auto":
             self._check(self.lib.rn_set_sweep_pairing(self.h, PAIRINGS[sweep_pairing]))
+        if stop_tolerance or stop_check_every:      # (a context that never asks for it makes exactly the calls it always made)
+            self.setStopTolerance(stop_tolerance, stop_check_every)
         for k, v in (knobs or {}).items():
             self.debugSetKnob(k, v)
 
@@ -370,7 +379,34 @@ class Solver:
         n = self.max_iterations if maxIterations is None else int(maxIterations)
         hist = np.zeros(max(n, 1))
         self._check(self.lib.rn_algorithm_apg(self.h, n, hist.ctypes.data))
+        if getattr(self, "_stop_tol", 0.0) > 0:      # under a stop tolerance only the iterations that ran have an entry
+            n = self.last_solve()["iterations"]
         return hist[:n]
+
+    def apg_solve(self, maxIterations=None, tol=0.0, check_every=0, history=True):
+        """rn_apg_solve: apgReset, then batches of check_every iterations (0: the library's default) until the residual of a batch's last
+        iteration is <= tol (0: never) or maxIterations have run.  Returns (iterations run, vecPrimalInfs of those iterations or None)."""
+        n = self.max_iterations if maxIterations is None else int(maxIterations)
+        hist = np.zeros(max(n, 1)) if history else None
+        run = C.c_int(0)
+        self._check(self.lib.rn_apg_solve(self.h, n, float(tol), int(check_every), C.byref(run), hist.ctypes.data if history else None))
+        return run.value, (hist[: run.value] if history else None)
+
+    def setStopTolerance(self, tol, check_every=0):
+        self._check(self.lib.rn_set_stop_tolerance(self.h, float(tol), int(check_every)))
+        self._stop_tol = float(tol)
+
+    def stopTolerance(self):
+        """(tol, check_every) as set by setStopTolerance (0: off, the library's default batch length)"""
+        t, e = C.c_double(0), C.c_int(0)
+        self._check(self.lib.rn_get_stop_tolerance(self.h, C.byref(t), C.byref(e)))
+        return t.value, e.value
+
+    def last_solve(self):
+        """rn_get_last_solve: dict(iterations, stopped, first_below, batches) of the last apg_solve / algorithmApg / controlAction"""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.rn_get_last_solve(self.h, out.ctypes.data))
+        return dict(zip(("iterations", "stopped", "first_below", "batches"), (int(v) for v in out)))
 
     def controlAction(self, nominalDemand, nominalPrices, currentX=None, prevU=None, prevDemand=None, maxIterations=None,
                       project=False):

@@ -36,6 +36,14 @@ struct TreeDev {
     const T *dy;            // [N][ny] preconditioner diagonal in y order: d_x | d_xs | d_u
 };
 
+// What the launch that closes an rn_apg_iterate batch publishes for the host (which decides, behind the synchronisation it has anyway,
+// whether the solve goes on: rn_apg_solve, rn_set_stop_tolerance): 16 bytes, in IterState and -- single GPU -- in a host-mapped copy.
+struct BatchRecord {
+    int verdict;           // optimistic batch: a tree-global distance exceeded its threshold (the batch is replayed); exact batch: 0
+    int firstBelow;        // first iteration OF THIS BATCH (0-based within it) whose residual was <= the tolerance handed to the launch, or -1
+    double lastResidual;   // vecPrimalInfs of the batch's last iteration (SmpcController.cu:1521)
+};
+
 struct IterState {         // device-resident scalars of the APG loop
     int it;                // iteration counter (advanced by whichever kernel does the iteration's bookkeeping)
     unsigned int ticket;   // arrival counter of the fix-up kernel's blocks (rare path only)
@@ -44,6 +52,7 @@ struct IterState {         // device-resident scalars of the APG loop
     double scaleX, scaleS; // 1 - gamma/(lambda dist) for the two halves (0 when not tripped)
     double distX, distS;   // tree-global distances of this iteration
     int commFail;          // one-shot exchange: a reader gave up waiting for a peer's packets (sticky; the host turns it into RN_E_COMM)
+    BatchRecord rec;       // of the batch closed last (written by its closing launch)
 };
 
 // ---- one-shot exchange at the cut (opt-in transport, rn_set_exchange_transport) -----------------------

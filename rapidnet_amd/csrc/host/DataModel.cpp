@@ -1,6 +1,8 @@
 // DataModel.cpp -- JSON loaders of the host data model (see DataModel.hpp for the reference map).
 #include "DataModel.hpp"
 
+#include <cmath>
+
 namespace {
 uint_t scalarInt(const jsonlite::Document &d, const char *key) {
     const jsonlite::Value &a = d[key];
@@ -163,6 +165,20 @@ SmpcConfiguration::SmpcConfiguration(string pathToFile) {
         sweepPairing = doc["sweepPairing"].str;
         if (sweepPairing != "auto" && sweepPairing != "on" && sweepPairing != "off")
             throw std::logic_error("controller configuration: sweepPairing must be \"auto\", \"on\" or \"off\" (got \"" + sweepPairing + "\")");
+    }
+    // ... and whether the APG solve of a control step ends on a residual tolerance (absent = 0: the reference's fixed maxIterations; rapidnet.h,
+    // rn_set_stop_tolerance), checked every stopCheckEvery iterations (absent = 0: the library's default)
+    stopTolerance = 0;
+    if (doc.HasMember("stopTolerance")) {
+        stopTolerance = scalarReal(doc, "stopTolerance");
+        if (!(stopTolerance >= 0) || !std::isfinite(stopTolerance))
+            throw std::logic_error("controller configuration: stopTolerance must be finite and >= 0");
+    }
+    stopCheckEvery = 0;
+    if (doc.HasMember("stopCheckEvery")) {
+        const long every = (long)scalarReal(doc, "stopCheckEvery");
+        if (every < 0) throw std::logic_error("controller configuration: stopCheckEvery must be >= 0");
+        stopCheckEvery = (uint_t)every;
     }
     lbfgsBufferSize = scalarInt(doc, "lbfgsBufferSize");
     pathToConfiguration = pathToFile;

@@ -124,6 +124,10 @@ public:
     string getOperatorStorage() { return operatorStorage; }
     // "sweepPairing" (optional key, not in the reference's files): "auto" (default), "on" or "off" -- Engine.hpp, setSweepPairing
     string getSweepPairing() { return sweepPairing; }
+    // "stopTolerance" / "stopCheckEvery" (optional keys, not in the reference's files): absent = 0 = the fixed maxIterations of the reference /
+    // the library's default batch length -- Engine.hpp, setStopTolerance
+    real_t getStopTolerance() { return stopTolerance; }
+    uint_t getStopCheckEvery() { return stopCheckEvery; }
     void setCurrentState();     // re-read from the configuration file (SmpcConfiguration.cu:240-256)
     void setPreviousControl();  // :261-277
     void setPreviousDemand();   // :283-299
@@ -133,9 +137,9 @@ public:
     ~SmpcConfiguration() {}
 
 private:
-    uint_t NX, NU, ND, NV, lbfgsBufferSize, maxIteration;
+    uint_t NX, NU, ND, NV, lbfgsBufferSize, maxIteration, stopCheckEvery;
     std::vector<real_t> matL, matLhat, matCostW, matDiagPrecnd, currentX, prevU, prevDemand;
-    real_t penaltyStateX, penaltySafetyX, stepSize, weightPrice, weightSmooth, weightSafety;
+    real_t penaltyStateX, penaltySafetyX, stepSize, weightPrice, weightSmooth, weightSafety, stopTolerance;
     string pathToConfiguration, pathToNetwork, pathToScenarioTree, pathToForecaster, algorithmName, operatorMode, operatorStorage, sweepPairing;
 };
 

@@ -55,6 +55,12 @@ int Engine::getOperatorStorage() {
     check(rn_get_operator_storage(ctx, nullptr, &active), "rn_get_operator_storage");
     return active;
 }
+void Engine::setStopTolerance(real_t tol, int checkEvery) { check(rn_set_stop_tolerance(ctx, tol, checkEvery), "rn_set_stop_tolerance"); }
+real_t Engine::getStopTolerance(int *checkEvery) {
+    double tol = 0;
+    check(rn_get_stop_tolerance(ctx, &tol, checkEvery), "rn_get_stop_tolerance");
+    return tol;
+}
 void Engine::setSweepPairing(int mode) { check(rn_set_sweep_pairing(ctx, mode), "rn_set_sweep_pairing"); }
 int Engine::getSweepPairing(int *active) {
     int requested = RN_PAIR_AUTO;
@@ -108,6 +114,8 @@ void Engine::create(int precision, int device, int operatorMode, int rank, int n
         const string m = ptrMySmpcConfig->getSweepPairing();
         if (m != "auto") check(rn_set_sweep_pairing(ctx, m == "on" ? RN_PAIR_ON : RN_PAIR_OFF), "rn_set_sweep_pairing");
     }
+    if (ptrMySmpcConfig->getStopTolerance() > 0)   // (a file without the key makes exactly the calls it always made)
+        check(rn_set_stop_tolerance(ctx, ptrMySmpcConfig->getStopTolerance(), (int)ptrMySmpcConfig->getStopCheckEvery()), "rn_set_stop_tolerance");
     // SmpcController::allocateApgAlgorithm (SmpcController.cu:124-151): per-iteration storage for maxIterations, allocated once
     check(rn_reserve_iterations(ctx, (int)ptrMySmpcConfig->getMaxIterations()), "rn_reserve_iterations");
     if (!apgFlag)   // SmpcController::allocateGlobalFbeAlgorithm / allocateNamaAlgorithm / allocateLbfgsBuffer (SmpcController.cu:234-330)

@@ -46,6 +46,12 @@ public:
     // blocks to what _AUTO pairs.  The constructors take it from the configuration file's optional "sweepPairing" key ("auto" | "on" | "off";
     // absent: auto).  At any time.
     void setSweepPairing(int mode);
+    // the APG solve of a control step ends once the primal infeasibility of the last iteration of a batch of `checkEvery` iterations is <= tol
+    // (rapidnet.h, rn_set_stop_tolerance; the reference always runs maxIterations, SmpcController.cu:1500-1525).  tol = 0 (the default): off;
+    // checkEvery <= 0: the library's default (20).  The constructors take both from the configuration file's optional "stopTolerance" /
+    // "stopCheckEvery" keys (absent: off).  At any time; the quasi-Newton loops ignore it.
+    void setStopTolerance(real_t tol, int checkEvery = 0);
+    real_t getStopTolerance(int *checkEvery = nullptr);
     int getSweepPairing(int *active = nullptr);      // what was asked for; *active: 1 when the next NAMA line search would run the pair
     // a per-node block handed in by the caller (the reference: write through getMatPhi() / getPtrMatPhi()[node] ..., Engine.cuh:170-230);
     // RN_OP_PHI, _PSI, _D, _F, col-major nv x (2nx | nu); after factorStep()

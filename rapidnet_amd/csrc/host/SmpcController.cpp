@@ -73,6 +73,11 @@ bool SmpcController::deviceMemoryChanged(const size_t before[4]) {
     return false;
 }
 
+uint_t SmpcController::getIterationsRun() {
+    long out[4] = {0, 0, -1, 0};
+    check(rn_get_last_solve(ptrMyEngine->getContext(), out), "rn_get_last_solve");
+    return (uint_t)out[0];
+}
 uint_t SmpcController::controlAction(real_t *u) {
     if (!factorStepFlag) { ptrMyEngine->factorStep(); factorStepFlag = true; }
     size_t before[4];

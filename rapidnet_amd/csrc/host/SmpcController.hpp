@@ -35,6 +35,9 @@ public:
     real_t getSafetyKpi(uint_t simulationTime);             // :1841-1843
     void updateKpi(real_t *state, real_t *control);         // :1769-1802
     real_t *getPrimalInfeasibility() { return vecPrimalInfs.data(); }
+    // iterations the last APG solve (controlAction, algorithmApg) ran: maxIterations unless Engine::setStopTolerance / the configuration's
+    // "stopTolerance" ended it earlier (rapidnet.h, rn_get_last_solve)
+    uint_t getIterationsRun();
     real_t *getValueFbe() { return vecValueFbe.data(); }    // :1883
     real_t *getVecTau() { return vecTau.data(); }
     ~SmpcController();

@@ -38,6 +38,11 @@ struct DualArgs {
     // partials of the main pass; this launch writes its own partials to `partials`.
     int decideHere, itHost, nMain;
     const Partial *mainPartials;
+    // the decideHere launch of a batch's LAST iteration also publishes the batch record (common.hpp, BatchRecord): the batch is hist[recFirst ..
+    // recFirst + recN), recN < 0: no record (every other launch), recN == 0: a record without the scan for recTol (nobody asked for one)
+    int recFirst, recN;
+    double recTol;
+    BatchRecord *hostRec;  // host-mapped copy (nullptr: none)
 };
 
 
@@ -89,6 +94,40 @@ __device__ __forceinline__ void write_history(const Partial &p, int it, double *
     histParts[4 * (size_t)it + 0] = p.absXi; histParts[4 * (size_t)it + 1] = p.valXi;
     histParts[4 * (size_t)it + 2] = p.absPsi; histParts[4 * (size_t)it + 3] = p.valPsi;
 }
+// The batch record (common.hpp, BatchRecord) of the batch whose history entries are hist[first .. first + n), stored by ONE thread: into the
+// iteration state and, where the host mapped one, into the host's copy (system-scope stores: the host reads them behind its stream
+// synchronisation, without a device-to-host copy of its own).
+__device__ __forceinline__ void store_batch_record(int verdict, int firstBelow, double last, IterState *st, BatchRecord *host) {
+    st->rec = BatchRecord{verdict, firstBelow, last};
+    if (host != nullptr) {
+        unsigned long long *w = reinterpret_cast<unsigned long long *>(host);
+        __hip_atomic_store(w, (unsigned long long)(unsigned int)verdict | ((unsigned long long)(unsigned int)firstBelow << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(w + 1, (unsigned long long)__double_as_longlong(last), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+// ... by the whole workgroup that does the closing launch's bookkeeping (EVERY thread calls): the first iteration of the batch whose residual
+// is <= tol comes from a scan of the batch's own history entries -- the n - 1 entries earlier launches wrote are read from memory, the last
+// one (`last`, valid in thread 0, which has just written it) is taken from the register.  n == 0: no scan, firstBelow = -1.
+__device__ __forceinline__ void publish_batch_record(const double *hist, int first, int n, double tol, double last, int verdict, IterState *st, BatchRecord *host) {
+    __shared__ int r_first;
+    if (threadIdx.x == 0) r_first = 0x7fffffff;
+    __syncthreads();
+    for (int i = threadIdx.x; i < n - 1; i += ELT_THREADS)      // ascending per thread: its first hit is its smallest
+        if (hist[first + i] <= tol) { atomicMin(&r_first, i); break; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int fb = r_first;
+        if (fb == 0x7fffffff) fb = (n > 0 && last <= tol) ? n - 1 : -1;
+        store_batch_record(verdict, fb, last, st, host);
+    }
+}
+// ... and by one thread alone (the fix-up launch's last arriver, which redoes the history entry of a tripped iteration: the rare path)
+__device__ __forceinline__ void publish_batch_record_serial(const double *hist, int first, int n, double tol, double last, IterState *st, BatchRecord *host) {
+    int fb = -1;
+    for (int i = 0; i < n - 1; i++) if (hist[first + i] <= tol) { fb = i; break; }
+    if (fb < 0 && n > 0 && last <= tol) fb = n - 1;
+    store_batch_record(0, fb, last, st, host);
+}
 
 
 #ifndef RN_DUAL_U
@@ -106,7 +145,7 @@ __global__ void __launch_bounds__(ELT_THREADS) k_dual_fused(DualArgs<T> a) {
     T scX = 0, scS = 0;
     if (FIXUP && a.decideHere) {
         __shared__ double dec[3];   // tripped, scaleX, scaleS
-        double tx2 = 0, ts2 = 0;
+        double tx2 = 0, ts2 = 0, lastRes = 0;
         Partial p;
         fold_partials(a.mainPartials, a.nMain, blockIdx.x == 0, tx2, ts2, p);
         if (threadIdx.x == 0) {
@@ -120,10 +159,13 @@ __global__ void __launch_bounds__(ELT_THREADS) k_dual_fused(DualArgs<T> a) {
                 a.st->tripped = (trX || trS) ? 1 : 0;
                 a.st->scaleX = dec[1]; a.st->scaleS = dec[2];
                 write_history(p, a.itHost, a.hist, a.histParts, a.histCap);
+                lastRes = p.valXi > p.valPsi ? p.valXi : p.valPsi;
                 a.st->it = a.itHost + 1;
             }
         }
         __syncthreads();
+        // the batch's last iteration: the batch record (a tripped iteration's residual is not final yet -- its record is the last arriver's, below)
+        if (blockIdx.x == 0 && a.recN >= 0 && dec[0] == 0.0) publish_batch_record(a.hist, a.recFirst, a.recN, a.recTol, lastRes, 0, a.st, a.hostRec);
         if (dec[0] == 0.0) return;   // common case: nothing to redo
         scX = (T)dec[1]; scS = (T)dec[2];
     } else if (FIXUP) {
@@ -256,6 +298,7 @@ __global__ void __launch_bounds__(ELT_THREADS) k_dual_fused(DualArgs<T> a) {
                 }
                 Partial pr{0, 0, aX, vX, aP, vP, iX, iP};
                 write_history(pr, a.decideHere ? a.itHost : a.st->it - 1, a.hist, a.histParts, a.histCap);
+                if (a.decideHere && a.recN >= 0) publish_batch_record_serial(a.hist, a.recFirst, a.recN, a.recTol, vX > vP ? vX : vP, a.st, a.hostRec);
                 a.st->ticket = 0;
             }
         }
@@ -475,11 +518,21 @@ __device__ void finalize_optimistic_body(const FinArgs &fin, const PeerTable *pe
 }
 template <typename T>
 __global__ void __launch_bounds__(ELT_THREADS) k_finalize_optimistic(const Partial *partials, int nblocks, IterState *st, T *tail,
-                                                                     double *hist, double *histParts, int histCap, double thrX, double thrS, int *hostVerdict = nullptr) {
+                                                                     double *hist, double *histParts, int histCap, double thrX, double thrS,
+                                                                     int recFirst, int recN, double recTol, BatchRecord *hostRec) {
     finalize_optimistic_body<T>(FinArgs{partials, nblocks, st, (void *)tail, hist, histParts, histCap, thrX, thrS});
-    // single GPU: the batch's verdict goes straight into a host-mapped word (thread 0 did the bookkeeping above: program order), so the host
-    // reads it behind its stream synchronisation without a device-to-host copy of its own
-    if (hostVerdict != nullptr && threadIdx.x == 0) __hip_atomic_store(hostVerdict, st->violated, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // single GPU (recN >= 0; a sharded batch is closed by k_batch_close_unpack): the batch record -- verdict, the last iteration's residual, the
+    // first iteration under recTol -- goes into the iteration state and straight into the host-mapped copy (thread 0 did the bookkeeping above
+    // and reads its own history entry back: program order), so the host reads it behind its stream synchronisation without a copy of its own
+    if (recN < 0) return;
+    double last = 0;
+    int verdict = 0;
+    if (threadIdx.x == 0) {
+        const int it = st->it - 1;
+        if (it >= 0 && it < histCap) last = hist[it];
+        verdict = st->violated;
+    }
+    publish_batch_record(hist, recFirst, recN, recTol, last, verdict, st, hostRec);
 }
 // Sharded APG, end of a batch (SmpcController::updatePrimalInfeasibity, SmpcController.cu:1480-1496, records ONE tree-global value
 // per iteration in vecPrimalInfs, :1521): the ranks' history entries are made tree-global by one MAX all-reduce per BATCH, which
@@ -506,12 +559,30 @@ __global__ void __launch_bounds__(ELT_THREADS) k_batch_close_pack(const T *tail,
     }
 }
 template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
-__global__ void __launch_bounds__(ELT_THREADS) k_batch_close_unpack(const double *in, double *hist, int first, int n, IterState *st) {
-    if (threadIdx.x == 0 && in[1 + 4 * (size_t)n] > 0.0) st->commFail = 1;      // a reader gave up on SOME rank: the batch is invalid on every rank
+__global__ void __launch_bounds__(ELT_THREADS) k_batch_close_unpack(const double *in, double *hist, int first, int n, IterState *st, double recTol, int recScan) {
+    __shared__ int r_first;
+    if (threadIdx.x == 0) { r_first = 0x7fffffff; if (in[1 + 4 * (size_t)n] > 0.0) st->commFail = 1; }      // a reader gave up on SOME rank: the batch is invalid on every rank
+    __syncthreads();
+    bool hit = false;
     for (int i = threadIdx.x; i < n; i += ELT_THREADS) {
         const double gx = in[1 + 4 * i] >= in[2 + 4 * i] ? in[1 + 4 * i] : -in[2 + 4 * i];
         const double gp = in[3 + 4 * i] >= in[4 + 4 * i] ? in[3 + 4 * i] : -in[4 + 4 * i];
-        hist[first + i] = gx > gp ? gx : gp;
+        const double r = gx > gp ? gx : gp;
+        hist[first + i] = r;
+        if (recScan && !hit && r <= recTol) { hit = true; atomicMin(&r_first, i); }
+    }
+    __syncthreads();
+    // the batch record of a sharded batch, from the tree-global values every rank holds after the all-reduce: the same bits, hence the same
+    // decision, on every rank (the host fetches it with the one copy that used to fetch the vote)
+    if (threadIdx.x == 0) {
+        double last = 0;
+        if (n > 0) {
+            const int i = n - 1;
+            const double gx = in[1 + 4 * i] >= in[2 + 4 * i] ? in[1 + 4 * i] : -in[2 + 4 * i];
+            const double gp = in[3 + 4 * i] >= in[4 + 4 * i] ? in[3 + 4 * i] : -in[4 + 4 * i];
+            last = gx > gp ? gx : gp;
+        }
+        store_batch_record(in[0] > 0.0 ? 1 : 0, r_first == 0x7fffffff ? -1 : r_first, last, st, nullptr);
     }
 }
 

@@ -49,6 +49,7 @@
 #endif
 #ifndef RN_OPT_LOCAL_MIN
 #define RN_OPT_LOCAL_MIN 16   // shortest rn_apg_iterate batch that takes the optimistic single-GPU path
+#define RN_STOP_CHECK_EVERY 20   // rn_apg_solve / rn_set_stop_tolerance: iterations per batch when the caller names none
 #endif
 #ifndef RN_OPT_BACKOFF
 #define RN_OPT_BACKOFF 8      // exact batches after an optimistic batch had to be replayed
@@ -146,6 +147,11 @@ struct CtxBase {
     virtual int set_parameters(double, double, double) = 0;
     virtual int apg_reset() = 0;
     virtual int apg_iterate(int, double *) = 0;
+    virtual int apg_run(int, double *) = 0;
+    virtual int apg_solve(int, double, int, int *, double *) = 0;
+    virtual int set_stop_tolerance(double, int) = 0;
+    virtual int get_stop_tolerance(double *, int *) = 0;
+    virtual int last_solve(long *) = 0;
     virtual int control_action(const double *, const double *, const double *, const double *, const double *, int, int,
                                double *) = 0;
     virtual int extrapolate(double) = 0;
@@ -401,7 +407,14 @@ struct Ctx : CtxBase {
                                  // soft bounds would otherwise pay checkpoint + replay on every batch of every control step)
     std::vector<double> h_T1, h_T2, h_Lt;   // zero-padded (rows % 16, cols % 4) copies for the MFMA GEMMs
     int chainStage = 0;
-    int *h_verdict = nullptr;    // host-mapped word the last launch of a single-GPU optimistic batch writes the batch's verdict into (nullptr: not granted -- a copy is used)
+    // host-mapped copy of the batch record (common.hpp, BatchRecord) that the closing launch of a single-GPU batch writes: the verdict of an
+    // optimistic batch and what a stop tolerance needs, read behind the batch's one synchronisation (nullptr: not granted -- a copy is used)
+    BatchRecord *h_rec = nullptr;
+    BatchRecord lastRec{0, -1, 0.0};   // of the batch run last, as the host read it (valid when that batch was run under a tolerance)
+    // rn_set_stop_tolerance: what rn_control_action and rn_algorithm_apg do (stopTol == 0: one batch of maxIterations, as ever)
+    double stopTol = 0.0;
+    int stopEvery = RN_STOP_CHECK_EVERY;
+    long lastSolve[4] = {0, 0, -1, 0};   // rn_get_last_solve
     bool unscaled_on() const { return knob[RN_KNOB_UNSCALED_WALK] != 0; }   // inner iterations of optimistic batches take that pair of kernels (default on)
     // rn_debug_set_knob (include/rapidnet_debug.h): launch-shape choices the library otherwise makes by problem size, forced by tests and A/B tools
     // on trees that would not take them by themselves; -1 = the library's own choice.  Before the factor step only.
@@ -489,7 +502,7 @@ struct Ctx : CtxBase {
         for (auto &p : pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
         for (auto e : freeEvents) (void)hipEventDestroy(e);
         for (void *p : ipcOpened) (void)hipIpcCloseMemHandle(p);
-        if (h_verdict) (void)hipHostFree(h_verdict);
+        if (h_rec) (void)hipHostFree(h_rec);
         if (d_inbox) (void)hipFree(d_inbox);
         for (void *p : allocs) (void)hipFree(p);
         if (evFork) (void)hipEventDestroy(evFork);
@@ -739,7 +752,7 @@ struct Ctx : CtxBase {
         RN_HIP(hipSetDevice(device));
         RN_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cu > 0) numCUs = cu; }
-        if (hipHostMalloc((void **)&h_verdict, sizeof(int), hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); h_verdict = nullptr; } else *h_verdict = 0;
+        if (hipHostMalloc((void **)&h_rec, sizeof(BatchRecord), hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); h_rec = nullptr; } else *h_rec = BatchRecord{0, -1, 0.0};
         {   // The library's device code is six code objects (one per kernel unit) and the HIP runtime loads a code object when its first kernel is
             // looked up: asked for here, so that no later call -- a control step under the caller's leak check (SmpcController.cu:1612-1623) --
             // is the one during which the device's free memory shrinks by a code object
@@ -1703,6 +1716,7 @@ struct Ctx : CtxBase {
         a.crownElems = 0; a.countCrown = 1;
         a.finalizedEarly = 0; a.hist = d_hist; a.histParts = d_histParts; a.histCap = histCap;
         if (cutStage > 0) { a.crownElems = h_stageCum[cutStage] * ny; a.countCrown = (rank == 0); }
+        a.recN = -1;   // (only the launch that closes a batch publishes a record: run_batch)
         a.regen = RN_DUAL_REGEN; a.stageOf = d_stageOf; a.sqrtp = d_sqrtp; a.dy = d_dy; a.blo = d_blo; a.bhi = d_bhi;
         return a;
     }
@@ -1792,7 +1806,10 @@ struct Ctx : CtxBase {
     // launch (single GPU) or cut launch (sharded: every rank's dist^2 rides in the tail of the cut payload -- ONE collective per iteration).
     // If a threshold was exceeded anywhere in the batch, the batch is replayed from its checkpoint as an exact batch: the result is exact
     // either way.
-    int run_batch(int n, double *primalInfs, bool optimistic) {
+    // recTol >= 0: the batch is run under a stop tolerance -- its closing launch scans the batch's history entries for recTol, and the host
+    // reads the batch record (lastRec) behind the batch's synchronisation: the one an optimistic batch has anyway, one of its own for an exact
+    // batch.  recTol < 0: nobody asked, nothing is scanned and an exact batch does not synchronise.  A replayed batch is judged on the replay's record.
+    int run_batch(int n, double *primalInfs, bool optimistic, double recTol = -1.0) {
         Batch b{};
         b.optimistic = optimistic; b.sharded = has_comm() && cutStage > 0;
         const int first = h_it;
@@ -1824,7 +1841,8 @@ struct Ctx : CtxBase {
                 hipEvent_t e3 = prof_begin(3);
                 if (b.optimistic) {   // the batch's last bookkeeping gets a launch of its own
                     hipLaunchKernelGGL(k_finalize_optimistic<T>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, main_partials(), d_state, tail, d_hist, d_histParts,
-                                       histCap, b.sharded ? -1.0 : penX / stepSize, b.sharded ? -1.0 : penXs / stepSize, b.sharded ? nullptr : h_verdict);
+                                       histCap, b.sharded ? -1.0 : penX / stepSize, b.sharded ? -1.0 : penXs / stepSize,
+                                       first, b.sharded ? -1 : (recTol >= 0 ? n : 0), recTol, b.sharded ? nullptr : h_rec);
                 } else if (b.sharded) {   // tree-global distances: sum the ranks' dist^2 (2 doubles) before deciding
                     hipLaunchKernelGGL(k_reduce_dist<>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, eltBlocks, d_dist2);
                     if (int rc = all_reduce(d_dist2, 2, true, "ncclAllReduce(dist)")) return fail_batch(rc);
@@ -1835,6 +1853,7 @@ struct Ctx : CtxBase {
                 } else {   // single GPU: the (small) fix-up launch also decides and does the bookkeeping (kernels.hpp, decideHere)
                     a.finalizedEarly = 1;
                     a.decideHere = 1; a.itHost = h_it; a.nMain = main_partials(); a.mainPartials = d_partials; a.partials = d_partials2;
+                    if (last && recTol >= 0) { a.recFirst = first; a.recN = n; a.recTol = recTol; a.hostRec = h_rec; }   // the launch that closes the batch
                     const int fixBlocks = std::min(eltBlocks, RN_FIXUP_BLOCKS);
                     if (last) hipLaunchKernelGGL((k_dual_fused<T, true, true>), dim3(fixBlocks), dim3(ELT_THREADS), 0, stream, a);
                     else hipLaunchKernelGGL((k_dual_fused<T, false, true>), dim3(fixBlocks), dim3(ELT_THREADS), 0, stream, a);
@@ -1852,33 +1871,31 @@ struct Ctx : CtxBase {
             // batch's history entries become tree-global (vecPrimalInfs, SmpcController.cu:1521) and the ranks agree on the verdict (every
             // rank takes the same replay decision even if an all-reduce algorithm ever delivered sums that differ in the last bit between ranks)
             if (tail) { if (int rc = all_reduce(tail, 2, sizeof(T) == 8, "ncclAllReduce(dist tail)")) return fail_batch(rc); }
-            if (int rc = globalize_history(first, n, tail)) return fail_batch(rc);
+            if (int rc = globalize_history(first, n, tail, recTol)) return fail_batch(rc);
         }
         RN_HIP(hipGetLastError());
         int violated = 0;
-        if (b.optimistic && n > 0) {
-            if (b.sharded) {
-                double votes = 0;
-                RN_HIP(hipMemcpyAsync(&votes, d_histGlob, sizeof(double), hipMemcpyDeviceToHost, stream));
+        const bool synced = n > 0 && (b.optimistic || recTol >= 0);
+        if (synced) {   // the batch record: the verdict of an optimistic batch, and what a stop tolerance asks about
+            if (!b.sharded && h_rec) {   // written by the batch's last launch (k_finalize_optimistic / the fix-up launch): no copy, one synchronisation
                 RN_HIP(hipStreamSynchronize(stream));
-                violated = votes > 0 ? 1 : 0;
-            } else if (h_verdict) {   // written by the batch's last launch (k_finalize_optimistic): no copy, one synchronisation
-                RN_HIP(hipStreamSynchronize(stream));
-                violated = *(volatile int *)h_verdict;
-            } else {
-                RN_HIP(hipMemcpyAsync(&violated, &d_state->violated, sizeof(int), hipMemcpyDeviceToHost, stream));
+                const volatile BatchRecord *r = h_rec;
+                lastRec.verdict = r->verdict; lastRec.firstBelow = r->firstBelow; lastRec.lastResidual = r->lastResidual;
+            } else {   // sharded (k_batch_close_unpack: tree-global values, the same bits on every rank), or no mapped memory: one copy
+                RN_HIP(hipMemcpyAsync(&lastRec, &d_state->rec, sizeof(BatchRecord), hipMemcpyDeviceToHost, stream));
                 RN_HIP(hipStreamSynchronize(stream));
             }
+            violated = b.optimistic ? lastRec.verdict : 0;
         }
         if (b.sharded && n > 0 && transport == 1 && peerReady) { if (int rc = check_comm_fail()) return fail_batch(rc); }
         if (violated) {   // the same n iterations once more from the checkpoint, as an exact batch; so are the next RN_OPT_BACKOFF batches
             fallbacks++;
             if (int rc = restore_iterates(saved)) return fail_batch(rc);
             optHold = RN_OPT_BACKOFF;
-            return run_batch(n, primalInfs, false);
+            return run_batch(n, primalInfs, false, recTol);
         }
         if (primalInfs && n > 0) {
-            if (!b.optimistic) RN_HIP(hipStreamSynchronize(stream));   // (an optimistic batch has synchronised for its verdict)
+            if (!synced) RN_HIP(hipStreamSynchronize(stream));   // (an optimistic batch has synchronised for its verdict, a batch under a tolerance for its record)
             RN_HIP(hipMemcpy(primalInfs, d_hist + first, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
         }
         return RN_OK;
@@ -2153,7 +2170,8 @@ struct Ctx : CtxBase {
         optimistic = mode; optHold = 0;
         return RN_OK;
     }
-    int apg_iterate(int n, double *primalInfs) override {
+    int apg_iterate(int n, double *primalInfs) override { return apg_iterate(n, primalInfs, -1.0); }
+    int apg_iterate(int n, double *primalInfs, double recTol) {
         RN_CHECK(factored && affine_ready, RN_E_STATE, "rn_apg_iterate before the factor step / affine terms");
         RN_CHECK(n >= 0, RN_E_ARG, "rn_apg_iterate: negative iteration count");
         RN_CHECK(!poisoned, RN_E_STATE, "rn_apg_iterate: an earlier batch failed half-way; call rn_apg_reset first");
@@ -2170,18 +2188,74 @@ struct Ctx : CtxBase {
         if (opt && optHold > 0) { optHold--; opt = false; }
         if (opt) optBatches++;
         else if (n > 0) exactBatches++;
-        return run_batch(n, primalInfs, opt);
+        return run_batch(n, primalInfs, opt, recTol);
+    }
+    // The loop of rn_apg_solve (the reset, or the warm restart, is the caller's): batches of `every` iterations through apg_iterate -- so the
+    // iterates are those of the same sequence of rn_apg_iterate calls, bit for bit -- until the residual of a batch's LAST iteration is <= tol
+    // or maxIt iterations have run (SmpcController::algorithmApg runs maxIterations whatever the residual, SmpcController.cu:1500-1525).  The
+    // decision is the host's and is taken where the host synchronises anyway: behind the launch that closes the batch, which has published the
+    // batch record (common.hpp, BatchRecord).  Sharded: the record is built from the all-reduced history, the same bits on every rank, so all
+    // ranks stop together.  tol == 0 never stops early.
+    int solve_loop(int maxIt, double tol, int every, double *primalInfs) {
+        lastSolve[0] = 0; lastSolve[1] = 0; lastSolve[2] = -1; lastSolve[3] = 0;
+        for (int done = 0; done < maxIt;) {
+            const int n = std::min(every, maxIt - done);
+            if (int rc = apg_iterate(n, primalInfs ? primalInfs + done : nullptr, tol)) return rc;
+            if (lastSolve[2] < 0 && lastRec.firstBelow >= 0) lastSolve[2] = done + lastRec.firstBelow;
+            done += n;
+            lastSolve[0] = done; lastSolve[3]++;
+            if (tol > 0 && lastRec.lastResidual <= tol) { lastSolve[1] = 1; break; }
+        }
+        return RN_OK;
+    }
+    // what rn_algorithm_apg and rn_control_action run after their reset: one batch of maxIt iterations -- today's path, untouched -- unless
+    // rn_set_stop_tolerance named a tolerance
+    int apg_run(int maxIt, double *primalInfs) override {
+        if (stopTol > 0) {
+            RN_CHECK(factored && affine_ready, RN_E_STATE, "rn_apg_iterate before the factor step / affine terms");
+            RN_CHECK(maxIt >= 0, RN_E_ARG, "rn_apg_iterate: negative iteration count");
+            return solve_loop(maxIt, stopTol, stopEvery, primalInfs);
+        }
+        if (int rc = apg_iterate(maxIt, primalInfs)) return rc;
+        lastSolve[0] = maxIt; lastSolve[1] = 0; lastSolve[2] = -1; lastSolve[3] = maxIt > 0 ? 1 : 0;
+        return RN_OK;
+    }
+    int apg_solve(int maxIt, double tol, int every, int *iterationsRun, double *primalInfs) override {
+        RN_CHECK(iterationsRun, RN_E_ARG, "rn_apg_solve: null iterationsRun");
+        RN_CHECK(maxIt >= 0, RN_E_ARG, "rn_apg_solve: negative iteration count");
+        RN_CHECK(std::isfinite(tol) && tol >= 0, RN_E_ARG, "rn_apg_solve: the tolerance must be finite and >= 0");
+        RN_CHECK(factored && affine_ready, RN_E_STATE, "rn_apg_solve before the factor step / affine terms");
+        *iterationsRun = 0;
+        if (int rc = apg_reset()) return rc;
+        const int rc = solve_loop(maxIt, tol, every > 0 ? every : RN_STOP_CHECK_EVERY, primalInfs);
+        *iterationsRun = (int)lastSolve[0];
+        return rc;
+    }
+    int set_stop_tolerance(double tol, int every) override {
+        RN_CHECK(std::isfinite(tol) && tol >= 0, RN_E_ARG, "rn_set_stop_tolerance: the tolerance must be finite and >= 0");
+        stopTol = tol; stopEvery = every > 0 ? every : RN_STOP_CHECK_EVERY;
+        return RN_OK;
+    }
+    int get_stop_tolerance(double *tol, int *every) override {
+        if (tol) *tol = stopTol;
+        if (every) *every = stopEvery;
+        return RN_OK;
+    }
+    int last_solve(long *out) override {
+        RN_CHECK(out, RN_E_ARG, "rn_get_last_solve: null output");
+        for (int i = 0; i < 4; i++) out[i] = lastSolve[i];
+        return RN_OK;
     }
     // Sharded contexts, once per batch: vecPrimalInfs[first .. first + n) of this rank (arg-max over its own nodes) -> the
     // tree-global values, on every rank (SmpcController.cu:1480-1496, :1521); element 0 of the payload carries the ranks'
     // verdict on the optimistic batch (tail = the all-reduced dist^2 of its last iteration; nullptr: no verdict).
-    int globalize_history(int first, int n, T *tail) {
+    int globalize_history(int first, int n, T *tail, double recTol) {
         hipLaunchKernelGGL(k_batch_close_pack<T>, dim3(1), dim3(ELT_THREADS), 0, stream, (const T *)tail, d_state, penX / stepSize, penXs / stepSize,
                            (const double *)d_histParts, first, n, d_histGlob);
         // (the last element: one-shot exchange, "a reader of this rank gave up waiting" -- the MAX makes it every rank's verdict, so all
         //  ranks return RN_E_COMM for the batch together instead of the late one alone)
         if (int rc = all_reduce(d_histGlob, (size_t)4 * n + 2, true, "ncclAllReduce(verdict + primal infeasibilities)", 2 /* ncclMax */)) return rc;
-        hipLaunchKernelGGL(k_batch_close_unpack<>, dim3(1), dim3(ELT_THREADS), 0, stream, (const double *)d_histGlob, d_hist, first, n, d_state);
+        hipLaunchKernelGGL(k_batch_close_unpack<>, dim3(1), dim3(ELT_THREADS), 0, stream, (const double *)d_histGlob, d_hist, first, n, d_state, recTol, recTol >= 0 ? 1 : 0);
         if (int rc = comm_check()) return rc;
         RN_HIP(hipGetLastError());
         return RN_OK;
@@ -2241,7 +2315,7 @@ struct Ctx : CtxBase {
         if (int rc = eliminate(dhat, ahat)) return rc;
         if (warmStart && h_it > 0 && !poisoned) { if (int rc = apg_restart_keep_duals()) return rc; }   // y, y+ kept; theta = {1,1}
         else if (int rc = apg_reset()) return rc;
-        if (int rc = apg_iterate(maxIt, nullptr)) return rc;
+        if (int rc = apg_run(maxIt, nullptr)) return rc;
         T *src = d_u;
         if (project) {  // SmpcController.cu:1647-1650: clamp with the (scaled) bounds of the root node
             RN_HIP(hipMemcpyAsync(d_tmp, d_u, d.nu * sizeof(T), hipMemcpyDeviceToDevice, stream));
@@ -2939,7 +3013,11 @@ int rn_eliminate_input_disturbance_coupling(rn_ctx *ctx, const double *dh, const
 int rn_set_parameters(rn_ctx *ctx, double s, double px, double pxs) { RN_GUARD(ctx); return ctx->impl->set_parameters(s, px, pxs); }
 int rn_apg_reset(rn_ctx *ctx) { RN_GUARD(ctx); return ctx->impl->apg_reset(); }
 int rn_apg_iterate(rn_ctx *ctx, int n, double *h) { RN_GUARD(ctx); return ctx->impl->apg_iterate(n, h); }
-int rn_algorithm_apg(rn_ctx *ctx, int n, double *h) { RN_GUARD(ctx); if (int rc = ctx->impl->apg_reset()) return rc; return ctx->impl->apg_iterate(n, h); }
+int rn_algorithm_apg(rn_ctx *ctx, int n, double *h) { RN_GUARD(ctx); if (int rc = ctx->impl->apg_reset()) return rc; return ctx->impl->apg_run(n, h); }
+int rn_apg_solve(rn_ctx *ctx, int maxIt, double tol, int every, int *run, double *h) { RN_GUARD(ctx); return ctx->impl->apg_solve(maxIt, tol, every, run, h); }
+int rn_set_stop_tolerance(rn_ctx *ctx, double tol, int every) { RN_GUARD(ctx); return ctx->impl->set_stop_tolerance(tol, every); }
+int rn_get_stop_tolerance(rn_ctx *ctx, double *tol, int *every) { RN_GUARD(ctx); return ctx->impl->get_stop_tolerance(tol, every); }
+int rn_get_last_solve(rn_ctx *ctx, long out[4]) { RN_GUARD(ctx); return ctx->impl->last_solve(out); }
 int rn_control_action(rn_ctx *ctx, const double *x, const double *u, const double *dm, const double *dh, const double *ah, int maxIt,
                       int project, double *u0) { RN_GUARD(ctx); return ctx->impl->control_action(x, u, dm, dh, ah, maxIt, project, u0); }
 int rn_dual_extrapolation_step(rn_ctx *ctx, double l) { RN_GUARD(ctx); return ctx->impl->extrapolate(l); }
