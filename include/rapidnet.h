@@ -165,6 +165,41 @@ int rn_get_sweep_pairing(rn_ctx *ctx, int *requested, int *active);
 int rn_factor_step(rn_ctx *ctx, const rn_system *sys);
 /* tree errors uploaded once (the reference re-uploads them every control step, Engine.cu:1205,1228) */
 int rn_set_tree_errors(rn_ctx *ctx, const double *errorDemandNode /* nodes*nd */, const double *errorPriceNode /* nodes*nu */);
+/* Scenario probabilities and tree errors replaced in place, for a forecaster that re-weights a tree of FIXED topology between two control
+ * steps (ScenarioTree.cuh:92-154 getProbArray / getErrorDemandArray / getErrorPriceArray; the reference uploads devTreeProb once,
+ * Engine.cu:263-286, and the errors with every control step, Engine.cu:1205,1228; calculateZeta, Engine.cu:1251, is what reads them).
+ * Layouts as in rn_tree and rn_set_tree_errors: probNode [nodes], errorDemandNode [nodes][nd], errorPriceNode [nodes][nu].  Any pointer may be
+ * NULL: on a set that array keeps its bits, on a get it is skipped; all three NULL: RN_E_ARG.
+ * nodes: the context's node count; on a context made by rn_create_sharded with nranks > 1 a SET takes the FULL tree's count (rn_shard_info
+ *   info[6]) and the full-tree arrays -- every rank makes the same call, as rn_create_sharded takes the full tree, and the context picks its rows
+ *   by its global-node map -- while a GET takes the local count and returns local rows in the order of rn_shard_global_nodes.  Any other count:
+ *   RN_E_ARG.
+ * Values: probNode entries must be positive and finite (rn_create's rule).  The host form checks first and returns RN_E_ARG with nothing
+ *   changed.  The device form cannot without a synchronisation: its kernel counts the offending entries on the device and the library reads the
+ *   count behind the synchronisation of the rn_eliminate_input_disturbance_coupling that has to follow (rn_control_action included): that call
+ *   returns RN_E_ARG, its message names rn_set_tree_data_device and the count, and the context refuses to iterate (RN_E_STATE) until a valid
+ *   set and an elimination have been made.  The errors are not validated (rn_set_tree_errors does not either).
+ * State: before rn_factor_step the arrays are replaced and the factor step uses them.  On a factored context a call that gives probNode
+ *   re-runs, on the context's stream, what of the factor step depends on p -- p, sqrt(p), the scaled bounds and, where the context holds dense
+ *   blocks, their expansion (Engine.cu:721-745) in the storage type in force; no host factorisation, no upload of a shared matrix -- and the
+ *   context stays factored.  As after rn_factor_step, blocks handed in by the caller are recomputed from the factor step's formulas; an
+ *   RN_OPS_AUTO context that was never handed a block stays structured.  With probNode given the affine terms and every control-step constant
+ *   derived from them are invalid: iterating before the next rn_eliminate_input_disturbance_coupling is RN_E_STATE (rn_control_action
+ *   recomputes them itself).  Errors alone behave as rn_set_tree_errors: they take effect at the next elimination.  Duals, warm start,
+ *   algorithm, L-BFGS memory, stop tolerance, operator mode, operator storage and sweep pairing are untouched.
+ * Sharded: a context made by rn_create_sharded recomputes the children moments of its cut parents (rn_set_cut_children_moments) whenever
+ *   probNode or errorDemandNode is given, over ALL children in ascending order, from the arrays of the call and -- for the one that is
+ *   missing -- the full-tree values of the cut stage it retains.  A context sharded by hand (rn_create on a local tree, rn_set_cut_stage) takes
+ *   local rows and its moments become unset: rn_set_cut_children_moments has to follow before the affine terms.
+ * rn_set_tree_data / rn_get_tree_data: host arrays of doubles; they synchronise, as rn_set does, and their staging is allocated and freed inside
+ *   the call (rn_device_memory_info info[2] is the same before and after).
+ * rn_set_tree_data_device: arrays in device memory, elements of type `precision` (RN_F32 / RN_F64 whatever the context's own type; any other
+ *   value: RN_E_ARG); launches on the context's stream only -- no allocation, no host synchronisation; the caller orders its producer against
+ *   rn_stream as rn_device_pointer describes.  Every non-NULL pointer is checked as rn_set_operators_device checks its arrays (device of the
+ *   context, alignment, length where the runtime knows it) before anything is launched: otherwise RN_E_ARG. */
+int rn_set_tree_data(rn_ctx *ctx, size_t nodes, const double *probNode, const double *errorDemandNode, const double *errorPriceNode);
+int rn_set_tree_data_device(rn_ctx *ctx, size_t nodes, int precision, const void *probNode, const void *errorDemandNode, const void *errorPriceNode);
+int rn_get_tree_data(rn_ctx *ctx, size_t nodes, double *probNode, double *errorDemandNode, double *errorPriceNode);
 /* Engine::setDemandUncertaintyFlag / setPriceUncertaintyFlag / SmpcConfiguration::getWeightEconomical */
 int rn_set_uncertainty(rn_ctx *ctx, int demandUncertainty, int priceUncertainty, double weightEconomical);
 /* Engine::updateStateControl (Engine.cu:1300-1316) */
@@ -288,7 +323,7 @@ int rn_get_operator(rn_ctx *ctx, int op_id, int node, double *host, size_t n);
 /* ... and its counterpart: a block handed in by the caller (the reference's Engine returns the device pointers of these arrays,
  * Engine.cuh:170-230 getMatPhi() ... getPtrMatF(), so its callers may overwrite any block).  RN_OP_PHI, _PSI, _D, _F of one node -- the
  * blocks solveStep multiplies with (SmpcController.cu:617-638); the next sweep uses them.  After rn_factor_step; a later rn_factor_step
- * recomputes every block.  RN_OPS_AUTO contexts switch to dense storage on the first call; RN_OPS_STRUCTURED contexts (no per-node
+ * recomputes every block, and so does a later rn_set_tree_data / rn_set_tree_data_device that gives probNode.  RN_OPS_AUTO contexts switch to dense storage on the first call; RN_OPS_STRUCTURED contexts (no per-node
  * blocks by request): RN_E_STATE.  Omega_i, Theta_i, G_i are shared matrices scaled by p_i here (K identical copies in the reference,
  * Engine.cu:306-308): RN_E_ARG.  A context with RN_STORE_F32 blocks rounds the caller's values to the nearest fp32 on upload. */
 int rn_set_operator(rn_ctx *ctx, int op_id, int node, const double *host, size_t n);

@@ -160,6 +160,7 @@ TEST_OPERATOR_STORAGE = os.path.join(BIN_DIR, "test_operator_storage")
 TEST_SWEEP_PAIRING = os.path.join(BIN_DIR, "test_sweep_pairing")
 TEST_OPERATOR_BULK = os.path.join(BIN_DIR, "test_operator_bulk")
 TEST_STOP_TOLERANCE = os.path.join(BIN_DIR, "test_stop_tolerance")
+TEST_TREE_DATA = os.path.join(BIN_DIR, "test_tree_data")
 
 
 def build_host(force=False):
@@ -199,6 +200,11 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_STOP_TOLERANCE, test_src, "-L" + HERE, "-lrapidnet_host",
                                "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
         _stamp(TEST_STOP_TOLERANCE, [test_src] + deps + hdr)
+    test_src = os.path.join(ROOT, "tests", "cpp", "test_tree_data.cpp")
+    if force or _stale(TEST_TREE_DATA, [test_src] + deps + hdr):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_TREE_DATA, test_src, "-L" + HERE, "-lrapidnet_host",
+                               "-lrapidnet_hip", "-ldl", "-Wl,-rpath,$ORIGIN/.."])
+        _stamp(TEST_TREE_DATA, [test_src] + deps + hdr)
     return LIB_HOST
 
 

@@ -46,6 +46,7 @@ SYMBOLS = [
     "rn_get_range", "rn_set_range", "rn_get_kernel_info", "rn_default_cut_stage", "rn_partition_create", "rn_partition_destroy", "rn_create_sharded", "rn_shard_info", "rn_shard_global_nodes",
     "rn_debug_set_allreduce", "rn_debug_local_group_create", "rn_debug_local_group_join", "rn_debug_local_group_destroy",
     "rn_guard_check", "rn_device_memory_info", "rn_reserve_iterations", "rn_profile_read_collective", "rn_debug_inject_allocation", "rn_guard_report", "rn_debug_guard_poke",
+    "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_debug_cut_moments",
     "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info",
 ]
 
@@ -234,6 +235,10 @@ def load():
     lib.rn_debug_set_knob.argtypes = [vp, ip, ip]
     lib.rn_debug_stream_info.argtypes = [vp, dp]
     lib.rn_profile_read_collective.argtypes = [vp, dp, dp]
+    lib.rn_set_tree_data.argtypes = [vp, C.c_size_t, dp, dp, dp]
+    lib.rn_set_tree_data_device.argtypes = [vp, C.c_size_t, ip, vp, vp, vp]
+    lib.rn_get_tree_data.argtypes = [vp, C.c_size_t, dp, dp, dp]
+    lib.rn_debug_cut_moments.argtypes = [vp, dp, dp, C.c_size_t]
     _LIB = lib
     return lib
 
@@ -611,6 +616,53 @@ class Solver:
         r, a = C.c_int(0), C.c_int(0)
         self._check(self.lib.rn_get_sweep_pairing(self.h, C.byref(r), C.byref(a)))
         return {v: k for k, v in PAIRINGS.items()}[r.value], a.value
+
+    # ---- scenario probabilities and tree errors in place (rn_set_tree_data ...) ------------------------------------
+    def _treeNodes(self):
+        """the node count a SET takes: the full tree's on a shard made by rn_create_sharded"""
+        return self.full_nodes if self.nranks > 1 else self.nodes
+
+    def setTreeData(self, prob=None, errorDemand=None, errorPrice=None):
+        """rn_set_tree_data: new probNode [nodes], errorDemandNode [nodes][nd], errorPriceNode [nodes][nu] (None: that array stays as it is); on a
+        shard (nranks > 1) the FULL tree's arrays.  With prob given the affine terms must be recomputed before the next iteration."""
+        n = self._treeNodes()
+        arrs = [None if v is None else _f64(v) for v in (prob, errorDemand, errorPrice)]
+        for a, nm, dim in zip(arrs, ("prob", "errorDemand", "errorPrice"), (1, self.nd, self.nu)):
+            if a is not None and a.size != n * dim:
+                raise ValueError("setTreeData: %s needs %d x %d values, got %d" % (nm, n, dim, a.size))
+        self._check(self.lib.rn_set_tree_data(self.h, n, *[None if a is None else a.ctypes.data for a in arrs]))
+
+    def setTreeDataDevice(self, precision, prob=0, errorDemand=0, errorPrice=0, nodes=None):
+        """rn_set_tree_data_device: integer device addresses (0: not given) of arrays of `precision` ("f64" | "f32" or an RN_F* value) elements;
+        launches on the context's stream, nothing is waited for"""
+        prec = {"f64": RN_F64, "f32": RN_F32}.get(precision, precision)
+        self._check(self.lib.rn_set_tree_data_device(self.h, self._treeNodes() if nodes is None else int(nodes), int(prec),
+                                                     *[int(p) or None for p in (prob, errorDemand, errorPrice)]))
+
+    def getTreeData(self):
+        """rn_get_tree_data: dict(prob [nodes], errorDemand [nodes][nd], errorPrice [nodes][nu]) as the context holds them (local rows on a shard)"""
+        out = {"prob": np.zeros(self.nodes), "errorDemand": np.zeros((self.nodes, self.nd)), "errorPrice": np.zeros((self.nodes, self.nu))}
+        self._check(self.lib.rn_get_tree_data(self.h, self.nodes, out["prob"].ctypes.data, out["errorDemand"].ctypes.data, out["errorPrice"].ctypes.data))
+        return out
+
+    def updateTree(self, tree):
+        """a re-weighted scenario tree of the SAME topology (on a shard: the full tree): replaces self.tree and hands its probabilities and errors
+        to the context (setTreeData with all three arrays)"""
+        for k in ("N", "K", "nodes", "nNonLeafNodes"):
+            if int(_s(tree, k)) != int(_s(self.tree, k)):
+                raise ValueError("updateTree: %s differs from the context's tree" % k)
+        for k in ("stages", "ancestor", "nChildren", "nodesPerStage"):
+            if not np.array_equal(_i32(tree[k]), _i32(self.tree[k])):
+                raise ValueError("updateTree: the topology (%s) differs from the context's tree" % k)
+        self.tree = tree
+        self.setTreeData(tree["probNode"], tree["errorDemandNode"], tree["errorPriceNode"])
+
+    def debugCutMoments(self):
+        """rn_debug_cut_moments: (E [parents][nd], P [parents]) as the context holds them"""
+        n = self.shardInfo()["cut_parents"]
+        E, P = np.zeros((n, self.nd)), np.zeros(n)
+        self._check(self.lib.rn_debug_cut_moments(self.h, E.ctypes.data, P.ctypes.data, n))
+        return E, P
 
     def synchronize(self):
         self._check(self.lib.rn_synchronize(self.h))

@@ -78,6 +78,27 @@ ScenarioTree::ScenarioTree(string pathToFileName) {
     _ASSERT((uint_t)nChildCumulArray.size() == nNodes && (uint_t)nChildArray.size() == nNonleafNodes);
     _ASSERT((uint_t)leaveArray.size() == nScenario);
 }
+namespace {
+void replaceArray(std::vector<real_t> &dst, const real_t *src, size_t n, const char *what) {
+    if (!src || n != dst.size())
+        throw std::invalid_argument(string("ScenarioTree::") + what + ": " + std::to_string(dst.size()) + " values expected, got " + std::to_string(n));
+    dst.assign(src, src + n);
+}
+}  // namespace
+void ScenarioTree::setProbArray(const real_t *prob, size_t n) { replaceArray(probNodeArray, prob, n, "setProbArray"); }
+void ScenarioTree::setErrorDemandArray(const real_t *errorDemand, size_t n) { replaceArray(errorDemandArray, errorDemand, n, "setErrorDemandArray"); }
+void ScenarioTree::setErrorPriceArray(const real_t *errorPrice, size_t n) { replaceArray(errorPriceArray, errorPrice, n, "setErrorPriceArray"); }
+void ScenarioTree::reload(string pathToFileName) {
+    ScenarioTree other(pathToFileName);
+    if (other.nPredHorizon != nPredHorizon || other.nScenario != nScenario || other.nNodes != nNodes || other.nNonleafNodes != nNonleafNodes ||
+        other.dimDemand != dimDemand || other.dimPrice != dimPrice)
+        throw std::invalid_argument("ScenarioTree::reload: " + pathToFileName + " has other dimensions than the loaded tree");
+    if (other.stageArray != stageArray || other.ancestorArray != ancestorArray || other.nChildArray != nChildArray || other.nodesPerStage != nodesPerStage)
+        throw std::invalid_argument("ScenarioTree::reload: " + pathToFileName + " has another topology than the loaded tree");
+    probNodeArray.swap(other.probNodeArray);
+    errorDemandArray.swap(other.errorDemandArray);
+    errorPriceArray.swap(other.errorPriceArray);
+}
 uint_t ScenarioTree::getFinalBranchNode() {
     for (uint_t i = 0; i < nPredHorizon - 1; i++)
         if (nodesPerStage[i] == nodesPerStage[i + 1]) return nodesPerStageCumul[i + 1];

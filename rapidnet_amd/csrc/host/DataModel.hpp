@@ -64,6 +64,15 @@ public:
     real_t *getErrorPriceArray() { return errorPriceArray.data(); }
     uint_t getDimDemand() { return dimDemand; }
     uint_t getDimPrice() { return dimPrice; }
+    // A re-weighted tree of the same topology (the reference loads its tree once, ScenarioTree.cu:32-128): new values for probNode [nodes],
+    // errorDemandNode [nodes][dimDemand], errorPriceNode [nodes][dimPrice]; `n` must be the array's size (std::invalid_argument otherwise).
+    // Engine::updateScenarioTree() hands the current arrays to the device.
+    void setProbArray(const real_t *prob, size_t n);
+    void setErrorDemandArray(const real_t *errorDemand, size_t n);
+    void setErrorPriceArray(const real_t *errorPrice, size_t n);
+    // re-reads a scenarioTree.json of the SAME topology: any difference in N, K, the node counts, the dimensions, `stages`, `ancestor`,
+    // `nChildren` or `nodesPerStage` throws std::invalid_argument and nothing changes
+    void reload(string pathToFileName);
     ~ScenarioTree() {}
 
 private:

@@ -80,6 +80,19 @@ void Engine::getOperatorsDevice(int precision, void *phi, void *psi, void *D, vo
     check(rn_get_operators_device(ctx, getNumLocalNodes(), precision, phi, psi, D, F), "rn_get_operators_device");
 }
 
+void Engine::setTreeData(const real_t *prob, const real_t *errorDemand, const real_t *errorPrice) {
+    check(rn_set_tree_data(ctx, ptrMyScenarioTree->getNumNodes(), prob, errorDemand, errorPrice), "rn_set_tree_data");
+}
+void Engine::setTreeDataDevice(int precision, const void *prob, const void *errorDemand, const void *errorPrice) {
+    check(rn_set_tree_data_device(ctx, ptrMyScenarioTree->getNumNodes(), precision, prob, errorDemand, errorPrice), "rn_set_tree_data_device");
+}
+void Engine::getTreeData(real_t *prob, real_t *errorDemand, real_t *errorPrice) {
+    check(rn_get_tree_data(ctx, getNumLocalNodes(), prob, errorDemand, errorPrice), "rn_get_tree_data");
+}
+void Engine::updateScenarioTree() {
+    setTreeData(ptrMyScenarioTree->getProbArray(), ptrMyScenarioTree->getErrorDemandArray(), ptrMyScenarioTree->getErrorPriceArray());
+}
+
 void Engine::create(int precision, int device, int operatorMode, int rank, int nranks, const void *id128, int cutStage) {
     myRank = rank; numRanks = nranks;
     priceUncertaintyFlag = true; demandUncertaintyFlag = true;

@@ -65,6 +65,17 @@ public:
     // (rn_stream(getContext())), nothing is waited for
     void setOperatorsDevice(int precision, const void *phi, const void *psi, const void *D, const void *F);
     void getOperatorsDevice(int precision, void *phi, void *psi, void *D, void *F);
+    // Scenario probabilities and tree errors replaced in place between two control steps (rapidnet.h, rn_set_tree_data; the reference uploads
+    // devTreeProb once, Engine.cu:263-286, and the errors with every control step, Engine.cu:1205,1228): probNode [nodes], errorDemandNode
+    // [nodes][nd], errorPriceNode [nodes][nu] of the FULL tree (a sharded engine picks its rows, as its constructor does); a null pointer
+    // leaves that array as it is.  With prob given the next eliminateInputDistubanceCoupling (controlAction makes one) has to precede any iteration.
+    void setTreeData(const real_t *prob, const real_t *errorDemand, const real_t *errorPrice);
+    // ... device arrays of RN_F32 / RN_F64 elements: launches on the engine's stream (rn_stream(getContext())), nothing is waited for
+    void setTreeDataDevice(int precision, const void *prob, const void *errorDemand, const void *errorPrice);
+    // what the engine holds (getNumLocalNodes() rows, in the order of getGlobalNodes()); a null pointer skips that array
+    void getTreeData(real_t *prob, real_t *errorDemand, real_t *errorPrice);
+    // pushes the ScenarioTree's current arrays (ScenarioTree::setProbArray ... / reload)
+    void updateScenarioTree();
     int getRank() { return myRank; }
     int getNumRanks() { return numRanks; }
     uint_t getNumLocalNodes();                       // nodes this rank holds (= the tree's node count on one GPU)

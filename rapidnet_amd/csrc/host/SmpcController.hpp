@@ -24,6 +24,13 @@ public:
     SmpcConfiguration *getSmpcConfiguration() { return ptrMySmpcConfig; }
     Forecaster *getForecaster() { return ptrMyForecaster; }
     Engine *getEngine() { return ptrMyEngine; }
+    // a re-weighted scenario tree between two controlAction calls: re-reads a scenarioTree.json of the SAME topology (ScenarioTree::reload; any
+    // other throws std::invalid_argument and changes nothing) and hands its probabilities and errors to the device (Engine::updateScenarioTree,
+    // rapidnet.h rn_set_tree_data) -- no new context, no factor step; the next controlAction recomputes the affine terms as it always does
+    void updateScenarioTree(const std::string &pathToScenarioTreeJson) {
+        ptrMyEngine->getScenarioTree()->reload(pathToScenarioTreeJson);
+        ptrMyEngine->updateScenarioTree();
+    }
     void moveForewardInTime();                              // :1679-1716
     // in-built simulator of moveForewardInTime: false (default) = the reference as written, x+ = x + B u (its disturbance
     // term lands in the x of node 0 instead of the state update, :1695); true = x+ = x + e_0 + B u (DwnNetwork.cuh:41-57)

@@ -9,19 +9,20 @@ namespace rn {
 // HBM ceiling probes for bench.py (rn_measure_hbm): what kernels that do nothing but stream reach on THIS box -- the practical
 // denominator next to the 8 TB/s spec.  16 B per lane per load, non-temporal, flat: the whole grid sweeps one region, thread-interleaved.
 // (The probes in the solver's access shapes -- chunk per workgroup, lockstep pieces -- live in tools/probes/probe_stream.hip.)
+// One kernel, two loops: dst == nullptr is the read-only probe, otherwise the copy (the branch is outside the loops and uniform over the grid).
 template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
-__global__ void __launch_bounds__(256) k_bw_read(const nat_d2 *src, long long n, double *sink) {
+__global__ void __launch_bounds__(256) k_bw_probe(const nat_d2 *src, nat_d2 *dst, long long n, double *sink) {
+    if (dst) {
+        for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+            __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);   // non-temporal both ways: the fastest copy variant of probe_stream.hip
+        return;
+    }
     double acc = 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const nat_d2 v = __builtin_nontemporal_load(src + i);
         acc += v[0] + v[1];
     }
     if (acc == 1.2345e-300) sink[blockIdx.x & 65535] = acc;   // keeps the loads alive without a store stream
-}
-template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
-__global__ void __launch_bounds__(256) k_bw_copy(const nat_d2 *src, nat_d2 *dst, long long n) {
-    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-        __builtin_nontemporal_store(__builtin_nontemporal_load(src + i), dst + i);   // non-temporal both ways: the fastest copy variant of probe_stream.hip
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -84,7 +85,7 @@ __global__ void k_expand_operators(ExpandArgs<T, S> a) {
 // neither the padding rows nor the tail of strideA change.  The other direction reads slots and scatters entry by entry.
 // Consecutive lanes own consecutive slots of a node's block (columns are adjacent), so the block side is one flat 16-B-per-lane stream and
 // the caller's side is contiguous per array; it is read 16 B wide where a slot's entries lie in one array at a 16-byte boundary, entry by
-// entry otherwise (still coalesced).  Non-temporal both ways, as k_bw_copy.  Launch: blockIdx.x strides the slots of one node, blockIdx.y
+// entry otherwise (still coalesced).  Non-temporal both ways, as the copy loop of k_bw_probe.  Launch: blockIdx.x strides the slots of one node, blockIdx.y
 // the nodes -- numCUs * 4 workgroups in all, the shape rn_measure_hbm found best for a read + write stream.
 // The element types arrive as flags and not as template parameters: the four (caller, stored) pairs in two directions would be eight
 // kernels; the branch is uniform over the grid.
@@ -167,6 +168,89 @@ template <bool TO_BLOCKS>
 __global__ void __launch_bounds__(PACK_THREADS) k_pack_operators(PackOpsArgs a) {
     if (a.callerF64) { if (a.storedF64) pack_operators_body<double, double, TO_BLOCKS>(a); else pack_operators_body<double, float, TO_BLOCKS>(a); }
     else { if (a.storedF64) pack_operators_body<float, double, TO_BLOCKS>(a); else pack_operators_body<float, float, TO_BLOCKS>(a); }
+}
+
+// ------------------------------------------------------------------------------------------------------
+// Scenario probabilities and tree errors replaced in place (rn_set_tree_data / rn_set_tree_data_device; ScenarioTree.cuh:92-154, devTreeProb
+// Engine.cu:263-286, the errors of Engine.cu:1205,1228).  The caller's arrays hold elements of type Src (float or double: the host form stages
+// doubles) and, on a context made by rn_create_sharded, the rows of the FULL tree: a local node reads row gmap[node].  Written in the context's
+// type: prob, sqrt(prob) -- the square root taken in double, correctly rounded, then rounded to T: the bits rn_create uploads --, errD, errP;
+// a pointer that is null leaves its array alone.  Probabilities that are not positive and finite are counted, one plain store per workgroup
+// into bad[blockIdx.x] (the host adds the words behind a synchronisation it makes anyway); the words are only written when prob is given.
+// On a multi-rank shard the children moments of the cut parents (rn_set_cut_children_moments) follow from the same arrays: one thread per
+// (parent, component), children in ascending order, in double, product and sum rounded separately -- the bits of partition.hpp's host loop --
+// then converted to T.  The array that was not given comes from the full-tree values of the cut stage the context retains (fullP, fullE),
+// which a given array replaces.  A thread of component t < nd reads fullP only when prob is absent and the thread of component nd writes it
+// only when prob is present; fullE[.., t] belongs to the thread of component t: no races.
+// The element types arrive as flags and not as template parameters, as in k_pack_operators: the four (context, caller) pairs would be four
+// kernels; the branch is uniform over the grid.
+struct TreeDataArgs {
+    const void *prob, *errD, *errP;   // [rows], [rows][nd], [rows][nu] of Src (callerF64); nullptr: not given
+    const int *gmap;                  // [nodes] row of every local node; nullptr: identity
+    int nodes, nd, nu;
+    int ctxF64, callerF64;            // T, Src: doubles (1) or floats (0)
+    void *dprob, *dsqrtp, *derrD, *derrP;   // of T
+    double *prob64;                   // fp32 contexts: the probabilities once more as doubles (rn_get_tree_data, the host copy); else nullptr
+    int *bad;                         // [gridDim.x]
+    int nPar, cutFirst;               // cut parents (0: no moments); full-tree index of the first node of the cut stage
+    const int *cutC0, *cutNc;         // [nPar] full-tree index of a cut parent's first child, its number of children
+    double *fullP, *fullE;            // [cut-stage nodes], [cut-stage nodes][nd]
+    void *momE, *momP;                // of T: [nPar][nd], [nPar]
+};
+constexpr int TREE_THREADS = 256, TREE_MAX_BLOCKS = 64;
+template <typename T, typename Src>
+__device__ __forceinline__ void tree_data_body(const TreeDataArgs &a) {
+    T *const dprob = static_cast<T *>(a.dprob), *const dsqrtp = static_cast<T *>(a.dsqrtp), *const derrD = static_cast<T *>(a.derrD), *const derrP = static_cast<T *>(a.derrP);
+    T *const momE = static_cast<T *>(a.momE), *const momP = static_cast<T *>(a.momP);
+    const Src *const prob = static_cast<const Src *>(a.prob), *const errD = static_cast<const Src *>(a.errD), *const errP = static_cast<const Src *>(a.errP);
+    const int W = max(max(a.nd, a.nu), 1);
+    const long long total = (long long)a.nodes * W;
+    int bad = 0;
+    for (long long base = (long long)blockIdx.x * TREE_THREADS; base < total; base += (long long)gridDim.x * TREE_THREADS) {   // (uniform trip count: the barrier below)
+        const long long i = base + threadIdx.x;
+        bool isBad = false;
+        if (i < total) {
+            const int node = (int)(i / W), t = (int)(i - (long long)node * W);
+            const size_t row = a.gmap ? (size_t)a.gmap[node] : (size_t)node;
+            if (t == 0 && prob) {
+                const double p = (double)prob[row];
+                isBad = !(p > 0.0 && p < __builtin_huge_val());
+                dprob[node] = (T)p;
+                dsqrtp[node] = (T)__dsqrt_rn(p);
+                if (a.prob64) a.prob64[node] = p;
+            }
+            if (errD && t < a.nd) derrD[(size_t)node * a.nd + t] = (T)errD[row * a.nd + t];
+            if (errP && t < a.nu) derrP[(size_t)node * a.nu + t] = (T)errP[row * a.nu + t];
+        }
+        bad += __syncthreads_count(isBad);
+    }
+    if (prob && threadIdx.x == 0) a.bad[blockIdx.x] = bad;
+    if (a.nPar <= 0 || (!prob && !errD)) return;
+    const int C = a.nd + 1;
+    for (int i = blockIdx.x * TREE_THREADS + threadIdx.x; i < a.nPar * C; i += gridDim.x * TREE_THREADS) {
+        const int j = i / C, t = i - j * C, c0 = a.cutC0[j], nc = a.cutNc[j];
+        double s = 0.0;
+        for (int c = c0; c < c0 + nc; c++) {
+#pragma clang fp contract(off)
+            const size_t k = (size_t)(c - a.cutFirst);
+            const double pc = prob ? (double)prob[c] : a.fullP[k];
+            if (t < a.nd) {
+                const double e = errD ? (double)errD[(size_t)c * a.nd + t] : a.fullE[k * a.nd + t];
+                const double pe = pc * e;
+                s = s + pe;
+                if (errD) a.fullE[k * a.nd + t] = e;
+            } else {
+                s = s + pc;
+                if (prob) a.fullP[k] = pc;
+            }
+        }
+        if (t < a.nd) momE[(size_t)j * a.nd + t] = (T)s; else momP[j] = (T)s;
+    }
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void __launch_bounds__(TREE_THREADS) k_tree_data(TreeDataArgs a) {
+    if (a.ctxF64) { if (a.callerF64) tree_data_body<double, double>(a); else tree_data_body<double, float>(a); }
+    else { if (a.callerF64) tree_data_body<float, double>(a); else tree_data_body<float, float>(a); }
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -16,6 +16,10 @@ namespace rn {
 struct PartitionData {
     std::vector<int> stages, nodesPerStage, nodesPerStageCumul, ancestor, nChildren, nChildrenCumul, globalNode;
     std::vector<double> probNode, errD, errP, momE, momP;
+    // the contiguous full-tree child range of every cut parent (rn_set_tree_data recomputes the moments from it), and whether every parent's
+    // children are in fact contiguous and ascending in the full tree
+    std::vector<int> cutChildStart, cutChildCount;
+    bool cutContiguous = true;
 };
 
 inline int default_cut_stage(const rn_dims *d, const rn_tree *t) {
@@ -99,9 +103,13 @@ inline int build_partition(const rn_dims *d, const rn_tree *t, const double *err
     const int first = cum[cut - 1], nPar = cum[cut] - cum[cut - 1];
     p->momP.assign(nPar, 0.0);
     if (errD) p->momE.assign((size_t)nPar * nd, 0.0);
+    p->cutChildStart.assign(nPar, cum[cut]); p->cutChildCount.assign(nPar, 0);
     for (int c = cum[cut]; c < cum[cut + 1]; c++) {
         const int par = t->ancestor[c] - 1 - first;
         if (par < 0 || par >= nPar) { delete p; err = "rn_partition_create: ancestor must be a node of the previous stage"; return RN_E_ARG; }
+        if (p->cutChildCount[par] == 0) p->cutChildStart[par] = c;
+        if (p->cutChildStart[par] + p->cutChildCount[par] != c) p->cutContiguous = false;
+        p->cutChildCount[par]++;
         const double pc = t->probNode[c];
         p->momP[par] += pc;
         if (errD) for (int j = 0; j < nd; j++) p->momE[(size_t)par * nd + j] += pc * errD[(size_t)c * nd + j];

@@ -235,6 +235,10 @@ struct CtxBase {
     virtual int get_operator_storage(int *, int *) = 0;
     virtual int set_sweep_pairing(int) = 0;
     virtual int get_sweep_pairing(int *, int *) = 0;
+    virtual int set_tree_data(size_t, int, bool, const void *, const void *, const void *) = 0;
+    virtual int get_tree_data(size_t, double *, double *, double *) = 0;
+    virtual int set_cut_children(const int *, const int *, int, bool, int, int, const double *, const double *) = 0;
+    virtual int cut_moments(double *, double *, size_t) = 0;
 };
 
 // ---- in-process stand-in for the communicator (rn_debug_local_group_*): `n` contexts of one process, one host thread each ----
@@ -437,6 +441,19 @@ struct Ctx : CtxBase {
     T *d_cut = nullptr;  // multi-GPU all-reduce payload
     T *d_momE = nullptr, *d_momP = nullptr;  // multi-GPU: children moments of the cut parents (static tree data)
     bool moments_set = false;
+    // rn_set_tree_data (k_tree_data): the per-workgroup counts of bad probabilities of the last device-form set and whether the host has still
+    // to read them (eliminate does, behind its uploads' synchronisation); treeBad: the last set held bad entries -- the context refuses the
+    // affine terms until a valid one; hProbStale: h_prob is older than d_prob (a device-form set) and is read back by whoever needs it
+    int *d_treeBad = nullptr;
+    double *d_prob64 = nullptr;         // fp32 contexts: the probabilities as given (doubles), for rn_get_tree_data and the host copy
+    bool treeCheckPending = false, treeBad = false, hProbStale = false;
+    long treeBadCount = 0;
+    // a context made by rn_create_sharded: the full-tree row of every local node on the device, the contiguous full-tree child range of every
+    // cut parent (build_partition) and the full-tree p and errorDemand of the cut stage's nodes, from which k_tree_data recomputes the moments
+    int *d_gmap = nullptr, *d_cutC0 = nullptr, *d_cutNc = nullptr;
+    double *d_fullP = nullptr, *d_fullE = nullptr;
+    int nCutPar = 0, cutFirstFull = 0;
+    bool cutContiguous = true;
     // logical views (see DESIGN.md "iterate buffers")
     T *p_xi = nullptr, *p_upd = nullptr, *p_acc = nullptr, *p_acc_other = nullptr, *p_acc_view = nullptr;
     bool acc_ready = false;
@@ -830,12 +847,16 @@ struct Ctx : CtxBase {
         DA(d_ybuf[0], n * ny) DA(d_ybuf[1], n * ny) DA(d_wbuf[0], n * ny) DA(d_wbuf[1], n * ny)
         DA(d_tmp, n * (size_t)std::max(2 * nx, std::max(nu, nv)))
         DA(d_cut, (size_t)nodes * (nv + 2 * nx))  // upper bound on cut parents
+        DA(d_treeBad, TREE_MAX_BLOCKS)
+        if (sizeof(T) == 4) { DA(d_prob64, n) }
         DA(d_tune, 8) DA(d_state, 1) DA(d_partials, std::max(ELT_MAX_BLOCKS, RN_DUAL_STAGE_MAX_BLOCKS)) DA(d_partials2, ELT_MAX_BLOCKS) DA(d_dist2, 2)
 #undef DA
         std::vector<double> sq(nodes);
         for (int i = 0; i < nodes; i++) sq[i] = std::sqrt(h_prob[i]);
         if (int rc = upload(d_sqrtp, sq.data(), nodes)) return rc;
         if (int rc = upload(d_prob, h_prob.data(), nodes)) return rc;
+        if (d_prob64) RN_HIP(hipMemcpy(d_prob64, h_prob.data(), n * sizeof(double), hipMemcpyHostToDevice));
+        RN_HIP(hipMemsetAsync(d_treeBad, 0, TREE_MAX_BLOCKS * sizeof(int), stream));
         RN_HIP(hipMemsetAsync(d_errD, 0, n * nd * sizeof(T), stream));
         RN_HIP(hipMemsetAsync(d_errP, 0, n * nu * sizeof(T), stream));
         RN_HIP(hipMemsetAsync(d_z, 0, n * ny * sizeof(T), stream));
@@ -957,6 +978,16 @@ struct Ctx : CtxBase {
             else if (int rc = dalloc(&d_A, (size_t)d.nodes * strideA)) return rc;
         }
         RN_HIP(hipMemsetAsync(d_my, 0, (size_t)d.nodes * 2 * nv * sizeof(T), stream));   // structured mode never writes m1
+        if (int rc = launch_expand()) return rc;
+        factored = true;
+        if (int rc = refresh_bounds_copies()) return rc;
+        RN_HIP(hipStreamSynchronize(stream));
+        return RN_OK;
+    }
+    // the part of the factor step that depends on p_i: the scaled bounds and, where the context holds dense blocks, the blocks themselves
+    // (Engine.cu:721-745), in the storage type in force.  One launch on the context's stream (rn_factor_step, rn_set_tree_data)
+    int launch_expand() {
+        const int nx = d.nx, nu = d.nu, nv = d.nv;
         ExpandArgs<T> ea{};
         ea.tr = tree_dev(); ea.nx = nx; ea.nu = nu; ea.nv = nv; ea.ny = ny; ea.LD = LD; ea.strideA = strideA; ea.nodes = d.nodes;
         ea.T1 = d_T1; ea.T2 = d_T2; ea.Bbt = d_Bbt; ea.Lt = d_Lt; ea.A = d_A; ea.skipBlocks = structured; ea.blo = d_blo; ea.bhi = d_bhi; ea.lo = d_lo; ea.hi = d_hi;
@@ -973,9 +1004,6 @@ struct Ctx : CtxBase {
         }
         if (!expanded) hipLaunchKernelGGL(k_expand_operators<T>, dim3(d.nodes, colChunks), dim3(LD >= 192 ? 256 : (LD >= 96 ? 128 : 64)), 0, stream, ea);
         RN_HIP(hipGetLastError());
-        factored = true;
-        if (int rc = refresh_bounds_copies()) return rc;
-        RN_HIP(hipStreamSynchronize(stream));
         return RN_OK;
     }
     int set_tree_errors(const double *ed, const double *ep) override {
@@ -1003,6 +1031,16 @@ struct Ctx : CtxBase {
         RN_HIP(hipSetDevice(device));
         if (int rc = upload(d_dhat, dhat, (size_t)d.N * d.nd)) return rc;
         if (int rc = upload(d_ahat, ahat, (size_t)d.N * d.nu)) return rc;
+        if (treeCheckPending) {   // (the uploads above have synchronised the stream: the counts of the last rn_set_tree_data_device are complete)
+            int cnt[TREE_MAX_BLOCKS];
+            RN_HIP(hipMemcpyAsync(cnt, d_treeBad, sizeof cnt, hipMemcpyDeviceToHost, stream));
+            RN_HIP(hipStreamSynchronize(stream));
+            treeBadCount = 0;
+            for (int v : cnt) treeBadCount += v;
+            treeCheckPending = false; treeBad = treeBadCount > 0;
+        }
+        RN_CHECK(!treeBad, RN_E_ARG, "rn_eliminate_input_disturbance_coupling: rn_set_tree_data_device was given " + std::to_string(treeBadCount) +
+                 " probNode entries that are not positive and finite; set valid probabilities first");
         AffineArgs<T> a{};
         a.tr = tree_dev(); a.nx = d.nx; a.nu = d.nu; a.nv = d.nv; a.nd = d.nd;
         a.Gd = d_Gd; a.Lhat = d_Lhat; a.WLt = d_WLt; a.Lt = d_Lt; a.errD = d_errD; a.errP = d_errP; a.dhat = d_dhat; a.ahat = d_ahat;
@@ -2585,6 +2623,7 @@ struct Ctx : CtxBase {
         RN_CHECK(factored, RN_E_STATE, "rn_get_operator before rn_factor_step");
         RN_CHECK(host && node >= 0 && node < d.nodes, RN_E_ARG, "rn_get_operator: bad node");
         const int nx = d.nx, nu = d.nu, nv = d.nv;
+        if (int rc = refresh_h_prob()) return rc;
         const double p = h_prob[node];
         if (op == RN_OP_OMEGA) { RN_CHECK(n == (size_t)nv * nv, RN_E_ARG, "rn_get_operator: size"); for (size_t i = 0; i < n; i++) host[i] = h_Rinv[i] / p; return RN_OK; }
         if (op == RN_OP_G) { RN_CHECK(n == (size_t)nv * nx, RN_E_ARG, "rn_get_operator: size"); for (size_t i = 0; i < n; i++) host[i] = h_Bbt[i]; return RN_OK; }
@@ -2775,13 +2814,13 @@ struct Ctx : CtxBase {
         for (int r = 0; r < reps + 1; r++) {   // first pass = warm-up
             float ms = 0;
             (void)hipEventRecord(e0, stream);
-            hipLaunchKernelGGL(k_bw_read<>, dim3(blocks), dim3(256), 0, stream, (const nat_d2 *)a, n, sink);
+            hipLaunchKernelGGL(k_bw_probe<>, dim3(blocks), dim3(256), 0, stream, (const nat_d2 *)a, (nat_d2 *)nullptr, n, sink);
             (void)hipEventRecord(e1, stream); (void)hipEventSynchronize(e1); (void)hipEventElapsedTime(&ms, e0, e1);
             if (r > 0 && ms > 0) bestR = std::max(bestR, (double)bytes / (ms * 1e-3) / 1e9);
             (void)hipEventRecord(e0, stream);
             // copy: 4 workgroups per CU measured best for a read + write stream (tools/probes/probe_stream.hip: 6.2 TB/s with
             // 1 024 workgroups, 5.2-5.4 with 4 096 or 8 192 on a 1 GiB vector)
-            hipLaunchKernelGGL(k_bw_copy<>, dim3(numCUs * 4), dim3(256), 0, stream, (const nat_d2 *)a, (nat_d2 *)b, n);
+            hipLaunchKernelGGL(k_bw_probe<>, dim3(numCUs * 4), dim3(256), 0, stream, (const nat_d2 *)a, (nat_d2 *)b, n, sink);
             (void)hipEventRecord(e1, stream); (void)hipEventSynchronize(e1); (void)hipEventElapsedTime(&ms, e0, e1);
             if (r > 0 && ms > 0) bestC = std::max(bestC, 2.0 * (double)bytes / (ms * 1e-3) / 1e9);
         }
@@ -2877,7 +2916,7 @@ struct Ctx : CtxBase {
     }
     // a caller's device array: memory of this context's device (hipPointerGetAttributes) that holds `bytes` bytes from p on.  Anything
     // else -- a host pointer above all -- is refused here, before a kernel could see it
-    int check_device_array(const void *p, size_t bytes, size_t elem, const std::string &what) {
+    int check_device_array(const void *p, size_t bytes, size_t elem, const std::string &what, const char *shape = "nodes x nv x columns") {
         RN_CHECK(((uintptr_t)p & (elem - 1)) == 0, RN_E_ARG, what + ": a pointer is not aligned to its element type");
         hipPointerAttribute_t at;
         std::memset(&at, 0, sizeof at);
@@ -2887,7 +2926,7 @@ struct Ctx : CtxBase {
         hipDeviceptr_t base = nullptr; size_t len = 0;
         if (hipMemGetAddressRange(&base, &len, (hipDeviceptr_t)p) == hipSuccess)
             RN_CHECK((const char *)p >= (const char *)base && (size_t)((const char *)p - (const char *)base) + bytes <= len, RN_E_ARG,
-                     what + ": an array is shorter than nodes x nv x columns elements");
+                     what + ": an array is shorter than " + shape + " elements");
         else (void)hipGetLastError();
         return RN_OK;
     }
@@ -2961,6 +3000,131 @@ struct Ctx : CtxBase {
         RN_HIP(es);
         return RN_OK;
     }
+    // ---- scenario probabilities and tree errors in place (rn_set_tree_data, rn_set_tree_data_device, rn_get_tree_data; k_tree_data, k_misc.hpp) ----
+    bool lib_sharded() const { return nranks > 1 && !globalNode.empty() && d_gmap != nullptr; }   // made by rn_create_sharded
+    int refresh_h_prob() {
+        if (!hProbStale) return RN_OK;
+        RN_HIP(hipSetDevice(device));
+        if (d_prob64) {
+            RN_HIP(hipMemcpyAsync(h_prob.data(), d_prob64, (size_t)d.nodes * sizeof(double), hipMemcpyDeviceToHost, stream));
+            RN_HIP(hipStreamSynchronize(stream));
+        } else if (int rc = download(h_prob.data(), d_prob, (size_t)d.nodes)) return rc;
+        hProbStale = false;
+        return RN_OK;
+    }
+    void tree_data_launch(bool callerF64, const void *prob, const void *errD, const void *errP) {
+        TreeDataArgs a{};
+        a.prob = prob; a.errD = errD; a.errP = errP; a.ctxF64 = sizeof(T) == 8 ? 1 : 0; a.callerF64 = callerF64 ? 1 : 0;
+        a.gmap = lib_sharded() ? d_gmap : nullptr;
+        a.nodes = d.nodes; a.nd = d.nd; a.nu = d.nu;
+        a.dprob = d_prob; a.dsqrtp = d_sqrtp; a.derrD = d_errD; a.derrP = d_errP; a.prob64 = d_prob64; a.bad = d_treeBad;
+        a.nPar = lib_sharded() ? nCutPar : 0; a.cutFirst = cutFirstFull; a.cutC0 = d_cutC0; a.cutNc = d_cutNc; a.fullP = d_fullP; a.fullE = d_fullE;
+        a.momE = d_momE; a.momP = d_momP;
+        const long long work = std::max<long long>((long long)d.nodes * std::max(std::max(d.nd, d.nu), 1), (long long)a.nPar * (d.nd + 1));
+        const int blocks = (int)std::max<long long>(1, std::min<long long>(TREE_MAX_BLOCKS, (work + TREE_THREADS - 1) / TREE_THREADS));
+        hipLaunchKernelGGL(k_tree_data<>, dim3(blocks), dim3(TREE_THREADS), 0, stream, a);
+    }
+    int set_tree_data(size_t nodes, int callerPrec, bool dev, const void *prob, const void *errD, const void *errP) override {
+        const std::string what = dev ? "rn_set_tree_data_device" : "rn_set_tree_data";
+        RN_CHECK(prob || errD || errP, RN_E_ARG, what + ": all three arrays are NULL");
+        RN_CHECK(callerPrec == RN_F64 || callerPrec == RN_F32, RN_E_ARG, what + ": precision is RN_F32 or RN_F64");
+        const bool lib = lib_sharded();
+        RN_CHECK(nodes == (size_t)(lib ? fullNodes : d.nodes), RN_E_ARG,
+                 what + (lib ? ": nodes must be the FULL tree's node count on a context made by rn_create_sharded" : ": nodes must be the context's node count"));
+        RN_CHECK(!lib || !(prob || errD) || (cutContiguous && d_momE), RN_E_STATE, what + ": the children of a cut parent are not contiguous in the full tree");
+        RN_HIP(hipSetDevice(device));
+        const size_t elem = callerPrec == RN_F64 ? 8 : 4;
+        const void *src[3] = {prob, errD, errP};
+        const size_t cnt[3] = {nodes, nodes * (size_t)d.nd, nodes * (size_t)d.nu};
+        const char *shape[3] = {"nodes", "nodes x nd", "nodes x nu"};
+        if (dev) {
+            for (int i = 0; i < 3; i++)
+                if (src[i]) { if (int rc = check_device_array(src[i], cnt[i] * elem, elem, what, shape[i])) return rc; }
+        } else if (prob) {
+            const double *p = static_cast<const double *>(prob);
+            for (size_t i = 0; i < nodes; i++) RN_CHECK(p[i] > 0.0 && std::isfinite(p[i]), RN_E_ARG, what + ": probNode must be positive and finite");
+        }
+        if (prob && factored) { if (int rc = v_flush()) return rc; }      // (a pending v is the previous probabilities')
+        char *stage = nullptr;
+        if (dev) {
+            tree_data_launch(callerPrec == RN_F64, prob, errD, errP);
+        } else {   // the same kernel behind a staging copy that lives inside the call (not one of the context's allocations)
+            size_t bytes = 0, at[3] = {0, 0, 0};
+            for (int i = 0; i < 3; i++) if (src[i]) { at[i] = bytes; bytes += (cnt[i] * sizeof(double) + 255) / 256 * 256; }
+            RN_HIP(hipMalloc((void **)&stage, bytes));
+            const void *dv[3] = {nullptr, nullptr, nullptr};
+            hipError_t e = hipSuccess;
+            for (int i = 0; i < 3 && e == hipSuccess; i++) if (src[i]) {
+                dv[i] = stage + at[i];
+                e = hipMemcpyAsync(stage + at[i], src[i], cnt[i] * sizeof(double), hipMemcpyHostToDevice, stream);
+            }
+            if (e != hipSuccess) { (void)hipStreamSynchronize(stream); (void)hipFree(stage); RN_HIP(e); }
+            tree_data_launch(true, dv[0], dv[1], dv[2]);
+        }
+        hipError_t e = hipGetLastError();
+        int rcx = RN_OK;
+        if (e == hipSuccess && prob && factored) {      // what of the factor step depends on p, in the storage type in force
+            rcx = launch_expand();
+            if (rcx == RN_OK) rcx = refresh_bounds_copies();
+        }
+        if (!dev) {
+            const hipError_t es = hipStreamSynchronize(stream);    // (before the staging goes: everything that uses it is on this stream)
+            (void)hipFree(stage);
+            if (e == hipSuccess) e = es;
+        }
+        RN_HIP(e);
+        if (rcx != RN_OK) return rcx;
+        if (prob) {
+            if (dev) { treeCheckPending = true; hProbStale = true; }
+            else {
+                const double *p = static_cast<const double *>(prob);
+                for (int i = 0; i < d.nodes; i++) h_prob[i] = p[lib ? globalNode[i] : i];
+                treeCheckPending = false; treeBad = false; treeBadCount = 0; hProbStale = false;
+            }
+            affine_ready = false; linConstValid = false; aux_dirty = true;      // the affine terms and every control-step constant read p
+        }
+        if ((prob || errD) && cutStage > 0 && nranks > 1 && !lib) moments_set = false;   // sharded by hand: the caller's moments are the old tree's
+        return RN_OK;
+    }
+    int get_tree_data(size_t nodes, double *prob, double *errD, double *errP) override {
+        RN_CHECK(prob || errD || errP, RN_E_ARG, "rn_get_tree_data: all three arrays are NULL");
+        RN_CHECK(nodes == (size_t)d.nodes, RN_E_ARG, "rn_get_tree_data: nodes must be the context's (local) node count");
+        RN_HIP(hipSetDevice(device));
+        if (prob) {
+            if (d_prob64) {
+                RN_HIP(hipMemcpyAsync(prob, d_prob64, nodes * sizeof(double), hipMemcpyDeviceToHost, stream));
+                RN_HIP(hipStreamSynchronize(stream));
+            } else if (int rc = download(prob, d_prob, nodes)) return rc;
+        }
+        if (errD) { if (int rc = download(errD, d_errD, nodes * d.nd)) return rc; }
+        if (errP) { if (int rc = download(errP, d_errP, nodes * d.nu)) return rc; }
+        return RN_OK;
+    }
+    // rn_create_sharded, after the moments: what k_tree_data needs to recompute them (and the full-tree row of every local node)
+    int set_cut_children(const int *c0, const int *nc, int nPar, bool contiguous, int cutFirst, int nCutNodes, const double *fullP, const double *fullE) override {
+        RN_CHECK(c0 && nc && fullP && nPar > 0 && nCutNodes > 0 && !globalNode.empty(), RN_E_ARG, "set_cut_children: bad input");
+        RN_HIP(hipSetDevice(device));
+        if (int rc = dalloc(&d_gmap, (size_t)d.nodes)) return rc;
+        if (int rc = dalloc(&d_cutC0, (size_t)nPar)) return rc;
+        if (int rc = dalloc(&d_cutNc, (size_t)nPar)) return rc;
+        if (int rc = dalloc(&d_fullP, (size_t)nCutNodes)) return rc;
+        if (int rc = dalloc(&d_fullE, (size_t)nCutNodes * d.nd)) return rc;
+        RN_HIP(hipMemcpy(d_gmap, globalNode.data(), (size_t)d.nodes * sizeof(int), hipMemcpyHostToDevice));
+        RN_HIP(hipMemcpy(d_cutC0, c0, (size_t)nPar * sizeof(int), hipMemcpyHostToDevice));
+        RN_HIP(hipMemcpy(d_cutNc, nc, (size_t)nPar * sizeof(int), hipMemcpyHostToDevice));
+        RN_HIP(hipMemcpy(d_fullP, fullP, (size_t)nCutNodes * sizeof(double), hipMemcpyHostToDevice));
+        if (fullE) RN_HIP(hipMemcpy(d_fullE, fullE, (size_t)nCutNodes * d.nd * sizeof(double), hipMemcpyHostToDevice));
+        else RN_HIP(hipMemset(d_fullE, 0, (size_t)nCutNodes * d.nd * sizeof(double)));
+        nCutPar = nPar; cutFirstFull = cutFirst; cutContiguous = contiguous;
+        return RN_OK;
+    }
+    int cut_moments(double *E, double *P, size_t nParents) override {
+        RN_CHECK(cutStage > 0 && moments_set && d_momE, RN_E_STATE, "rn_debug_cut_moments: no children moments are set");
+        RN_CHECK(E && P && nParents == (size_t)(h_stageCum[cutStage] - h_stageCum[cutStage - 1]), RN_E_ARG, "rn_debug_cut_moments: one row per cut parent expected");
+        RN_HIP(hipSetDevice(device));
+        if (int rc = download(E, d_momE, nParents * d.nd)) return rc;
+        return download(P, d_momP, nParents);
+    }
     int set_cut_moments(const double *E, const double *P, size_t nParents) override {
         RN_CHECK(cutStage > 0, RN_E_STATE, "rn_set_cut_children_moments: set the cut stage first");
         RN_CHECK(E && P && nParents == (size_t)(h_stageCum[cutStage] - h_stageCum[cutStage - 1]), RN_E_ARG, "rn_set_cut_children_moments: one row per cut parent expected");
@@ -3007,6 +3171,10 @@ const char *rn_last_error(const rn_ctx *ctx) { return (ctx && ctx->impl) ? ctx->
 int rn_synchronize(rn_ctx *ctx) { RN_GUARD(ctx); return ctx->impl->synchronize(); }
 int rn_factor_step(rn_ctx *ctx, const rn_system *sys) { RN_GUARD(ctx); return ctx->impl->factor_step(sys); }
 int rn_set_tree_errors(rn_ctx *ctx, const double *ed, const double *ep) { RN_GUARD(ctx); return ctx->impl->set_tree_errors(ed, ep); }
+int rn_set_tree_data(rn_ctx *ctx, size_t nodes, const double *p, const double *ed, const double *ep) { RN_GUARD(ctx); return ctx->impl->set_tree_data(nodes, RN_F64, false, p, ed, ep); }
+int rn_set_tree_data_device(rn_ctx *ctx, size_t nodes, int precision, const void *p, const void *ed, const void *ep) { RN_GUARD(ctx); return ctx->impl->set_tree_data(nodes, precision, true, p, ed, ep); }
+int rn_get_tree_data(rn_ctx *ctx, size_t nodes, double *p, double *ed, double *ep) { RN_GUARD(ctx); return ctx->impl->get_tree_data(nodes, p, ed, ep); }
+int rn_debug_cut_moments(rn_ctx *ctx, double *E, double *P, size_t n) { RN_GUARD(ctx); return ctx->impl->cut_moments(E, P, n); }
 int rn_set_uncertainty(rn_ctx *ctx, int dflag, int pflag, double w) { RN_GUARD(ctx); return ctx->impl->set_uncertainty(dflag, pflag, w); }
 int rn_update_state_control(rn_ctx *ctx, const double *x, const double *u, const double *dm) { RN_GUARD(ctx); return ctx->impl->update_state_control(x, u, dm); }
 int rn_eliminate_input_disturbance_coupling(rn_ctx *ctx, const double *dh, const double *ah) { RN_GUARD(ctx); return ctx->impl->eliminate(dh, ah); }
@@ -3136,6 +3304,12 @@ int rn_create_sharded(const rn_dims *dims, const rn_tree *tree, const double *er
             const double *E = part.momE;
             if (!E) { zeros.assign((size_t)part.nCutParents * dims->nd, 0.0); E = zeros.data(); }
             rc = c->set_cut_moments(E, part.momP, (size_t)part.nCutParents);
+        }
+        if (rc == RN_OK) {   // what rn_set_tree_data needs to recompute the moments: every cut parent's child range, the cut stage's full-tree p and errorDemand
+            const rn::PartitionData *pd = static_cast<const rn::PartitionData *>(part.owner);
+            const int c0 = tree->nodesPerStageCumul[part.cutStage], c1 = tree->nodesPerStageCumul[part.cutStage + 1];
+            rc = c->set_cut_children(pd->cutChildStart.data(), pd->cutChildCount.data(), part.nCutParents, pd->cutContiguous, c0, c1 - c0,
+                                     tree->probNode + c0, errD ? errD + (size_t)c0 * dims->nd : nullptr);
         }
         if (rc == RN_OK && id128) rc = c->exchange_prepare_api();    // AUTO / one-shot: this rank's inbox, the peers' mapped (collective; falls back by agreement)
         if (rc != RN_OK) { g_create_error = c->err; rn_destroy(ctx); ctx = nullptr; }
