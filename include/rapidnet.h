@@ -200,6 +200,42 @@ int rn_set_tree_errors(rn_ctx *ctx, const double *errorDemandNode /* nodes*nd */
 int rn_set_tree_data(rn_ctx *ctx, size_t nodes, const double *probNode, const double *errorDemandNode, const double *errorPriceNode);
 int rn_set_tree_data_device(rn_ctx *ctx, size_t nodes, int precision, const void *probNode, const void *errorDemandNode, const void *errorPriceNode);
 int rn_get_tree_data(rn_ctx *ctx, size_t nodes, double *probNode, double *errorDemandNode, double *errorPriceNode);
+/* Box and safety bounds per stage or per node, replaced in place (the reference keeps devSysXmin ... devSysUmax as per-node arrays and hands
+ * out their device pointers, Engine.cuh:294-314 getSysXmin() ... getSysUmax(), so its callers can give any node its own bounds; the scaling is
+ * Engine.cu preconditionConstraintX / preconditionConstraintU): a safety volume that follows the demand forecast, a pump out of service for
+ * the next hours, a tank taken down in one scenario only -- without another rn_factor_step.
+ * granularity / rows: RN_BOUNDS_SHARED, rows = 1: one row for the whole tree (what rn_factor_step sets from rn_system); RN_BOUNDS_PER_STAGE,
+ *   rows = dims.N: a node at stage s uses row s, the row index of matDiagPrecnd; RN_BOUNDS_PER_NODE, rows = the context's node count: node i
+ *   uses row i -- on a sharded context the LOCAL rows in the order of rn_shard_global_nodes, as rn_set_operators takes them (the caller gives
+ *   replicated crown nodes the same values on every rank).  Any other pair: RN_E_ARG.
+ * Values: xmin, xmax, xsafe [rows][nx], umin, umax [rows][nu], physical (unscaled), the units of rn_system.  The library applies
+ *   sqrt(p_i) d_c exactly as the factor step does (the same expression, the same single rounding); the upper bound of the safety half stays
+ *   the internal +BIG.
+ * NULL: a NULL array keeps its values while the granularity stays what it is; a call that changes the granularity needs all five (RN_E_ARG
+ *   otherwise); all five NULL: RN_E_ARG.
+ * State: RN_E_STATE before rn_factor_step.  A later rn_factor_step returns the context to RN_BOUNDS_SHARED with its own vectors (as it
+ *   recomputes handed-in operator blocks); a later rn_set_tree_data[_device] that gives probNode keeps granularity and physical values and
+ *   rescales them with the new sqrt(p).  Duals, warm start, algorithm, L-BFGS memory, stop tolerance, operator mode and storage, sweep pairing
+ *   and the affine terms are untouched (bounds do not enter rn_eliminate_input_disturbance_coupling); an RN_OPS_AUTO context stays structured.
+ *   rn_control_action(..., projectOnBounds) clamps with the root's row.
+ * rn_set_bounds: host arrays of doubles.  It validates first -- every value finite, xmin <= xmax, umin <= umax (an array that is not given is
+ *   compared as the context holds it) -- and returns RN_E_ARG with nothing changed otherwise; its staging is allocated and freed inside the
+ *   call (rn_device_memory_info info[2] is the same before and after at a granularity already in force) and it synchronises, as rn_set does.
+ * rn_set_bounds_device: arrays in device memory, elements of type `precision` (RN_F32 / RN_F64 whatever the context's own type); launches on
+ *   the context's stream only, no host synchronisation.  Pointers are checked as rn_set_operators_device checks its arrays.  The VALUES ARE NOT
+ *   VALIDATED: a NaN or a lower bound above its upper bound goes into the solver as given.  The first call at a new granularity (either
+ *   form) allocates that table ([rows][ny] x 2 in the context's type) and may synchronise; later calls allocate nothing.
+ * rn_get_bounds: the physical values as the context holds them (in its own type: an fp32 context returns the floats it keeps), rows as
+ *   rn_get_bounds_layout reports; a NULL array is skipped, all five NULL: RN_E_ARG.
+ * Cost: RN_BOUNDS_SHARED and RN_BOUNDS_PER_STAGE tables stay in cache; in RN_BOUNDS_PER_NODE the fused dual update reads two more streams
+ *   (rn_algorithmic_bytes counts 7 n_y instead of 5 n_y reals per node in that mode): the caller's choice. */
+enum { RN_BOUNDS_SHARED = 0, RN_BOUNDS_PER_STAGE = 1, RN_BOUNDS_PER_NODE = 2 };
+int rn_set_bounds(rn_ctx *ctx, int granularity, size_t rows, const double *xmin, const double *xmax, const double *xsafe /* [rows][nx] */,
+                  const double *umin, const double *umax /* [rows][nu] */);
+int rn_set_bounds_device(rn_ctx *ctx, int granularity, size_t rows, int precision, const void *xmin, const void *xmax, const void *xsafe,
+                         const void *umin, const void *umax);
+int rn_get_bounds_layout(rn_ctx *ctx, int *granularity, size_t *rows);
+int rn_get_bounds(rn_ctx *ctx, size_t rows, double *xmin, double *xmax, double *xsafe, double *umin, double *umax);
 /* Engine::setDemandUncertaintyFlag / setPriceUncertaintyFlag / SmpcConfiguration::getWeightEconomical */
 int rn_set_uncertainty(rn_ctx *ctx, int demandUncertainty, int priceUncertainty, double weightEconomical);
 /* Engine::updateStateControl (Engine.cu:1300-1316) */

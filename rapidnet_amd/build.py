@@ -47,7 +47,7 @@ UNITS = {
     "k_misc": ["common.hpp", "k_misc.hpp"],
     "k_fbe": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "fbe_kernels.hpp"],
     "rapidnet_capi": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "k_stream.hpp", "k_misc.hpp", "kernels.hpp", "fbe_kernels.hpp", "fbe_methods.inc",
-                      "partition.hpp"],
+                      "partition.hpp", "bounds.hpp"],
 }
 OBJ_DIR = os.path.join(HERE, "build")
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]
@@ -161,6 +161,7 @@ TEST_SWEEP_PAIRING = os.path.join(BIN_DIR, "test_sweep_pairing")
 TEST_OPERATOR_BULK = os.path.join(BIN_DIR, "test_operator_bulk")
 TEST_STOP_TOLERANCE = os.path.join(BIN_DIR, "test_stop_tolerance")
 TEST_TREE_DATA = os.path.join(BIN_DIR, "test_tree_data")
+TEST_BOUNDS = os.path.join(BIN_DIR, "test_bounds")
 
 
 def build_host(force=False):
@@ -205,6 +206,11 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_TREE_DATA, test_src, "-L" + HERE, "-lrapidnet_host",
                                "-lrapidnet_hip", "-ldl", "-Wl,-rpath,$ORIGIN/.."])
         _stamp(TEST_TREE_DATA, [test_src] + deps + hdr)
+    test_src = os.path.join(ROOT, "tests", "cpp", "test_bounds.cpp")
+    if force or _stale(TEST_BOUNDS, [test_src] + deps + hdr):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_BOUNDS, test_src, "-L" + HERE, "-lrapidnet_host",
+                               "-lrapidnet_hip", "-ldl", "-Wl,-rpath,$ORIGIN/.."])
+        _stamp(TEST_BOUNDS, [test_src] + deps + hdr)
     return LIB_HOST
 
 

@@ -25,6 +25,8 @@ STORE_NATIVE, STORE_F32 = 0, 1
 STORAGES = {"native": STORE_NATIVE, "f32": STORE_F32}
 PAIR_OFF, PAIR_ON, PAIR_AUTO = 0, 1, 2
 PAIRINGS = {"off": PAIR_OFF, "on": PAIR_ON, "auto": PAIR_AUTO}
+BOUNDS_SHARED, BOUNDS_PER_STAGE, BOUNDS_PER_NODE = 0, 1, 2      # rn_set_bounds
+BOUNDS = {"shared": BOUNDS_SHARED, "stage": BOUNDS_PER_STAGE, "node": BOUNDS_PER_NODE}
 # include/rapidnet_debug.h, RN_KNOB_*
 KNOBS = {k: i for i, k in enumerate(("dual_trips", "dual_pipe", "vlv_wide", "slab_pipe", "slab_frag", "unscaled_walk", "stream_two_per_cu",
                                      "stream_split", "nama_pair", "ls_sequential", "value_mfma", "tune_bias_us", "struct_linear", "fuse_split"))}
@@ -46,7 +48,7 @@ SYMBOLS = [
     "rn_get_range", "rn_set_range", "rn_get_kernel_info", "rn_default_cut_stage", "rn_partition_create", "rn_partition_destroy", "rn_create_sharded", "rn_shard_info", "rn_shard_global_nodes",
     "rn_debug_set_allreduce", "rn_debug_local_group_create", "rn_debug_local_group_join", "rn_debug_local_group_destroy",
     "rn_guard_check", "rn_device_memory_info", "rn_reserve_iterations", "rn_profile_read_collective", "rn_debug_inject_allocation", "rn_guard_report", "rn_debug_guard_poke",
-    "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_debug_cut_moments",
+    "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_set_bounds", "rn_set_bounds_device", "rn_get_bounds_layout", "rn_get_bounds", "rn_debug_cut_moments",
     "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info",
 ]
 
@@ -238,6 +240,10 @@ def load():
     lib.rn_set_tree_data.argtypes = [vp, C.c_size_t, dp, dp, dp]
     lib.rn_set_tree_data_device.argtypes = [vp, C.c_size_t, ip, vp, vp, vp]
     lib.rn_get_tree_data.argtypes = [vp, C.c_size_t, dp, dp, dp]
+    lib.rn_set_bounds.argtypes = [vp, ip, C.c_size_t, dp, dp, dp, dp, dp]
+    lib.rn_set_bounds_device.argtypes = [vp, ip, C.c_size_t, ip, vp, vp, vp, vp, vp]
+    lib.rn_get_bounds_layout.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
+    lib.rn_get_bounds.argtypes = [vp, C.c_size_t, dp, dp, dp, dp, dp]
     lib.rn_debug_cut_moments.argtypes = [vp, dp, dp, C.c_size_t]
     _LIB = lib
     return lib
@@ -643,6 +649,44 @@ class Solver:
         """rn_get_tree_data: dict(prob [nodes], errorDemand [nodes][nd], errorPrice [nodes][nu]) as the context holds them (local rows on a shard)"""
         out = {"prob": np.zeros(self.nodes), "errorDemand": np.zeros((self.nodes, self.nd)), "errorPrice": np.zeros((self.nodes, self.nu))}
         self._check(self.lib.rn_get_tree_data(self.h, self.nodes, out["prob"].ctypes.data, out["errorDemand"].ctypes.data, out["errorPrice"].ctypes.data))
+        return out
+
+    # ---- box and safety bounds per stage or per node in place (rn_set_bounds ...) ----------------------------------
+    def _boundsRows(self, granularity):
+        g = BOUNDS.get(granularity, granularity)
+        return int(g), {BOUNDS_SHARED: 1, BOUNDS_PER_STAGE: self.N, BOUNDS_PER_NODE: self.nodes}.get(g, 0)
+
+    def setBounds(self, granularity, xmin=None, xmax=None, xsafe=None, umin=None, umax=None, rows=None):
+        """rn_set_bounds: physical bounds, xmin / xmax / xsafe [rows][nx], umin / umax [rows][nu]; granularity "shared" | "stage" | "node" or a
+        BOUNDS_* value (rows 1, N, the context's local node count); None keeps that array while the granularity stays what it is"""
+        g, r = self._boundsRows(granularity)
+        r = r if rows is None else int(rows)
+        arrs = [None if v is None else _f64(v) for v in (xmin, xmax, xsafe, umin, umax)]
+        for a, nm, dim in zip(arrs, ("xmin", "xmax", "xsafe", "umin", "umax"), (self.nx, self.nx, self.nx, self.nu, self.nu)):
+            if a is not None and a.size != r * dim:
+                raise ValueError("setBounds: %s needs %d x %d values, got %d" % (nm, r, dim, a.size))
+        self._check(self.lib.rn_set_bounds(self.h, g, r, *[None if a is None else a.ctypes.data for a in arrs]))
+
+    def setBoundsDevice(self, granularity, precision, xmin=0, xmax=0, xsafe=0, umin=0, umax=0, rows=None):
+        """rn_set_bounds_device: integer device addresses (0: not given) of arrays of `precision` ("f64" | "f32" or an RN_F* value) elements;
+        launches on the context's stream, nothing is waited for and the values are not validated"""
+        g, r = self._boundsRows(granularity)
+        prec = {"f64": RN_F64, "f32": RN_F32}.get(precision, precision)
+        self._check(self.lib.rn_set_bounds_device(self.h, g, r if rows is None else int(rows), int(prec),
+                                                  *[int(p) or None for p in (xmin, xmax, xsafe, umin, umax)]))
+
+    def boundsLayout(self):
+        """rn_get_bounds_layout: (granularity as a BOUNDS_* value, rows)"""
+        g, r = C.c_int(0), C.c_size_t(0)
+        self._check(self.lib.rn_get_bounds_layout(self.h, C.byref(g), C.byref(r)))
+        return g.value, r.value
+
+    def getBounds(self):
+        """rn_get_bounds: dict(granularity, rows, xmin, xmax, xsafe [rows][nx], umin, umax [rows][nu]), physical values as the context holds them"""
+        g, r = self.boundsLayout()
+        out = {k: np.zeros((r, self.nx if k[0] == "x" else self.nu)) for k in ("xmin", "xmax", "xsafe", "umin", "umax")}
+        self._check(self.lib.rn_get_bounds(self.h, r, *[out[k].ctypes.data for k in ("xmin", "xmax", "xsafe", "umin", "umax")]))
+        out["granularity"], out["rows"] = g, r
         return out
 
     def updateTree(self, tree):

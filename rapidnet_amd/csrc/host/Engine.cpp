@@ -93,6 +93,23 @@ void Engine::updateScenarioTree() {
     setTreeData(ptrMyScenarioTree->getProbArray(), ptrMyScenarioTree->getErrorDemandArray(), ptrMyScenarioTree->getErrorPriceArray());
 }
 
+void Engine::setBounds(int granularity, size_t rows, const real_t *xmin, const real_t *xmax, const real_t *xsafe, const real_t *umin, const real_t *umax) {
+    check(rn_set_bounds(ctx, granularity, rows, xmin, xmax, xsafe, umin, umax), "rn_set_bounds");
+}
+void Engine::setBoundsDevice(int granularity, size_t rows, int precision, const void *xmin, const void *xmax, const void *xsafe, const void *umin, const void *umax) {
+    check(rn_set_bounds_device(ctx, granularity, rows, precision, xmin, xmax, xsafe, umin, umax), "rn_set_bounds_device");
+}
+int Engine::getBoundsLayout(size_t *rows) {
+    int granularity = RN_BOUNDS_SHARED;
+    size_t r = 0;
+    check(rn_get_bounds_layout(ctx, &granularity, &r), "rn_get_bounds_layout");
+    if (rows) *rows = r;
+    return granularity;
+}
+void Engine::getBounds(size_t rows, real_t *xmin, real_t *xmax, real_t *xsafe, real_t *umin, real_t *umax) {
+    check(rn_get_bounds(ctx, rows, xmin, xmax, xsafe, umin, umax), "rn_get_bounds");
+}
+
 void Engine::create(int precision, int device, int operatorMode, int rank, int nranks, const void *id128, int cutStage) {
     myRank = rank; numRanks = nranks;
     priceUncertaintyFlag = true; demandUncertaintyFlag = true;

@@ -76,6 +76,18 @@ public:
     void getTreeData(real_t *prob, real_t *errorDemand, real_t *errorPrice);
     // pushes the ScenarioTree's current arrays (ScenarioTree::setProbArray ... / reload)
     void updateScenarioTree();
+    // Box and safety bounds per stage or per node, replaced in place after factorStep() (rapidnet.h, rn_set_bounds; the reference's callers write
+    // through getSysXmin() ... getSysUmax(), Engine.cuh:294-314): physical values, xmin / xmax / xsafe [rows][nx], umin / umax [rows][nu];
+    // granularity RN_BOUNDS_SHARED (rows 1), RN_BOUNDS_PER_STAGE (rows N) or RN_BOUNDS_PER_NODE (rows getNumLocalNodes(), in the order of
+    // getGlobalNodes()).  A null pointer keeps that array while the granularity stays what it is; factorStep() returns to the network's vectors.
+    void setBounds(int granularity, size_t rows, const real_t *xmin, const real_t *xmax, const real_t *xsafe, const real_t *umin, const real_t *umax);
+    // ... device arrays of RN_F32 / RN_F64 elements: launches on the engine's stream (rn_stream(getContext())), nothing is waited for and
+    // the values are not validated
+    void setBoundsDevice(int granularity, size_t rows, int precision, const void *xmin, const void *xmax, const void *xsafe, const void *umin, const void *umax);
+    // what the engine holds: the granularity in force (*rows: its row count), and the physical values (rows as getBoundsLayout reports; a null
+    // pointer skips that array)
+    int getBoundsLayout(size_t *rows = nullptr);
+    void getBounds(size_t rows, real_t *xmin, real_t *xmax, real_t *xsafe, real_t *umin, real_t *umax);
     int getRank() { return myRank; }
     int getNumRanks() { return numRanks; }
     uint_t getNumLocalNodes();                       // nodes this rank holds (= the tree's node count on one GPU)

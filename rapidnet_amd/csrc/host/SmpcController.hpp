@@ -31,6 +31,12 @@ public:
         ptrMyEngine->getScenarioTree()->reload(pathToScenarioTreeJson);
         ptrMyEngine->updateScenarioTree();
     }
+    // bounds per stage or per node between two controlAction calls (Engine::setBounds, rapidnet.h rn_set_bounds): no new context, no factor
+    // step beyond the first; a receding horizon shifts the rows every step, so the caller sets them each step
+    void updateBounds(int granularity, size_t rows, const real_t *xmin, const real_t *xmax, const real_t *xsafe, const real_t *umin, const real_t *umax) {
+        if (!factorStepFlag) { ptrMyEngine->factorStep(); factorStepFlag = true; }
+        ptrMyEngine->setBounds(granularity, rows, xmin, xmax, xsafe, umin, umax);
+    }
     void moveForewardInTime();                              // :1679-1716
     // in-built simulator of moveForewardInTime: false (default) = the reference as written, x+ = x + B u (its disturbance
     // term lands in the x of node 0 instead of the state update, :1695); true = x+ = x + e_0 + B u (DwnNetwork.cuh:41-57)

@@ -31,6 +31,9 @@ struct DualArgs {
     // lo = (sqrt(p_i) d_c) blo_c, hi = (sqrt(p_i) d_c) bhi_c (safety half: bhi_c), from tables that live in L1/L2
     int regen;
     const int *stageOf; const T *sqrtp, *dy, *blo, *bhi;
+    // row of the unscaled bound tables a node reads (rn_set_bounds): blo + stage * bStrideStage + node * bStrideNode + c, in elements --
+    // (0, 0) one row for the whole tree, (ny, 0) a row per stage, (0, ny) a row per node; rows * ny fits an int (checked by the host)
+    int bStrideStage, bStrideNode;
     // decideHere (fix-up launch only): the trip decision and the bookkeeping of the iteration are done by THIS launch
     // instead of a k_decide_finalize launch of their own: every workgroup folds the main pass's dist^2 partials itself
     // (same order everywhere => same decision), workgroup 0 also folds the arg-max, writes the history entry and advances
@@ -214,9 +217,10 @@ __global__ void __launch_bounds__(ELT_THREADS) k_dual_fused(DualArgs<T> a) {
                     int cc = c0, nn = nd0;
 #pragma unroll
                     for (int e = 0; e < VN; e++) {
-                        const T k = a.sqrtp[nn] * a.dy[(size_t)a.stageOf[nn] * ny + cc];
-                        lo[e] = k * a.blo[cc];
-                        hi[e] = (cc >= nx && cc < 2 * nx) ? a.bhi[cc] : k * a.bhi[cc];
+                        const int stg = a.stageOf[nn], bc = stg * a.bStrideStage + nn * a.bStrideNode + cc;
+                        const T k = a.sqrtp[nn] * a.dy[(size_t)stg * ny + cc];
+                        lo[e] = k * a.blo[bc];
+                        hi[e] = (cc >= nx && cc < 2 * nx) ? a.bhi[bc] : k * a.bhi[bc];
                         if (++cc == ny) { cc = 0; nn++; }
                     }
                 } else { lo = reinterpret_cast<const VT *>(a.lo)[iv]; hi = reinterpret_cast<const VT *>(a.hi)[iv]; }
@@ -363,8 +367,9 @@ __device__ __forceinline__ void dual_slot_load(DualSlot<T> &s, const DualArgs<T>
 #else
     s.sp = a.sqrtp[node];
     s.dy = *reinterpret_cast<const VT *>(a.dy + (size_t)stage * a.ny + s.c);
-    s.blo = *reinterpret_cast<const VT *>(a.blo + s.c);
-    s.bhi = *reinterpret_cast<const VT *>(a.bhi + s.c);
+    const int bc = stage * a.bStrideStage + node * a.bStrideNode + s.c;
+    s.blo = *reinterpret_cast<const VT *>(a.blo + bc);
+    s.bhi = *reinterpret_cast<const VT *>(a.bhi + bc);
 #endif
 }
 template <typename T, bool MATERIALIZE, bool SCALE = false>

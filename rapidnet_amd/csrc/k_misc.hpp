@@ -42,7 +42,8 @@ struct ExpandArgs {
     S *A;
     // scaled bounds in y order
     int skipBlocks;       // structured operator mode: only the scaled bounds are produced
-    const T *blo, *bhi;   // [ny] unscaled: xmin|xsafe|umin and xmax|+BIG|umax
+    const T *blo, *bhi;   // [rows][ny] unscaled: xmin|xsafe|umin and xmax|+BIG|umax
+    int bStrideStage, bStrideNode;   // the row of a node (rn_set_bounds): stage * bStrideStage + node * bStrideNode, in elements
     T *lo, *hi;           // [node][ny]
 };
 template <typename T, typename S = T>
@@ -65,9 +66,10 @@ __global__ void k_expand_operators(ExpandArgs<T, S> a) {
         if (threadIdx.x == 0) {
             // bound scaling: preconditionConstraintX/U.  "+BIG" stays +BIG (no upper bound on the safety half)
             const T k = sp * d;
-            a.lo[(size_t)node * a.ny + c] = k * a.blo[c];
+            const int bc = stage * a.bStrideStage + node * a.bStrideNode + c;
+            a.lo[(size_t)node * a.ny + c] = k * a.blo[bc];
             const bool safety = (c >= a.nx && c < 2 * a.nx);
-            a.hi[(size_t)node * a.ny + c] = safety ? a.bhi[c] : k * a.bhi[c];
+            a.hi[(size_t)node * a.ny + c] = safety ? a.bhi[bc] : k * a.bhi[bc];
         }
     }
 }
@@ -196,8 +198,74 @@ struct TreeDataArgs {
     const int *cutC0, *cutNc;         // [nPar] full-tree index of a cut parent's first child, its number of children
     double *fullP, *fullE;            // [cut-stage nodes], [cut-stage nodes][nd]
     void *momE, *momP;                // of T: [nPar][nd], [nPar]
+    // Box and safety bounds replaced in place (rn_set_bounds / rn_set_bounds_device; Engine.cuh:294-314 getSysXmin() ... getSysUmax(), Engine.cu
+    // preconditionConstraintX/U): the caller's physical values, [bRows][nx] (xmin, xmax, xsafe) and [bRows][nu] (umin, umax) of Src, nullptr: not
+    // given.  A node reads row stage * bRowStage + node * bRowNode ((0,0) shared, (1,0) per stage, (0,1) per node; local nodes: no gmap).  Written
+    // in T: the unscaled tables blo / bhi [bRows][ny] in y order (xmin|xsafe|umin, xmax|+BIG|umax; the +BIG columns are always written), the
+    // scaled lo / hi [nodes][ny] of every node -- (sqrt(p_i) d_c) v, k_expand_operators' expression and rounding, straight from the caller's value
+    // and not through the table, which other workgroups are still writing -- and, where they exist, the node-major copies rn_device_pointer hands
+    // out.  An array that was not given leaves its columns of every output alone.  bRows == 0: no bounds in this launch.
+    const void *bnd[5];               // xmin, xmax, xsafe, umin, umax
+    int bRows, bRowStage, bRowNode, nx, ny;
+    const int *stageOf;               // [nodes]
+    const void *sqrtpIn, *dy;         // of T: [nodes], [N][ny]
+    void *blo, *bhi, *lo, *hi;        // of T
+    void *bndCopy[5];                 // of T: [nodes][nx | nu] in the order of bnd, or all nullptr
 };
-constexpr int TREE_THREADS = 256, TREE_MAX_BLOCKS = 64;
+constexpr int TREE_THREADS = 256, TREE_MAX_BLOCKS = 64, BOUNDS_MAX_BLOCKS = 1024;
+__device__ __forceinline__ void bounds_big(double &v) { v = __longlong_as_double(0x7F7F7F7F7F7F7F7FLL); }   // bytes 0x7F (Engine.cu:454-455)
+__device__ __forceinline__ void bounds_big(float &v) { v = __int_as_float(0x7F7F7F7F); }
+// column c of the y order: the caller's arrays that hold its lower / upper bound (hi == nullptr in the safety half: +BIG, or not given), the
+// node-major copies they go to, the index inside a row and the row length (branches, not indexed pointer arrays: those would live in scratch)
+template <typename T, typename Src>
+struct BoundsCol { const Src *lo, *hi; T *copyLo, *copyHi; int t, dim; bool safety; };
+template <typename T, typename Src>
+__device__ __forceinline__ BoundsCol<T, Src> bounds_column(const TreeDataArgs &a, int c) {
+    BoundsCol<T, Src> k;
+    if (c < a.nx) {
+        k.lo = static_cast<const Src *>(a.bnd[0]); k.hi = static_cast<const Src *>(a.bnd[1]);
+        k.copyLo = static_cast<T *>(a.bndCopy[0]); k.copyHi = static_cast<T *>(a.bndCopy[1]); k.t = c; k.dim = a.nx; k.safety = false;
+    } else if (c < 2 * a.nx) {
+        k.lo = static_cast<const Src *>(a.bnd[2]); k.hi = nullptr;
+        k.copyLo = static_cast<T *>(a.bndCopy[2]); k.copyHi = nullptr; k.t = c - a.nx; k.dim = a.nx; k.safety = true;
+    } else {
+        k.lo = static_cast<const Src *>(a.bnd[3]); k.hi = static_cast<const Src *>(a.bnd[4]);
+        k.copyLo = static_cast<T *>(a.bndCopy[3]); k.copyHi = static_cast<T *>(a.bndCopy[4]); k.t = c - 2 * a.nx; k.dim = a.nu; k.safety = false;
+    }
+    return k;
+}
+template <typename T, typename Src>
+__device__ __forceinline__ void bounds_body(const TreeDataArgs &a) {
+    T *const blo = static_cast<T *>(a.blo), *const bhi = static_cast<T *>(a.bhi), *const lo = static_cast<T *>(a.lo), *const hi = static_cast<T *>(a.hi);
+    const T *const sqrtp = static_cast<const T *>(a.sqrtpIn), *const dy = static_cast<const T *>(a.dy);
+    const int ny = a.ny;
+    const long long stride = (long long)gridDim.x * TREE_THREADS, gid = (long long)blockIdx.x * TREE_THREADS + threadIdx.x;
+    T big; bounds_big(big);
+    for (long long i = gid; i < (long long)a.bRows * ny; i += stride) {      // the unscaled tables
+        const int row = (int)(i / ny), c = (int)(i - (long long)row * ny);
+        const BoundsCol<T, Src> k = bounds_column<T, Src>(a, c);
+        if (k.lo) blo[i] = (T)k.lo[(size_t)row * k.dim + k.t];
+        if (k.safety) bhi[i] = big;
+        else if (k.hi) bhi[i] = (T)k.hi[(size_t)row * k.dim + k.t];
+    }
+    for (long long i = gid; i < (long long)a.nodes * ny; i += stride) {      // the scaled bounds of every node
+        const int node = (int)(i / ny), c = (int)(i - (long long)node * ny);
+        const int stage = a.stageOf[node];
+        const size_t row = (size_t)stage * a.bRowStage + (size_t)node * a.bRowNode;
+        const BoundsCol<T, Src> k = bounds_column<T, Src>(a, c);
+        const T f = sqrtp[node] * dy[(size_t)stage * ny + c];
+        if (k.lo) {
+            const T v = f * (T)k.lo[row * k.dim + k.t];
+            lo[i] = v;
+            if (k.copyLo) k.copyLo[(size_t)node * k.dim + k.t] = v;
+        }
+        if (k.hi) {
+            const T v = f * (T)k.hi[row * k.dim + k.t];
+            hi[i] = v;
+            if (k.copyHi) k.copyHi[(size_t)node * k.dim + k.t] = v;
+        }
+    }
+}
 template <typename T, typename Src>
 __device__ __forceinline__ void tree_data_body(const TreeDataArgs &a) {
     T *const dprob = static_cast<T *>(a.dprob), *const dsqrtp = static_cast<T *>(a.dsqrtp), *const derrD = static_cast<T *>(a.derrD), *const derrP = static_cast<T *>(a.derrP);
@@ -205,6 +273,8 @@ __device__ __forceinline__ void tree_data_body(const TreeDataArgs &a) {
     const Src *const prob = static_cast<const Src *>(a.prob), *const errD = static_cast<const Src *>(a.errD), *const errP = static_cast<const Src *>(a.errP);
     const int W = max(max(a.nd, a.nu), 1);
     const long long total = (long long)a.nodes * W;
+    if (a.bRows > 0) bounds_body<T, Src>(a);
+    if (!prob && !errD && !errP) return;      // (a launch of rn_set_bounds)
     int bad = 0;
     for (long long base = (long long)blockIdx.x * TREE_THREADS; base < total; base += (long long)gridDim.x * TREE_THREADS) {   // (uniform trip count: the barrier below)
         const long long i = base + threadIdx.x;

@@ -1199,8 +1199,9 @@ __global__ void __launch_bounds__(CHAIN_THREADS, 2) k_down_chain_dual(SweepArgs<
             wv[u] = reinterpret_cast<const VT *>(da.w)[ivv[u]];
             ypv[u] = reinterpret_cast<const VT *>(da.yprev)[ivv[u]];
             dyv[u] = *reinterpret_cast<const VT *>(da.dy + (size_t)(on[u] ? stage : 0) * ny + cv[u]);
-            blov[u] = *reinterpret_cast<const VT *>(da.blo + cv[u]);
-            bhiv[u] = *reinterpret_cast<const VT *>(da.bhi + cv[u]);
+            const int bc = (on[u] ? stage : 0) * da.bStrideStage + nd * da.bStrideNode + cv[u];
+            blov[u] = *reinterpret_cast<const VT *>(da.blo + bc);
+            bhiv[u] = *reinterpret_cast<const VT *>(da.bhi + bc);
         }
 #pragma unroll
         for (int u = 0; u < U; u++) {

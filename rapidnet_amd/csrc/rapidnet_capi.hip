@@ -27,6 +27,7 @@
 #include "kernels.hpp"
 #include "fbe_kernels.hpp"
 #include "partition.hpp"
+#include "bounds.hpp"
 
 // Every kernel this file launches is compiled in ONE of the units k_stream.hip ... k_fbe.hip; here the instantiations are only declared.
 // (RN_NO_EXTERN_TEMPLATES: the one-unit build tools/gen_instantiations.py uses to find out what is launched.)
@@ -237,6 +238,9 @@ struct CtxBase {
     virtual int get_sweep_pairing(int *, int *) = 0;
     virtual int set_tree_data(size_t, int, bool, const void *, const void *, const void *) = 0;
     virtual int get_tree_data(size_t, double *, double *, double *) = 0;
+    virtual int set_bounds(int, size_t, int, bool, const void *const *) = 0;
+    virtual int get_bounds_layout(int *, size_t *) = 0;
+    virtual int get_bounds(size_t, double *const *) = 0;
     virtual int set_cut_children(const int *, const int *, int, bool, int, int, const double *, const double *) = 0;
     virtual int cut_moments(double *, double *, size_t) = 0;
 };
@@ -436,6 +440,14 @@ struct Ctx : CtxBase {
         hipLaunchKernelGGL(k_hx_scale<T>, dim3(blocks), dim3(ELT_THREADS), 0, stream, d_hx, d_sqrtp, d_dy, d_stageOf, ny, total);
     }
     T *d_lo = nullptr, *d_hi = nullptr, *d_z = nullptr, *d_res = nullptr;
+    // rn_set_bounds: d_blo / d_bhi point at the unscaled table of the granularity in force ([rows][ny]; one table per granularity, allocated by
+    // the first set at that granularity and kept); the element strides by which the kernels find a node's row: k_dual.hpp, DualArgs
+    T *d_bloG[3] = {nullptr, nullptr, nullptr}, *d_bhiG[3] = {nullptr, nullptr, nullptr};
+    int boundsGran = RN_BOUNDS_SHARED;
+    bool keepBounds = false;      // materialise_dense re-runs the factor step: the bounds stay the caller's
+    size_t bounds_rows(int g) const { return bounds::rows_of(g, d.N, d.nodes); }
+    int b_stride_stage() const { int s, n; bounds::strides_of(boundsGran, ny, &s, &n); return s; }
+    int b_stride_node() const { int s, n; bounds::strides_of(boundsGran, ny, &s, &n); return n; }
     T *d_ybuf[2] = {nullptr, nullptr}, *d_wbuf[2] = {nullptr, nullptr};
     T *d_tmp = nullptr;  // nodes*max(2nx,nu) staging for reference-layout get/set
     T *d_cut = nullptr;  // multi-GPU all-reduce payload
@@ -969,7 +981,12 @@ struct Ctx : CtxBase {
         UP(d_Rinv, h_Rinv.data(), nv * nv) UP(d_Bbt, h_Bbt.data(), nv * nx) UP(d_L, s->matL, nu * nv) UP(d_B, s->matB, nx * nu)
         UP(d_Lt, Lt.data(), nv * nu) UP(d_WLt, WLt.data(), nv * nu) UP(d_T1, T1.data(), nv * nx) UP(d_T2, T2.data(), nv * nu)
         UP(d_Gd, s->matGd, nx * nd) UP(d_Lhat, s->matLhat, nu * nd) UP(d_alpha1, s->costAlpha1, nu) UP(d_W, s->costW, nu * nu)
-        UP(d_dy, dy.data(), (size_t)N * ny) UP(d_blo, blo.data(), ny) UP(d_bhi, bhi.data(), ny)
+        UP(d_dy, dy.data(), (size_t)N * ny)
+        if (!keepBounds) {      // back to one row for the whole tree (rn_set_bounds)
+            if (!d_bloG[0]) { d_bloG[0] = d_blo; d_bhiG[0] = d_bhi; }
+            d_blo = d_bloG[0]; d_bhi = d_bhiG[0]; boundsGran = RN_BOUNDS_SHARED;
+            UP(d_blo, blo.data(), ny) UP(d_bhi, bhi.data(), ny)
+        }
 #undef UP
         if (d_Wp) { if (int rc = upload_padded(d_Wp, s->costW, nu, nu)) return rc; }   // k_value_mfma's copy of W (rn_set_algorithm may come before the factor step)
         if (int rc = stream_split_setup()) return rc;
@@ -991,6 +1008,7 @@ struct Ctx : CtxBase {
         ExpandArgs<T> ea{};
         ea.tr = tree_dev(); ea.nx = nx; ea.nu = nu; ea.nv = nv; ea.ny = ny; ea.LD = LD; ea.strideA = strideA; ea.nodes = d.nodes;
         ea.T1 = d_T1; ea.T2 = d_T2; ea.Bbt = d_Bbt; ea.Lt = d_Lt; ea.A = d_A; ea.skipBlocks = structured; ea.blo = d_blo; ea.bhi = d_bhi; ea.lo = d_lo; ea.hi = d_hi;
+        ea.bStrideStage = b_stride_stage(); ea.bStrideNode = b_stride_node();
         const int colChunks = std::min(ny, 8);
         bool expanded = false;
         if constexpr (sizeof(T) == 8) {
@@ -998,6 +1016,7 @@ struct Ctx : CtxBase {
                 ExpandArgs<double, float> ef{};
                 ef.tr = ea.tr; ef.nx = nx; ef.nu = nu; ef.nv = nv; ef.ny = ny; ef.LD = LD; ef.strideA = strideA; ef.nodes = d.nodes;
                 ef.T1 = d_T1; ef.T2 = d_T2; ef.Bbt = d_Bbt; ef.Lt = d_Lt; ef.A = d_A32; ef.skipBlocks = structured; ef.blo = d_blo; ef.bhi = d_bhi; ef.lo = d_lo; ef.hi = d_hi;
+                ef.bStrideStage = ea.bStrideStage; ef.bStrideNode = ea.bStrideNode;
                 hipLaunchKernelGGL((k_expand_operators<double, float>), dim3(d.nodes, colChunks), dim3(LD >= 192 ? 256 : (LD >= 96 ? 128 : 64)), 0, stream, ef);
                 expanded = true;
             }
@@ -1115,7 +1134,8 @@ struct Ctx : CtxBase {
         const double s = sizeof(T), n = d.nodes, sa = block_elem();
         if (bwd) *bwd = structured ? 0.0 : n * ((double)2 * d.nv * ny * sa + (ny + 2.0 * d.nv + d.nx) * s);
         // fused dual update: Hx, w, y+prev read, y+, w_next written (+ the two scaled-bound streams unless they are regenerated)
-        if (dual) *dual = (RN_DUAL_REGEN ? 5.0 : 7.0) * (double)ntot() * s;
+        // (RN_BOUNDS_PER_NODE, rn_set_bounds: the unscaled tables are two streams of their own again)
+        if (dual) *dual = (RN_DUAL_REGEN && boundsGran != RN_BOUNDS_PER_NODE ? 5.0 : 7.0) * (double)ntot() * s;
         return RN_OK;
     }
     int synchronize() override { RN_HIP(hipSetDevice(device)); RN_HIP(hipStreamSynchronize(stream)); return RN_OK; }
@@ -1756,6 +1776,7 @@ struct Ctx : CtxBase {
         if (cutStage > 0) { a.crownElems = h_stageCum[cutStage] * ny; a.countCrown = (rank == 0); }
         a.recN = -1;   // (only the launch that closes a batch publishes a record: run_batch)
         a.regen = RN_DUAL_REGEN; a.stageOf = d_stageOf; a.sqrtp = d_sqrtp; a.dy = d_dy; a.blo = d_blo; a.bhi = d_bhi;
+        a.bStrideStage = b_stride_stage(); a.bStrideNode = b_stride_node();
         return a;
     }
     int lamUploaded = 0;   // leading entries of h_lam that are on the device (kept across restarts: the theta recursion always starts at (1, 1))
@@ -2874,7 +2895,10 @@ struct Ctx : CtxBase {
         structured = 0; splitFirst = -1;      // (the streaming kernel's launch shape is decided by the factor step)
         rn_system sy{h_sys.B.data(), h_sys.Gd.data(), h_sys.L.data(), h_sys.Lhat.data(), h_sys.W.data(), h_sys.diag.data(), h_sys.xmin.data(), h_sys.xmax.data(),
                      h_sys.xsafe.data(), h_sys.umin.data(), h_sys.umax.data(), h_sys.alpha1.data()};
-        if (int rc = factor_step(&sy)) { structured = 1; return rc; }
+        keepBounds = true;
+        const int rcf = factor_step(&sy);
+        keepBounds = false;
+        if (rcf) { structured = 1; return rcf; }
         if (algorithm == RN_ALG_NAMA) return set_algorithm(algorithm, lbfgsSize);   // (its paired sweep needs buffers of its own in dense mode)
         return RN_OK;
     }
@@ -3100,6 +3124,104 @@ struct Ctx : CtxBase {
         if (errP) { if (int rc = download(errP, d_errP, nodes * d.nu)) return rc; }
         return RN_OK;
     }
+    // ---- box and safety bounds per stage or per node in place (rn_set_bounds, rn_set_bounds_device, rn_get_bounds; k_tree_data, k_misc.hpp;
+    // replaces Engine.cuh:294-314 getSysXmin() ... getSysUmax() and Engine.cu preconditionConstraintX/U) ----
+    void bounds_launch(int gran, bool callerF64, const void *const *b) {
+        TreeDataArgs a{};
+        a.ctxF64 = sizeof(T) == 8 ? 1 : 0; a.callerF64 = callerF64 ? 1 : 0;
+        a.nodes = d.nodes; a.nd = d.nd; a.nu = d.nu; a.nx = d.nx; a.ny = ny;
+        for (int i = 0; i < 5; i++) { a.bnd[i] = b[i]; a.bndCopy[i] = d_bnd[i]; }
+        a.bRows = (int)bounds_rows(gran); a.bRowStage = gran == RN_BOUNDS_PER_STAGE ? 1 : 0; a.bRowNode = gran == RN_BOUNDS_PER_NODE ? 1 : 0;
+        a.stageOf = d_stageOf; a.sqrtpIn = d_sqrtp; a.dy = d_dy;
+        a.blo = d_bloG[gran]; a.bhi = d_bhiG[gran]; a.lo = d_lo; a.hi = d_hi;
+        const long long work = (long long)d.nodes * ny;
+        const int blocks = (int)std::max<long long>(1, std::min<long long>(BOUNDS_MAX_BLOCKS, (work + TREE_THREADS - 1) / TREE_THREADS));
+        hipLaunchKernelGGL(k_tree_data<>, dim3(blocks), dim3(TREE_THREADS), 0, stream, a);
+    }
+    int set_bounds(int gran, size_t rows, int callerPrec, bool dev, const void *const *b) override {
+        const std::string what = dev ? "rn_set_bounds_device" : "rn_set_bounds";
+        RN_CHECK(factored, RN_E_STATE, what + " before rn_factor_step");
+        RN_CHECK(bounds::known(gran), RN_E_ARG, what + ": granularity is RN_BOUNDS_SHARED, _PER_STAGE or _PER_NODE");
+        RN_CHECK(callerPrec == RN_F64 || callerPrec == RN_F32, RN_E_ARG, what + ": precision is RN_F32 or RN_F64");
+        RN_CHECK(rows == bounds_rows(gran), RN_E_ARG, what + ": rows must be 1 (shared), dims.N (per stage) or the context's (local) node count (per node)");
+        RN_CHECK(bounds::table_fits(rows, ny), RN_E_ARG, what + ": the table does not fit a 32-bit index");
+        int given = 0;
+        for (int i = 0; i < 5; i++) given += b[i] != nullptr;
+        RN_CHECK(given > 0, RN_E_ARG, what + ": all five arrays are NULL");
+        RN_CHECK(gran == boundsGran || given == 5, RN_E_ARG, what + ": a call that changes the granularity needs all five arrays");
+        RN_HIP(hipSetDevice(device));
+        const int nx = d.nx, nu = d.nu;
+        const size_t elem = callerPrec == RN_F64 ? 8 : 4;
+        const size_t cnt[5] = {rows * nx, rows * nx, rows * nx, rows * nu, rows * nu};
+        const char *shape[5] = {"rows x nx", "rows x nx", "rows x nx", "rows x nu", "rows x nu"};
+        if (dev) {
+            for (int i = 0; i < 5; i++)
+                if (b[i]) { if (int rc = check_device_array(b[i], cnt[i] * elem, elem, what, shape[i])) return rc; }
+        } else {
+            // every value finite, lower <= upper pair by pair; the half of a pair that was not given as the context holds it (bounds.hpp)
+            const double *hb[5], *cur[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+            for (int i = 0; i < 5; i++) hb[i] = static_cast<const double *>(b[i]);
+            bool need[5];
+            bounds::needed_from_context(hb, need);
+            std::vector<double> held[5];
+            if (need[0] || need[1] || need[3] || need[4]) {
+                double *out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+                for (int i = 0; i < 5; i++) if (need[i]) { held[i].resize(cnt[i]); out[i] = held[i].data(); cur[i] = out[i]; }
+                if (int rc = get_bounds(rows, out)) return rc;
+            }
+            const int bad = bounds::validate(rows, nx, nu, hb, cur);
+            RN_CHECK(bad != bounds::NOT_FINITE, RN_E_ARG, what + ": a bound is not finite");
+            RN_CHECK(bad != bounds::XMIN_ABOVE_XMAX, RN_E_ARG, what + ": xmin > xmax");
+            RN_CHECK(bad != bounds::UMIN_ABOVE_UMAX, RN_E_ARG, what + ": umin > umax");
+        }
+        if (!d_bloG[gran]) {      // the first set at this granularity: its table, kept from here on
+            if (int rc = dalloc(&d_bloG[gran], rows * (size_t)ny)) return rc;
+            if (int rc = dalloc(&d_bhiG[gran], rows * (size_t)ny)) return rc;
+        }
+        char *stage = nullptr;
+        if (dev) {
+            bounds_launch(gran, callerPrec == RN_F64, b);
+        } else {   // the same kernel behind a staging copy that lives inside the call (not one of the context's allocations)
+            size_t bytes = 0, at[5] = {0, 0, 0, 0, 0};
+            for (int i = 0; i < 5; i++) if (b[i]) { at[i] = bytes; bytes += (cnt[i] * sizeof(double) + 255) / 256 * 256; }
+            RN_HIP(hipMalloc((void **)&stage, bytes));
+            const void *dv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+            hipError_t e = hipSuccess;
+            for (int i = 0; i < 5 && e == hipSuccess; i++) if (b[i]) {
+                dv[i] = stage + at[i];
+                e = hipMemcpyAsync(stage + at[i], b[i], cnt[i] * sizeof(double), hipMemcpyHostToDevice, stream);
+            }
+            if (e != hipSuccess) { (void)hipStreamSynchronize(stream); (void)hipFree(stage); RN_HIP(e); }
+            bounds_launch(gran, true, dv);
+        }
+        hipError_t e = hipGetLastError();
+        if (!dev) {
+            const hipError_t es = hipStreamSynchronize(stream);    // (before the staging goes: everything that uses it is on this stream)
+            (void)hipFree(stage);
+            if (e == hipSuccess) e = es;
+        }
+        RN_HIP(e);
+        d_blo = d_bloG[gran]; d_bhi = d_bhiG[gran]; boundsGran = gran;
+        return RN_OK;
+    }
+    int get_bounds_layout(int *gran, size_t *rows) override {
+        RN_CHECK(gran && rows, RN_E_ARG, "rn_get_bounds_layout: null output");
+        RN_CHECK(factored, RN_E_STATE, "rn_get_bounds_layout before rn_factor_step");
+        *gran = boundsGran; *rows = bounds_rows(boundsGran);
+        return RN_OK;
+    }
+    int get_bounds(size_t rows, double *const *out) override {
+        RN_CHECK(factored, RN_E_STATE, "rn_get_bounds before rn_factor_step");
+        RN_CHECK(out[0] || out[1] || out[2] || out[3] || out[4], RN_E_ARG, "rn_get_bounds: all five arrays are NULL");
+        RN_CHECK(rows == bounds_rows(boundsGran), RN_E_ARG, "rn_get_bounds: rows must be what rn_get_bounds_layout reports");
+        RN_HIP(hipSetDevice(device));
+        const int nx = d.nx, nu = d.nu;
+        std::vector<double> lo(rows * (size_t)ny), hi(rows * (size_t)ny);
+        if (int rc = download(lo.data(), d_blo, lo.size())) return rc;
+        if (int rc = download(hi.data(), d_bhi, hi.size())) return rc;
+        bounds::unpack_tables(rows, nx, nu, lo.data(), hi.data(), out);
+        return RN_OK;
+    }
     // rn_create_sharded, after the moments: what k_tree_data needs to recompute them (and the full-tree row of every local node)
     int set_cut_children(const int *c0, const int *nc, int nPar, bool contiguous, int cutFirst, int nCutNodes, const double *fullP, const double *fullE) override {
         RN_CHECK(c0 && nc && fullP && nPar > 0 && nCutNodes > 0 && !globalNode.empty(), RN_E_ARG, "set_cut_children: bad input");
@@ -3174,6 +3296,22 @@ int rn_set_tree_errors(rn_ctx *ctx, const double *ed, const double *ep) { RN_GUA
 int rn_set_tree_data(rn_ctx *ctx, size_t nodes, const double *p, const double *ed, const double *ep) { RN_GUARD(ctx); return ctx->impl->set_tree_data(nodes, RN_F64, false, p, ed, ep); }
 int rn_set_tree_data_device(rn_ctx *ctx, size_t nodes, int precision, const void *p, const void *ed, const void *ep) { RN_GUARD(ctx); return ctx->impl->set_tree_data(nodes, precision, true, p, ed, ep); }
 int rn_get_tree_data(rn_ctx *ctx, size_t nodes, double *p, double *ed, double *ep) { RN_GUARD(ctx); return ctx->impl->get_tree_data(nodes, p, ed, ep); }
+int rn_set_bounds(rn_ctx *ctx, int g, size_t rows, const double *xmin, const double *xmax, const double *xsafe, const double *umin, const double *umax) {
+    RN_GUARD(ctx);
+    const void *b[5] = {xmin, xmax, xsafe, umin, umax};
+    return ctx->impl->set_bounds(g, rows, RN_F64, false, b);
+}
+int rn_set_bounds_device(rn_ctx *ctx, int g, size_t rows, int precision, const void *xmin, const void *xmax, const void *xsafe, const void *umin, const void *umax) {
+    RN_GUARD(ctx);
+    const void *b[5] = {xmin, xmax, xsafe, umin, umax};
+    return ctx->impl->set_bounds(g, rows, precision, true, b);
+}
+int rn_get_bounds_layout(rn_ctx *ctx, int *g, size_t *rows) { RN_GUARD(ctx); return ctx->impl->get_bounds_layout(g, rows); }
+int rn_get_bounds(rn_ctx *ctx, size_t rows, double *xmin, double *xmax, double *xsafe, double *umin, double *umax) {
+    RN_GUARD(ctx);
+    double *b[5] = {xmin, xmax, xsafe, umin, umax};
+    return ctx->impl->get_bounds(rows, b);
+}
 int rn_debug_cut_moments(rn_ctx *ctx, double *E, double *P, size_t n) { RN_GUARD(ctx); return ctx->impl->cut_moments(E, P, n); }
 int rn_set_uncertainty(rn_ctx *ctx, int dflag, int pflag, double w) { RN_GUARD(ctx); return ctx->impl->set_uncertainty(dflag, pflag, w); }
 int rn_update_state_control(rn_ctx *ctx, const double *x, const double *u, const double *dm) { RN_GUARD(ctx); return ctx->impl->update_state_control(x, u, dm); }
