@@ -60,9 +60,10 @@
             DA(d_lsEval, (size_t)ELT_MAX_BLOCKS * LS_K * LS_EVAL) DA(d_lsVal, (size_t)lsValueBlocks * LS_K * 2) DA(d_lsScal, LS_K * LS_SCAL)
 #undef DA
             {   // the candidates' du tiles in LDS: [LS_K][nu][LS_TILE]; more than 64 KB needs the function attribute, more than the CU has: sequential search
+                // (the attribute asks for what the tile needs: the kernel's static arrays share the CU's 160 KB, so asking for all of it is refused)
                 const size_t ldsLs = (size_t)LS_K * d.nu * LS_TILE * sizeof(T);
                 lsFused = ldsLs <= 160 * 1024 &&
-                          (ldsLs <= 64 * 1024 || hipFuncSetAttribute((const void *)k_ls_value<T>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess);
+                          (ldsLs <= 64 * 1024 || hipFuncSetAttribute((const void *)k_ls_value<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsLs) == hipSuccess);
                 (void)hipGetLastError();
                 if (knob[RN_KNOB_LS_SEQUENTIAL] > 0) lsFused = false;   // A/B runs, tests: the trial-by-trial search
             }

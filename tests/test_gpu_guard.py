@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import test_gpu_fbe_nama as fbe
+import test_gpu_fbe_nama_f32 as f32
 import test_gpu_parity as par
 import test_gpu_sharded_batched as shb
 import test_gpu_stream_split as spl
@@ -101,6 +102,13 @@ def test_fbe_nama_loops_under_guard(guard, alg):
     fbe.test_loop_matches_oracle("medium", True, alg)
     fbe.test_line_search_direction_rule(alg, "positive")
     guard["contexts"] = 4
+
+
+@pytest.mark.parametrize("alg", fbe.ALGS)
+def test_f32_direction_and_line_search_under_guard(guard, alg):
+    """the fp32 element kernels on `odd` (n = 891 = 3 mod 4): the scalar walks of L-BFGS columns that start off a 16-byte boundary and the
+    tails behind the vector bodies are where a store one element past n would land in a red zone"""
+    guard["contexts"] = f32.guard_body(alg)
 
 
 @pytest.mark.parametrize("cases", [(("b236", "three", "f64"), ("nv129", "two", "f64"))])
