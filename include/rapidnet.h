@@ -417,7 +417,8 @@ int rn_profile_read_collective(rn_ctx *ctx, double *ms, long *launches);
 int rn_algorithmic_bytes(const rn_ctx *ctx, double *backwardStageBytesTotal, double *dualUpdateBytes);
 /* which kernels an iteration of this context launches: info = {1 if k_dual_stage is the main pass of the fused dual update
  * (0: the flat k_dual_fused), its workgroups, vectors per thread, pipeline depth, k_stream_gemv columns per span, slots per
- * thread and span, first chain stage c*, 1 if the v / Lv products run as the fused slab kernel k_gemm_vlv} */
+ * thread and span, first chain stage c*, 1 if the v / Lv products run as the fused slab kernel k_gemm_vlv -- 2 or 3 once a sweep
+ * has chosen k_gemm_vlv_wide with that many slabs per workgroup} */
 int rn_get_kernel_info(rn_ctx *ctx, int info[8]);
 /* streaming ceilings of THIS device measured with do-nothing kernels (16 B per lane per load, non-temporal): flat
  * grid-stride read-only GB/s and copy GB/s (read + written bytes), best of `reps` passes over `bytes`.

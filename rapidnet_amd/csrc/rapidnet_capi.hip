@@ -2341,7 +2341,7 @@ struct Ctx : CtxBase {
         out[3] = dualU;                                  // 2: double-buffered variant
         out[4] = G; out[5] = NL;                         // k_stream_gemv: columns per span, 16-byte slots per thread and span
         out[6] = chainStage;
-        out[7] = v_lv_is_slab() ? 1 : 0;                 // 1: k_gemm_vlv (slab), 0: two k_gemm_shared launches
+        out[7] = v_lv_is_slab() ? (wideCt >= 2 ? wideCt : 1) : 0;   // 1: k_gemm_vlv (slab), 0: two k_gemm_shared launches; 2 / 3: a sweep has chosen k_gemm_vlv_wide with that many slabs per workgroup
         return RN_OK;
     }
     // rn_debug_stream_info (include/rapidnet_debug.h): what stream_split_setup() decided, for the tests of the split last round

@@ -11,6 +11,7 @@ import gc
 import numpy as np
 import pytest
 
+import test_gpu_apg_f32 as apg32
 import test_gpu_fbe_nama as fbe
 import test_gpu_fbe_nama_f32 as f32
 import test_gpu_parity as par
@@ -109,6 +110,13 @@ def test_f32_direction_and_line_search_under_guard(guard, alg):
     """the fp32 element kernels on `odd` (n = 891 = 3 mod 4): the scalar walks of L-BFGS columns that start off a 16-byte boundary and the
     tails behind the vector bodies are where a store one element past n would land in a red zone"""
     guard["contexts"] = f32.guard_body(alg)
+
+
+def test_f32_apg_batches_under_guard(guard):
+    """the fp32 APG kernels on `small` (n = 1330 = 2 mod 4), dense and structured: one exact iteration and one optimistic batch of 16 from each
+    of the fp64 loop's fp32-rounded states -- the re-derived w behind rn_set, the checkpoint copies and the batch close are where a vector
+    body's last store or a tail would land in a red zone"""
+    guard["contexts"] = apg32.guard_body()
 
 
 @pytest.mark.parametrize("cases", [(("b236", "three", "f64"), ("nv129", "two", "f64"))])
