@@ -279,6 +279,24 @@ int rn_get_stop_tolerance(rn_ctx *ctx, double *tol, int *checkEvery);
  * residuals of :1480-1496): out = {iterations it ran, 1 if it stopped on the tolerance, first iteration (0-based, within that solve) whose
  * residual was <= tol or -1 (also -1 when no tolerance was set), batches run}. */
 int rn_get_last_solve(rn_ctx *ctx, long out[4]);
+/* Extension: adaptive restart of the momentum (O'Donoghue & Candes, gradient scheme).  The reference's theta recursion runs on for the whole
+ * solve (SmpcController.cu:1500-1525; the extrapolation it feeds: :535-557).  With RN_RESTART_GRADIENT, rn_apg_solve, rn_algorithm_apg and
+ * rn_control_action run their iterations in batches of checkEvery (rn_apg_solve's argument; rn_set_stop_tolerance's for the other two,
+ * default 20 -- a tolerance of 0 is allowed: restart without an early stop) and, at every batch end, behind the tolerance check (a solve that
+ * stops does not restart), one kernel evaluates g = <w_k - y_{k+1}, y_{k+1} - y_k> over the whole tree, summed in fp64 in a fixed order.
+ * g > 0: y := y_{k+1}, the next extrapolation starts the theta sequence again at {1, 1}; the iteration count, the residual history,
+ * rn_get_last_solve and the batch counters carry on.  A batch replayed through the exact path is judged on the replay; on a sharded
+ * context every rank holds the same bits of g and takes the same decision.  RN_RESTART_OFF (the default): nothing is launched or allocated,
+ * every solve is the reference's, bit for bit.  rn_algorithm_fbe_nama ignores the setting.  Any other mode: RN_E_ARG. */
+enum { RN_RESTART_OFF = 0, RN_RESTART_GRADIENT = 1 };
+int rn_set_restart(rn_ctx *ctx, int mode);
+/* the setting of rn_set_restart (SmpcController.cu:1500-1525, :535-557); mode NULL: RN_E_ARG */
+int rn_get_restart(rn_ctx *ctx, int *mode);
+/* Of the last rn_apg_solve / rn_algorithm_apg / rn_control_action under RN_RESTART_GRADIENT (the loop of SmpcController.cu:1500-1525, the
+ * extrapolation of :535-557): counts = {restarts, iteration count at the last restart or -1, batch ends tested, 0}; last = {g, na2, nb2} of
+ * the last test, na2 = |w_k - y_{k+1}|^2, nb2 = |y_{k+1} - y_k|^2 (g / sqrt(na2 nb2) is the cosine: how marginal the decision was).  With the
+ * mode off: {0, -1, 0, 0} and zeros.  Either pointer NULL: RN_E_ARG. */
+int rn_get_restart_info(rn_ctx *ctx, long counts[4], double last[3]);
 /* SmpcController::controlAction(real_t*) (SmpcController.cu:1607-1625): update state, eliminate, APG, copy u of the root node
  * (nu reals) to the host.  The reference's leak check around these calls (cudaMemGetInfo before and after, :1612-1623) is the
  * caller's, with rn_device_memory_info below -- the host class SmpcController::controlAction does exactly that. */

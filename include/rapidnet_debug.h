@@ -77,6 +77,11 @@ int rn_debug_set_knob(rn_ctx *ctx, int knob, int value);
  * per CU.  numCUs: the device's compute units, valid from rn_create on.  Reads only: nothing that is computed changes. */
 int rn_debug_stream_info(rn_ctx *ctx, int info[4]);
 
+/* The gradient restart test (rn_set_restart, rapidnet.h) alone: runs k_restart_test on the context's current w (the last sweep's input, what
+ * RN_BUF_ACC_* shows), y+ and y and returns out = {g, na2, nb2} -- the kernel can be checked without running a solve.  Allocates the kernel's
+ * partials on first use; changes no iterate.  On a sharded context every rank calls it (it contains the ranks' all-reduce). */
+int rn_debug_restart_test(rn_ctx *ctx, double out[3]);
+
 /* The children moments of the cut parents as the context holds them (rn_set_cut_children_moments, or recomputed by rn_set_tree_data on a
  * context made by rn_create_sharded): E [nParents][nd], P [nParents], widened from the context's type.  RN_E_STATE while none are set. */
 int rn_debug_cut_moments(rn_ctx *ctx, double *E, double *P, size_t nParents);

@@ -162,6 +162,7 @@ TEST_OPERATOR_BULK = os.path.join(BIN_DIR, "test_operator_bulk")
 TEST_STOP_TOLERANCE = os.path.join(BIN_DIR, "test_stop_tolerance")
 TEST_TREE_DATA = os.path.join(BIN_DIR, "test_tree_data")
 TEST_BOUNDS = os.path.join(BIN_DIR, "test_bounds")
+TEST_RESTART = os.path.join(BIN_DIR, "test_restart")
 
 
 def build_host(force=False):
@@ -211,6 +212,11 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_BOUNDS, test_src, "-L" + HERE, "-lrapidnet_host",
                                "-lrapidnet_hip", "-ldl", "-Wl,-rpath,$ORIGIN/.."])
         _stamp(TEST_BOUNDS, [test_src] + deps + hdr)
+    test_src = os.path.join(ROOT, "tests", "cpp", "test_restart.cpp")
+    if force or _stale(TEST_RESTART, [test_src] + deps + hdr):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_RESTART, test_src, "-L" + HERE, "-lrapidnet_host",
+                               "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
+        _stamp(TEST_RESTART, [test_src] + deps + hdr)
     return LIB_HOST
 
 

@@ -25,6 +25,8 @@ STORE_NATIVE, STORE_F32 = 0, 1
 STORAGES = {"native": STORE_NATIVE, "f32": STORE_F32}
 PAIR_OFF, PAIR_ON, PAIR_AUTO = 0, 1, 2
 PAIRINGS = {"off": PAIR_OFF, "on": PAIR_ON, "auto": PAIR_AUTO}
+RESTART_OFF, RESTART_GRADIENT = 0, 1   # rn_set_restart
+RESTARTS = {"off": RESTART_OFF, "gradient": RESTART_GRADIENT}
 BOUNDS_SHARED, BOUNDS_PER_STAGE, BOUNDS_PER_NODE = 0, 1, 2      # rn_set_bounds
 BOUNDS = {"shared": BOUNDS_SHARED, "stage": BOUNDS_PER_STAGE, "node": BOUNDS_PER_NODE}
 # include/rapidnet_debug.h, RN_KNOB_*
@@ -36,7 +38,7 @@ EXCHANGE_COLLECTIVE, EXCHANGE_ONESHOT, EXCHANGE_AUTO = 0, 1, 2
 SYMBOLS = [
     "rn_create", "rn_destroy", "rn_last_error", "rn_synchronize", "rn_factor_step", "rn_set_tree_errors",
     "rn_set_uncertainty", "rn_update_state_control", "rn_eliminate_input_disturbance_coupling", "rn_set_parameters",
-    "rn_apg_reset", "rn_apg_iterate", "rn_algorithm_apg", "rn_apg_solve", "rn_set_stop_tolerance", "rn_get_stop_tolerance", "rn_get_last_solve", "rn_control_action", "rn_dual_extrapolation_step",
+    "rn_apg_reset", "rn_apg_iterate", "rn_algorithm_apg", "rn_apg_solve", "rn_set_stop_tolerance", "rn_get_stop_tolerance", "rn_get_last_solve", "rn_set_restart", "rn_get_restart", "rn_get_restart_info", "rn_control_action", "rn_dual_extrapolation_step",
     "rn_solve_step", "rn_proximal_fun_g", "rn_compute_fixed_point_residual", "rn_dual_update",
     "rn_update_primal_infeasibility", "rn_get_prox_distances", "rn_buffer_size", "rn_get", "rn_set", "rn_get_operator",
     "rn_device_pointer", "rn_profile_enable", "rn_profile_reset", "rn_profile_read", "rn_algorithmic_bytes", "rn_stream",
@@ -49,7 +51,7 @@ SYMBOLS = [
     "rn_debug_set_allreduce", "rn_debug_local_group_create", "rn_debug_local_group_join", "rn_debug_local_group_destroy",
     "rn_guard_check", "rn_device_memory_info", "rn_reserve_iterations", "rn_profile_read_collective", "rn_debug_inject_allocation", "rn_guard_report", "rn_debug_guard_poke",
     "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_set_bounds", "rn_set_bounds_device", "rn_get_bounds_layout", "rn_get_bounds", "rn_debug_cut_moments",
-    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info",
+    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test",
 ]
 
 
@@ -153,6 +155,10 @@ def load():
     lib.rn_set_stop_tolerance.argtypes = [vp, C.c_double, ip]
     lib.rn_get_stop_tolerance.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     lib.rn_get_last_solve.argtypes = [vp, dp]
+    lib.rn_set_restart.argtypes = [vp, ip]
+    lib.rn_get_restart.argtypes = [vp, C.POINTER(C.c_int)]
+    lib.rn_get_restart_info.argtypes = [vp, dp, dp]
+    lib.rn_debug_restart_test.argtypes = [vp, dp]
     lib.rn_control_action.argtypes = [vp, dp, dp, dp, dp, dp, ip, ip, dp]
     lib.rn_dual_extrapolation_step.argtypes = [vp, C.c_double]
     for f in ("rn_solve_step", "rn_proximal_fun_g", "rn_compute_fixed_point_residual", "rn_dual_update"):
@@ -275,7 +281,7 @@ class Solver:
 
     def __init__(self, network, tree, config, precision="f64", device=0, structured=False, rank=0, nranks=1, cut_stage=0,
                  unique_id=None, knobs=None, operator_mode=None, operator_storage="native", sweep_pairing="auto", stop_tolerance=0.0,
-                 stop_check_every=0):
+                 stop_check_every=0, restart="off"):
         """nranks > 1: `tree` is the FULL scenario tree and the context is rank `rank`'s shard of it (rn_create_sharded:
         partition, communicator from `unique_id` -- None = none, the exchange is a test's job --, cut stage, children
         moments); self.nodes is then the LOCAL node count and self.global_nodes maps local -> full-tree node ids.
@@ -286,7 +292,9 @@ class Solver:
         sweep_pairing: "auto" | "on" | "off" (rn_set_sweep_pairing): NAMA's two Hessian sweeps in one pass over the dense blocks; "on" adds
         fp32-stored blocks to what "auto" pairs.
         stop_tolerance, stop_check_every (rn_set_stop_tolerance): with a tolerance > 0 controlAction and algorithmApg end once the residual of
-        the last iteration of a batch of stop_check_every iterations (0: the library's default, 20) is <= stop_tolerance; 0: fixed count."""
+        the last iteration of a batch of stop_check_every iterations (0: the library's default, 20) is <= stop_tolerance; 0: fixed count.
+        restart: "off" | "gradient" (rn_set_restart): the gradient test at every batch end restarts the momentum of apg_solve, algorithmApg and
+        controlAction."""
         self.lib = load()
         self.structured = bool(structured)
         self.network, self.tree, self.config = network, tree, config
@@ -327,6 +335,8 @@ class Solver:
             self._check(self.lib.rn_set_sweep_pairing(self.h, PAIRINGS[sweep_pairing]))
         if stop_tolerance or stop_check_every:      # (a context that never asks for it makes exactly the calls it always made)
             self.setStopTolerance(stop_tolerance, stop_check_every)
+        if restart != "off":
+            self.setRestart(restart)
         for k, v in (knobs or {}).items():
             self.debugSetKnob(k, v)
 
@@ -412,6 +422,27 @@ class Solver:
         t, e = C.c_double(0), C.c_int(0)
         self._check(self.lib.rn_get_stop_tolerance(self.h, C.byref(t), C.byref(e)))
         return t.value, e.value
+
+    def setRestart(self, mode):
+        """rn_set_restart: "off" | "gradient" (or the RN_RESTART_* value)"""
+        self._check(self.lib.rn_set_restart(self.h, RESTARTS[mode] if isinstance(mode, str) else int(mode)))
+
+    def restart(self):
+        m = C.c_int(0)
+        self._check(self.lib.rn_get_restart(self.h, C.byref(m)))
+        return {v: k for k, v in RESTARTS.items()}[m.value]
+
+    def last_restarts(self):
+        """rn_get_restart_info: dict(restarts, last_at, tested, g, na2, nb2) of the last apg_solve / algorithmApg / controlAction"""
+        cnt, last = np.zeros(4, dtype=np.int64), np.zeros(3)
+        self._check(self.lib.rn_get_restart_info(self.h, cnt.ctypes.data, last.ctypes.data))
+        return dict(restarts=int(cnt[0]), last_at=int(cnt[1]), tested=int(cnt[2]), g=float(last[0]), na2=float(last[1]), nb2=float(last[2]))
+
+    def debugRestartTest(self):
+        """rn_debug_restart_test (include/rapidnet_debug.h): (g, na2, nb2) of the gradient restart test on the current w, y+, y"""
+        out = np.zeros(3)
+        self._check(self.lib.rn_debug_restart_test(self.h, out.ctypes.data))
+        return tuple(float(v) for v in out)
 
     def last_solve(self):
         """rn_get_last_solve: dict(iterations, stopped, first_below, batches) of the last apg_solve / algorithmApg / controlAction"""

@@ -37,11 +37,14 @@ struct TreeDev {
 };
 
 // What the launch that closes an rn_apg_iterate batch publishes for the host (which decides, behind the synchronisation it has anyway,
-// whether the solve goes on: rn_apg_solve, rn_set_stop_tolerance): 16 bytes, in IterState and -- single GPU -- in a host-mapped copy.
+// whether the solve goes on: rn_apg_solve, rn_set_stop_tolerance; whether the momentum is restarted: rn_set_restart): 40 bytes, in IterState
+// and -- single GPU -- in a host-mapped copy.
 struct BatchRecord {
     int verdict;           // optimistic batch: a tree-global distance exceeded its threshold (the batch is replayed); exact batch: 0
     int firstBelow;        // first iteration OF THIS BATCH (0-based within it) whose residual was <= the tolerance handed to the launch, or -1
     double lastResidual;   // vecPrimalInfs of the batch's last iteration (SmpcController.cu:1521)
+    // the gradient restart test at the batch's end (k_restart_test, k_dual.hpp; written only when rn_set_restart asked for it):
+    double g, na2, nb2;    // <w_k - y_{k+1}, y_{k+1} - y_k>, |w_k - y_{k+1}|^2, |y_{k+1} - y_k|^2
 };
 
 struct IterState {         // device-resident scalars of the APG loop

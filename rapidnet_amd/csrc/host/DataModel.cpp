@@ -187,6 +187,14 @@ SmpcConfiguration::SmpcConfiguration(string pathToFile) {
         if (sweepPairing != "auto" && sweepPairing != "on" && sweepPairing != "off")
             throw std::logic_error("controller configuration: sweepPairing must be \"auto\", \"on\" or \"off\" (got \"" + sweepPairing + "\")");
     }
+    // ... and whether the gradient test restarts the momentum of the APG solve at its batch ends (absent = "off": rapidnet.h, rn_set_restart)
+    momentumRestart = "off";
+    if (doc.HasMember("momentumRestart")) {
+        _ASSERT(doc["momentumRestart"].IsString());
+        momentumRestart = doc["momentumRestart"].str;
+        if (momentumRestart != "off" && momentumRestart != "gradient")
+            throw std::logic_error("controller configuration: momentumRestart must be \"off\" or \"gradient\" (got \"" + momentumRestart + "\")");
+    }
     // ... and whether the APG solve of a control step ends on a residual tolerance (absent = 0: the reference's fixed maxIterations; rapidnet.h,
     // rn_set_stop_tolerance), checked every stopCheckEvery iterations (absent = 0: the library's default)
     stopTolerance = 0;

@@ -137,6 +137,8 @@ public:
     // the library's default batch length -- Engine.hpp, setStopTolerance
     real_t getStopTolerance() { return stopTolerance; }
     uint_t getStopCheckEvery() { return stopCheckEvery; }
+    // "momentumRestart" (optional key, not in the reference's files): "off" (default) or "gradient" -- Engine.hpp, setRestart
+    string getMomentumRestart() { return momentumRestart; }
     void setCurrentState();     // re-read from the configuration file (SmpcConfiguration.cu:240-256)
     void setPreviousControl();  // :261-277
     void setPreviousDemand();   // :283-299
@@ -149,7 +151,7 @@ private:
     uint_t NX, NU, ND, NV, lbfgsBufferSize, maxIteration, stopCheckEvery;
     std::vector<real_t> matL, matLhat, matCostW, matDiagPrecnd, currentX, prevU, prevDemand;
     real_t penaltyStateX, penaltySafetyX, stepSize, weightPrice, weightSmooth, weightSafety, stopTolerance;
-    string pathToConfiguration, pathToNetwork, pathToScenarioTree, pathToForecaster, algorithmName, operatorMode, operatorStorage, sweepPairing;
+    string pathToConfiguration, pathToNetwork, pathToScenarioTree, pathToForecaster, algorithmName, operatorMode, operatorStorage, sweepPairing, momentumRestart;
 };
 
 #endif

@@ -61,6 +61,12 @@ real_t Engine::getStopTolerance(int *checkEvery) {
     check(rn_get_stop_tolerance(ctx, &tol, checkEvery), "rn_get_stop_tolerance");
     return tol;
 }
+void Engine::setRestart(int mode) { check(rn_set_restart(ctx, mode), "rn_set_restart"); }
+int Engine::getRestart() {
+    int mode = RN_RESTART_OFF;
+    check(rn_get_restart(ctx, &mode), "rn_get_restart");
+    return mode;
+}
 void Engine::setSweepPairing(int mode) { check(rn_set_sweep_pairing(ctx, mode), "rn_set_sweep_pairing"); }
 int Engine::getSweepPairing(int *active) {
     int requested = RN_PAIR_AUTO;
@@ -146,6 +152,7 @@ void Engine::create(int precision, int device, int operatorMode, int rank, int n
     }
     if (ptrMySmpcConfig->getStopTolerance() > 0)   // (a file without the key makes exactly the calls it always made)
         check(rn_set_stop_tolerance(ctx, ptrMySmpcConfig->getStopTolerance(), (int)ptrMySmpcConfig->getStopCheckEvery()), "rn_set_stop_tolerance");
+    if (ptrMySmpcConfig->getMomentumRestart() == "gradient") check(rn_set_restart(ctx, RN_RESTART_GRADIENT), "rn_set_restart");
     // SmpcController::allocateApgAlgorithm (SmpcController.cu:124-151): per-iteration storage for maxIterations, allocated once
     check(rn_reserve_iterations(ctx, (int)ptrMySmpcConfig->getMaxIterations()), "rn_reserve_iterations");
     if (!apgFlag)   // SmpcController::allocateGlobalFbeAlgorithm / allocateNamaAlgorithm / allocateLbfgsBuffer (SmpcController.cu:234-330)

@@ -52,6 +52,12 @@ public:
     // "stopCheckEvery" keys (absent: off).  At any time; the quasi-Newton loops ignore it.
     void setStopTolerance(real_t tol, int checkEvery = 0);
     real_t getStopTolerance(int *checkEvery = nullptr);
+    // adaptive restart of the APG momentum (rapidnet.h, rn_set_restart; the reference's theta recursion is never restarted,
+    // SmpcController.cu:1500-1525, :535-557): RN_RESTART_OFF (the default) or RN_RESTART_GRADIENT -- the solve of a control step then runs in
+    // batches of the stop tolerance's checkEvery iterations and the gradient test at every batch end decides.  The constructors take it from
+    // the configuration file's optional "momentumRestart" key ("off" | "gradient"; absent: off).  At any time; the quasi-Newton loops ignore it.
+    void setRestart(int mode);
+    int getRestart();
     int getSweepPairing(int *active = nullptr);      // what was asked for; *active: 1 when the next NAMA line search would run the pair
     // a per-node block handed in by the caller (the reference: write through getMatPhi() / getPtrMatPhi()[node] ..., Engine.cuh:170-230);
     // RN_OP_PHI, _PSI, _D, _F, col-major nv x (2nx | nu); after factorStep()

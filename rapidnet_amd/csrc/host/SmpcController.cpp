@@ -78,6 +78,12 @@ uint_t SmpcController::getIterationsRun() {
     check(rn_get_last_solve(ptrMyEngine->getContext(), out), "rn_get_last_solve");
     return (uint_t)out[0];
 }
+uint_t SmpcController::getRestartsRun() {
+    long counts[4] = {0, -1, 0, 0};
+    double last[3] = {0, 0, 0};
+    check(rn_get_restart_info(ptrMyEngine->getContext(), counts, last), "rn_get_restart_info");
+    return (uint_t)counts[0];
+}
 uint_t SmpcController::controlAction(real_t *u) {
     if (!factorStepFlag) { ptrMyEngine->factorStep(); factorStepFlag = true; }
     size_t before[4];

@@ -51,6 +51,9 @@ public:
     // iterations the last APG solve (controlAction, algorithmApg) ran: maxIterations unless Engine::setStopTolerance / the configuration's
     // "stopTolerance" ended it earlier (rapidnet.h, rn_get_last_solve)
     uint_t getIterationsRun();
+    // momentum restarts of the last APG solve (controlAction, algorithmApg): 0 unless Engine::setRestart / the configuration's
+    // "momentumRestart": "gradient" asked for the gradient test (rapidnet.h, rn_get_restart_info)
+    uint_t getRestartsRun();
     real_t *getValueFbe() { return vecValueFbe.data(); }    // :1883
     real_t *getVecTau() { return vecTau.data(); }
     ~SmpcController();

@@ -101,7 +101,9 @@ __device__ __forceinline__ void write_history(const Partial &p, int it, double *
 // iteration state and, where the host mapped one, into the host's copy (system-scope stores: the host reads them behind its stream
 // synchronisation, without a device-to-host copy of its own).
 __device__ __forceinline__ void store_batch_record(int verdict, int firstBelow, double last, IterState *st, BatchRecord *host) {
-    st->rec = BatchRecord{verdict, firstBelow, last};
+    // only the closing launch's own three fields: g, na2, nb2 belong to k_restart_test, which runs behind this launch on the same stream (when
+    // rn_set_restart asked for it) -- neither launch depends on what the other stores, in whichever order they run
+    st->rec.verdict = verdict; st->rec.firstBelow = firstBelow; st->rec.lastResidual = last;
     if (host != nullptr) {
         unsigned long long *w = reinterpret_cast<unsigned long long *>(host);
         __hip_atomic_store(w, (unsigned long long)(unsigned int)verdict | ((unsigned long long)(unsigned int)firstBelow << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -738,5 +740,109 @@ __global__ void __launch_bounds__(ELT_THREADS) k_batch_open(const T *y0, const T
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// Gradient test of the adaptive momentum restart (O'Donoghue & Candes; rn_set_restart, run once per batch behind its closing launch -- the
+// reference's theta recursion, SmpcController.cu:1500-1525 and :535-557, is never restarted):
+//   g = <w_k - y_{k+1}, y_{k+1} - y_k>,  na2 = |w_k - y_{k+1}|^2,  nb2 = |y_{k+1} - y_k|^2
+// in ONE flat pass over the three vectors ([node][ny], 16 bytes per lane and stream).  Every product is formed and summed in double whatever T
+// is, in a fixed order -- a lane over its grid-stride positions, the wave (wave_sum_f64), the workgroup's waves in LDS, the workgroups'
+// partials by the workgroup that arrives last (agent-scope release -> ticket -> acquire; 256 lanes over the partials, then wave and LDS
+// as before) -- so the same iterates give the same bits on every run: no floating-point atomics.  Sharded contexts: the leading crownElems
+// elements are replicated on every rank; they are summed apart from the rank's own subtree rows and added on ONE rank (countCrown), so the
+// sum over the ranks counts them once.  The result goes into the batch record (common.hpp) and its host-mapped copy, beside lastResidual.
+// The element type arrives as a flag and not as a template parameter (one kernel instead of two, as k_pack_operators and k_tree_data do); the
+// branch is uniform over the grid.
+struct RestartArgs {
+    const void *w, *yp, *y;    // w_k (the last sweep's input), y_{k+1}, y_k: doubles (f64) or floats
+    int f64;
+    long long n, crownElems;
+    int countCrown;
+    double *partials;          // [gridDim.x][6]: subtree (g, na2, nb2), crown (g, na2, nb2)
+    unsigned int *ticket;      // arrival counter: the host zeroes it on the stream in front of every launch (the kernel leaves it at gridDim.x)
+    IterState *st;
+    BatchRecord *hostRec;      // host-mapped copy (nullptr: none)
+};
+// a lane's sums over its grid-stride positions of the flat range, elements of type T
+template <typename T>
+__device__ __forceinline__ void restart_lane_sums(const RestartArgs &a, double &sg, double &sa, double &sb, double &cg, double &ca, double &cb) {
+    typedef typename VecOf<T>::type VT;
+    constexpr int VN = VecOf<T>::N;
+    const T *aw = reinterpret_cast<const T *>(a.w), *ayp = reinterpret_cast<const T *>(a.yp), *ay = reinterpret_cast<const T *>(a.y);
+    const long long stride = (long long)gridDim.x * ELT_THREADS;
+    const long long gid = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    const long long nvec = a.n / VN;
+    for (long long iv = gid; iv < nvec; iv += stride) {
+        const VT w = reinterpret_cast<const VT *>(aw)[iv], yp = reinterpret_cast<const VT *>(ayp)[iv], y = reinterpret_cast<const VT *>(ay)[iv];
+#pragma unroll
+        for (int e = 0; e < VN; e++) {
+            const double d1 = (double)w[e] - (double)yp[e], d2 = (double)yp[e] - (double)y[e];
+            const bool crown = iv * VN + e < a.crownElems;
+            const double tg = d1 * d2, ta = d1 * d1, tb = d2 * d2;
+            sg += crown ? 0.0 : tg; sa += crown ? 0.0 : ta; sb += crown ? 0.0 : tb;
+            cg += crown ? tg : 0.0; ca += crown ? ta : 0.0; cb += crown ? tb : 0.0;
+        }
+    }
+    for (long long i = nvec * VN + gid; i < a.n; i += stride) {   // at most VN-1 tail elements
+        const double d1 = (double)aw[i] - (double)ayp[i], d2 = (double)ayp[i] - (double)ay[i];
+        const bool crown = i < a.crownElems;
+        const double tg = d1 * d2, ta = d1 * d1, tb = d2 * d2;
+        sg += crown ? 0.0 : tg; sa += crown ? 0.0 : ta; sb += crown ? 0.0 : tb;
+        cg += crown ? tg : 0.0; ca += crown ? ta : 0.0; cb += crown ? tb : 0.0;
+    }
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void __launch_bounds__(ELT_THREADS) k_restart_test(RestartArgs a) {
+    constexpr int NW = ELT_THREADS / 64, FLAG = NW * 6;
+    __shared__ double sh[NW * 6 + 1];   // the waves' sums; sh[FLAG] != 0: this workgroup arrived last
+    double sg = 0, sa = 0, sb = 0, cg = 0, ca = 0, cb = 0;
+    if (a.f64) restart_lane_sums<double>(a, sg, sa, sb, cg, ca, cb); else restart_lane_sums<float>(a, sg, sa, sb, cg, ca, cb);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    sg = wave_sum_f64(sg); sa = wave_sum_f64(sa); sb = wave_sum_f64(sb);
+    cg = wave_sum_f64(cg); ca = wave_sum_f64(ca); cb = wave_sum_f64(cb);
+    if (lane == 0) { double *q = sh + wave * 6; q[0] = sg; q[1] = sa; q[2] = sb; q[3] = cg; q[4] = ca; q[5] = cb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double *out = a.partials + (size_t)blockIdx.x * 6;
+        for (int k = 0; k < 6; k++) {
+            double t = sh[k];
+            for (int v = 1; v < NW; v++) t += sh[v * 6 + k];
+            out[k] = t;
+        }
+        // publish the partial, then draw a ticket: the last arriver folds (release -> ticket -> acquire, as the fix-up launch of k_dual_fused)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned int t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool last = t == gridDim.x - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        sh[FLAG] = last ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    if (sh[FLAG] == 0.0) return;
+    sg = sa = sb = cg = ca = cb = 0;
+    for (unsigned int b = threadIdx.x; b < gridDim.x; b += ELT_THREADS) {   // ascending per lane: a fixed order
+        const double *q = a.partials + (size_t)b * 6;
+        sg += q[0]; sa += q[1]; sb += q[2]; cg += q[3]; ca += q[4]; cb += q[5];
+    }
+    sg = wave_sum_f64(sg); sa = wave_sum_f64(sa); sb = wave_sum_f64(sb);
+    cg = wave_sum_f64(cg); ca = wave_sum_f64(ca); cb = wave_sum_f64(cb);
+    if (lane == 0) { double *q = sh + wave * 6; q[0] = sg; q[1] = sa; q[2] = sb; q[3] = cg; q[4] = ca; q[5] = cb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double r[3];
+        for (int k = 0; k < 3; k++) {
+            double s = sh[k], c = sh[3 + k];
+            for (int v = 1; v < NW; v++) { s += sh[v * 6 + k]; c += sh[v * 6 + 3 + k]; }
+            r[k] = a.countCrown ? c + s : s;
+        }
+        a.st->rec.g = r[0]; a.st->rec.na2 = r[1]; a.st->rec.nb2 = r[2];
+        if (a.hostRec != nullptr) {
+            unsigned long long *hw = reinterpret_cast<unsigned long long *>(a.hostRec);
+            for (int k = 0; k < 3; k++) __hip_atomic_store(hw + 2 + k, (unsigned long long)__double_as_longlong(r[k]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+}
 
 }  // namespace rn

@@ -89,14 +89,15 @@ __global__ void k_expand_operators(ExpandArgs<T, S> a) {
 // the caller's side is contiguous per array; it is read 16 B wide where a slot's entries lie in one array at a 16-byte boundary, entry by
 // entry otherwise (still coalesced).  Non-temporal both ways, as the copy loop of k_bw_probe.  Launch: blockIdx.x strides the slots of one node, blockIdx.y
 // the nodes -- numCUs * 4 workgroups in all, the shape rn_measure_hbm found best for a read + write stream.
-// The element types arrive as flags and not as template parameters: the four (caller, stored) pairs in two directions would be eight
-// kernels; the branch is uniform over the grid.
+// The element types and the direction arrive as flags and not as template parameters: the four (caller, stored) pairs in two directions
+// would be eight kernels; the branches are uniform over the grid.
 struct PackOpsArgs {
     void *A;              // the blocks, doubles or floats (storedF64), first node of the range
     size_t strideA;       // in stored entries
     void *op[4];          // caller's phi, psi, D, F: doubles or floats (callerF64), first node of the range; nullptr: not given
     int LD, nv, nx2, nu, nodes;
     int callerF64, storedF64;
+    int toBlocks;         // 1: caller's arrays -> blocks (set), 0: blocks -> caller's arrays (get)
 };
 constexpr int PACK_THREADS = 256;
 typedef float nat_f2 __attribute__((ext_vector_type(2)));
@@ -166,10 +167,14 @@ __device__ __forceinline__ void pack_operators_body(const PackOpsArgs &a) {
         }
     }
 }
-template <bool TO_BLOCKS>
+template <typename C, typename S>
+__device__ __forceinline__ void pack_operators_dir(const PackOpsArgs &a) {
+    if (a.toBlocks) pack_operators_body<C, S, true>(a); else pack_operators_body<C, S, false>(a);
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
 __global__ void __launch_bounds__(PACK_THREADS) k_pack_operators(PackOpsArgs a) {
-    if (a.callerF64) { if (a.storedF64) pack_operators_body<double, double, TO_BLOCKS>(a); else pack_operators_body<double, float, TO_BLOCKS>(a); }
-    else { if (a.storedF64) pack_operators_body<float, double, TO_BLOCKS>(a); else pack_operators_body<float, float, TO_BLOCKS>(a); }
+    if (a.callerF64) { if (a.storedF64) pack_operators_dir<double, double>(a); else pack_operators_dir<double, float>(a); }
+    else { if (a.storedF64) pack_operators_dir<float, double>(a); else pack_operators_dir<float, float>(a); }
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -153,6 +153,10 @@ struct CtxBase {
     virtual int set_stop_tolerance(double, int) = 0;
     virtual int get_stop_tolerance(double *, int *) = 0;
     virtual int last_solve(long *) = 0;
+    virtual int set_restart(int) = 0;
+    virtual int get_restart(int *) = 0;
+    virtual int restart_info(long *, double *) = 0;
+    virtual int debug_restart_test(double *) = 0;
     virtual int control_action(const double *, const double *, const double *, const double *, const double *, int, int,
                                double *) = 0;
     virtual int extrapolate(double) = 0;
@@ -423,6 +427,16 @@ struct Ctx : CtxBase {
     double stopTol = 0.0;
     int stopEvery = RN_STOP_CHECK_EVERY;
     long lastSolve[4] = {0, 0, -1, 0};   // rn_get_last_solve
+    // rn_set_restart: RN_RESTART_GRADIENT -- the APG loops run in batches (solve_loop) and every batch end evaluates the gradient test
+    // (k_restart_test, k_dual.hpp).  d_rt: the kernel's per-workgroup partials ([ELT_MAX_BLOCKS][6]) and, behind them, its arrival counter;
+    // allocated by the first rn_set_restart(RN_RESTART_GRADIENT) / rn_debug_restart_test, never by a context that leaves the mode off.
+    // lamBase: iteration at which the lambda sequence started last (0 after a reset; h_it at a restart inside a solve): iteration t takes
+    // h_lam[t - lamBase], while the iteration count, the history and the device's counter run on.
+    int restartMode = RN_RESTART_OFF;
+    double *d_rt = nullptr;
+    int lamBase = 0;
+    long restartCounts[4] = {0, -1, 0, 0};     // rn_get_restart_info: restarts, iteration of the last one, batches tested, 0
+    double restartLast[3] = {0.0, 0.0, 0.0};   // g, na2, nb2 of the last test
     bool unscaled_on() const { return knob[RN_KNOB_UNSCALED_WALK] != 0; }   // inner iterations of optimistic batches take that pair of kernels (default on)
     // rn_debug_set_knob (include/rapidnet_debug.h): launch-shape choices the library otherwise makes by problem size, forced by tests and A/B tools
     // on trees that would not take them by themselves; -1 = the library's own choice.  Before the factor step only.
@@ -1750,7 +1764,7 @@ struct Ctx : CtxBase {
         }
         mainPartials = dualBlocks;
         DualStageShape g = dshape;
-        g.lnNext = h_lam[h_it + 1];   // ensure_tables(h_it + n) has run: the table covers every iteration of the batch
+        g.lnNext = h_lam[h_it + 1 - lamBase];   // ensure_tables(h_it + n) has run: the table covers every iteration of the batch
         if (hxUnscaled && !materialize) {   // unscaled walk: Hx = sqrt(p_i) d_k * (primal value) is formed here
             if (dualU == 1) hipLaunchKernelGGL((k_dual_stage<T, false, 1, true>), dim3(dualBlocks), dim3(ELT_THREADS), 0, stream, a, g);
             else hipLaunchKernelGGL((k_dual_stage<T, false, 2, true>), dim3(dualBlocks), dim3(ELT_THREADS), 0, stream, a, g);
@@ -1769,7 +1783,12 @@ struct Ctx : CtxBase {
         a.ynew = p_xi; a.wnext = p_acc_other; a.z = d_z; a.res = d_res;
         a.n = ntot(); a.nx = d.nx; a.ny = ny;
         a.lambda = (T)stepSize; a.invLambda = (T)(1.0 / stepSize);
-        a.lamNext = d_lam; a.thrX = penX / stepSize; a.thrS = penXs / stepSize;
+        // the kernels index it by iteration: lamNext[t + 1] = entry t + 1 - lamBase of the sequence.  With lamBase > 0 the pointer stands IN
+        // FRONT of the allocation; the invariant that keeps every access inside it: the only read is lamNext[t + 1] of the iteration t being
+        // run (k_dual_fused), and t >= lamBase for every iteration behind a restart (lamBase is h_it at the restart, the device's counter runs
+        // with h_it), t + 1 - lamBase <= lamCap - 1 by ensure_tables.  A kernel that read lamNext[t] with t < lamBase would read outside.
+        a.lamNext = d_lam - lamBase;
+        a.thrX = penX / stepSize; a.thrS = penXs / stepSize;
         a.st = d_state; a.partials = d_partials;
         a.crownElems = 0; a.countCrown = 1;
         a.finalizedEarly = 0; a.hist = d_hist; a.histParts = d_histParts; a.histCap = histCap;
@@ -1822,6 +1841,7 @@ struct Ctx : CtxBase {
         acc_ready = true;  // w_0 = (1+l) 0 - l 0 = 0
         poisoned = false;
         h_it = 0;      // (the lambda table is the same fixed sequence after every restart: kept, with its device copy)
+        lamBase = 0;
         return ensure_tables(0);
     }
     // warm start: keep the duals of the previous control step, restart the momentum (theta = {1,1} => w_0 = y+)
@@ -1830,8 +1850,49 @@ struct Ctx : CtxBase {
         RN_HIP(hipMemcpyAsync(p_xi, p_upd, (size_t)ntot() * sizeof(T), hipMemcpyDeviceToDevice, stream));   // y := y+
         RN_HIP(hipMemsetAsync(d_state, 0, sizeof(IterState), stream));
         h_it = 0;
+        lamBase = 0;
         acc_ready = false;   // the first iteration re-derives w_0 = (1 + 0) y+ - 0 y
         return ensure_tables(0);
+    }
+    // The restart INSIDE a solve (rn_set_restart, decided at a batch end by solve_loop): y := y+, the next iteration re-derives w = y+ from
+    // the first entry of the lambda sequence (0) -- and nothing else moves: the iteration count, the history, the device's iteration state
+    // (its counter indexes the history; tripped / scale / dist are rewritten by every iteration, the verdict flag by every batch opening)
+    // and the batch counters are the solve's.
+    int momentum_restart() {
+        RN_HIP(hipMemcpyAsync(p_xi, p_upd, (size_t)ntot() * sizeof(T), hipMemcpyDeviceToDevice, stream));   // y := y+
+        acc_ready = false;
+        lamBase = h_it;
+        return RN_OK;
+    }
+    int restart_buffers() {
+        if (d_rt) return RN_OK;
+        RN_HIP(hipSetDevice(device));
+        if (int rc = dalloc(&d_rt, (size_t)6 * ELT_MAX_BLOCKS + 1)) return rc;
+        RN_HIP(hipMemsetAsync(d_rt, 0, ((size_t)6 * ELT_MAX_BLOCKS + 1) * sizeof(double), stream));
+        return RN_OK;
+    }
+    // k_restart_test on (w_k, y_{k+1}, y_k) = (p_acc_view, p_upd, p_xi) as they stand behind a batch's rotation; the result lands in the batch
+    // record (d_state->rec; single GPU: also in the host-mapped copy).  Sharded: every rank's sum counts its own subtree rows, rank 0's the
+    // replicated crown as well; the three doubles are summed over the ranks, then passed through a MAX all-reduce so that every rank holds
+    // the same bits -- hence takes the same decision -- whatever order a collective added them in.
+    int launch_restart_test(bool sharded) {
+        RestartArgs a{};
+        a.f64 = sizeof(T) == 8 ? 1 : 0;
+        a.w = p_acc_view; a.yp = p_upd; a.y = p_xi; a.n = ntot();
+        a.crownElems = 0; a.countCrown = 1;
+        if (cutStage > 0) { a.crownElems = (long long)h_stageCum[cutStage] * ny; a.countCrown = (rank == 0); }
+        a.partials = d_rt; a.ticket = reinterpret_cast<unsigned int *>(d_rt + (size_t)6 * ELT_MAX_BLOCKS);
+        a.st = d_state; a.hostRec = sharded ? nullptr : h_rec;
+        RN_HIP(hipMemsetAsync(a.ticket, 0, sizeof(double), stream));
+        hipEvent_t e3 = prof_begin(3);
+        hipLaunchKernelGGL(k_restart_test<>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, a);
+        prof_end(e3);
+        RN_HIP(hipGetLastError());
+        if (sharded) {
+            if (int rc = all_reduce(&d_state->rec.g, 3, true, "ncclAllReduce(restart test)")) return rc;
+            if (int rc = all_reduce(&d_state->rec.g, 3, true, "ncclAllReduce(restart test, agreement)", 2 /* ncclMax */)) return rc;
+        }
+        return RN_OK;
     }
     int set_warm_start(int on) override { warmStart = on ? 1 : 0; return RN_OK; }
     size_t cut_tail_offset() const { return (size_t)(h_stageCum[cutStage] - h_stageCum[cutStage - 1]) * (d.nv + 2 * d.nx); }
@@ -1868,7 +1929,8 @@ struct Ctx : CtxBase {
     // recTol >= 0: the batch is run under a stop tolerance -- its closing launch scans the batch's history entries for recTol, and the host
     // reads the batch record (lastRec) behind the batch's synchronisation: the one an optimistic batch has anyway, one of its own for an exact
     // batch.  recTol < 0: nobody asked, nothing is scanned and an exact batch does not synchronise.  A replayed batch is judged on the replay's record.
-    int run_batch(int n, double *primalInfs, bool optimistic, double recTol = -1.0) {
+    // rtest (with recTol >= 0): the gradient restart test is evaluated on the batch's final iterates, in front of the same synchronisation.
+    int run_batch(int n, double *primalInfs, bool optimistic, double recTol = -1.0, bool rtest = false) {
         Batch b{};
         b.optimistic = optimistic; b.sharded = has_comm() && cutStage > 0;
         const int first = h_it;
@@ -1883,11 +1945,11 @@ struct Ctx : CtxBase {
         for (int k = 0; k < n; k++) {
             const bool last = k == n - 1;
             if (!acc_ready) {   // re-derive w_t after manual buffer edits (SmpcController.cu:1514)
-                hipLaunchKernelGGL(k_extrapolate<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, p_acc, p_xi, p_upd, (T)h_lam[h_it], ntot());
+                hipLaunchKernelGGL(k_extrapolate<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, p_acc, p_xi, p_upd, (T)h_lam[h_it - lamBase], ntot());
                 acc_ready = true;
             }
             b.fuseReq = b.optimistic && fuse_want();
-            if (b.fuseReq) { b.fuseArgs = dual_args(); b.fuseMat = last; b.fuseLn = h_lam[h_it + 1]; }
+            if (b.fuseReq) { b.fuseArgs = dual_args(); b.fuseMat = last; b.fuseLn = h_lam[h_it + 1 - lamBase]; }
             if (int rc = launch_sweep(&b, 0, nullptr, last)) return fail_batch(rc);
             b.fuseReq = false;
             DualArgs<T> a = dual_args();
@@ -1933,6 +1995,7 @@ struct Ctx : CtxBase {
             if (int rc = globalize_history(first, n, tail, recTol)) return fail_batch(rc);
         }
         RN_HIP(hipGetLastError());
+        if (rtest && n > 0 && recTol >= 0) { if (int rc = launch_restart_test(b.sharded)) return fail_batch(rc); }
         int violated = 0;
         const bool synced = n > 0 && (b.optimistic || recTol >= 0);
         if (synced) {   // the batch record: the verdict of an optimistic batch, and what a stop tolerance asks about
@@ -1940,6 +2003,7 @@ struct Ctx : CtxBase {
                 RN_HIP(hipStreamSynchronize(stream));
                 const volatile BatchRecord *r = h_rec;
                 lastRec.verdict = r->verdict; lastRec.firstBelow = r->firstBelow; lastRec.lastResidual = r->lastResidual;
+                lastRec.g = r->g; lastRec.na2 = r->na2; lastRec.nb2 = r->nb2;
             } else {   // sharded (k_batch_close_unpack: tree-global values, the same bits on every rank), or no mapped memory: one copy
                 RN_HIP(hipMemcpyAsync(&lastRec, &d_state->rec, sizeof(BatchRecord), hipMemcpyDeviceToHost, stream));
                 RN_HIP(hipStreamSynchronize(stream));
@@ -1951,7 +2015,7 @@ struct Ctx : CtxBase {
             fallbacks++;
             if (int rc = restore_iterates(saved)) return fail_batch(rc);
             optHold = RN_OPT_BACKOFF;
-            return run_batch(n, primalInfs, false, recTol);
+            return run_batch(n, primalInfs, false, recTol, rtest);
         }
         if (primalInfs && n > 0) {
             if (!synced) RN_HIP(hipStreamSynchronize(stream));   // (an optimistic batch has synchronised for its verdict, a batch under a tolerance for its record)
@@ -2230,7 +2294,7 @@ struct Ctx : CtxBase {
         return RN_OK;
     }
     int apg_iterate(int n, double *primalInfs) override { return apg_iterate(n, primalInfs, -1.0); }
-    int apg_iterate(int n, double *primalInfs, double recTol) {
+    int apg_iterate(int n, double *primalInfs, double recTol, bool rtest = false) {
         RN_CHECK(factored && affine_ready, RN_E_STATE, "rn_apg_iterate before the factor step / affine terms");
         RN_CHECK(n >= 0, RN_E_ARG, "rn_apg_iterate: negative iteration count");
         RN_CHECK(!poisoned, RN_E_STATE, "rn_apg_iterate: an earlier batch failed half-way; call rn_apg_reset first");
@@ -2247,7 +2311,7 @@ struct Ctx : CtxBase {
         if (opt && optHold > 0) { optHold--; opt = false; }
         if (opt) optBatches++;
         else if (n > 0) exactBatches++;
-        return run_batch(n, primalInfs, opt, recTol);
+        return run_batch(n, primalInfs, opt, recTol, rtest);
     }
     // The loop of rn_apg_solve (the reset, or the warm restart, is the caller's): batches of `every` iterations through apg_iterate -- so the
     // iterates are those of the same sequence of rn_apg_iterate calls, bit for bit -- until the residual of a batch's LAST iteration is <= tol
@@ -2255,28 +2319,48 @@ struct Ctx : CtxBase {
     // decision is the host's and is taken where the host synchronises anyway: behind the launch that closes the batch, which has published the
     // batch record (common.hpp, BatchRecord).  Sharded: the record is built from the all-reduced history, the same bits on every rank, so all
     // ranks stop together.  tol == 0 never stops early.
+    // rn_set_restart(RN_RESTART_GRADIENT): behind the tolerance check -- a solve that stops does not restart -- the batch's gradient test
+    // decides whether the momentum starts again (g > 0: momentum_restart).  A replayed batch is judged on the replay; sharded ranks hold the
+    // same bits of g and decide alike.
     int solve_loop(int maxIt, double tol, int every, double *primalInfs) {
         lastSolve[0] = 0; lastSolve[1] = 0; lastSolve[2] = -1; lastSolve[3] = 0;
+        const bool rtest = restartMode == RN_RESTART_GRADIENT;
+        restartCounts[0] = 0; restartCounts[1] = -1; restartCounts[2] = 0; restartCounts[3] = 0;
+        restartLast[0] = restartLast[1] = restartLast[2] = 0.0;
         for (int done = 0; done < maxIt;) {
             const int n = std::min(every, maxIt - done);
-            if (int rc = apg_iterate(n, primalInfs ? primalInfs + done : nullptr, tol)) return rc;
+            if (int rc = apg_iterate(n, primalInfs ? primalInfs + done : nullptr, tol, rtest)) return rc;
             if (lastSolve[2] < 0 && lastRec.firstBelow >= 0) lastSolve[2] = done + lastRec.firstBelow;
             done += n;
             lastSolve[0] = done; lastSolve[3]++;
             if (tol > 0 && lastRec.lastResidual <= tol) { lastSolve[1] = 1; break; }
+            if (rtest) {
+                restartCounts[2]++;
+                restartLast[0] = lastRec.g; restartLast[1] = lastRec.na2; restartLast[2] = lastRec.nb2;
+                if (lastRec.g > 0 && !poisoned) {
+                    if (int rc = momentum_restart()) return rc;
+                    restartCounts[0]++; restartCounts[1] = done;
+                }
+            }
         }
         return RN_OK;
     }
     // what rn_algorithm_apg and rn_control_action run after their reset: one batch of maxIt iterations -- today's path, untouched -- unless
     // rn_set_stop_tolerance named a tolerance
     int apg_run(int maxIt, double *primalInfs) override {
-        if (stopTol > 0) {
+        if (stopTol > 0 || restartMode == RN_RESTART_GRADIENT) {   // (restart without a tolerance: batches of stopEvery, never stopping early)
             RN_CHECK(factored && affine_ready, RN_E_STATE, "rn_apg_iterate before the factor step / affine terms");
             RN_CHECK(maxIt >= 0, RN_E_ARG, "rn_apg_iterate: negative iteration count");
-            return solve_loop(maxIt, stopTol, stopEvery, primalInfs);
+            const int rc = solve_loop(maxIt, stopTol, stopEvery, primalInfs);
+            // no tolerance was set (the batches are the restart's): rn_get_last_solve promises -1 -- the closing launches scanned for
+            // entries <= 0, and vecPrimalInfs can be exactly 0 (`small`: over its first 140 iterations)
+            if (stopTol <= 0) lastSolve[2] = -1;
+            return rc;
         }
         if (int rc = apg_iterate(maxIt, primalInfs)) return rc;
         lastSolve[0] = maxIt; lastSolve[1] = 0; lastSolve[2] = -1; lastSolve[3] = maxIt > 0 ? 1 : 0;
+        restartCounts[0] = 0; restartCounts[1] = -1; restartCounts[2] = 0; restartCounts[3] = 0;
+        restartLast[0] = restartLast[1] = restartLast[2] = 0.0;
         return RN_OK;
     }
     int apg_solve(int maxIt, double tol, int every, int *iterationsRun, double *primalInfs) override {
@@ -2298,6 +2382,35 @@ struct Ctx : CtxBase {
     int get_stop_tolerance(double *tol, int *every) override {
         if (tol) *tol = stopTol;
         if (every) *every = stopEvery;
+        return RN_OK;
+    }
+    int set_restart(int mode) override {
+        RN_CHECK(mode == RN_RESTART_OFF || mode == RN_RESTART_GRADIENT, RN_E_ARG, "rn_set_restart: RN_RESTART_OFF or RN_RESTART_GRADIENT");
+        if (mode == RN_RESTART_GRADIENT) { if (int rc = restart_buffers()) return rc; }   // here, not inside a control step
+        restartMode = mode;
+        return RN_OK;
+    }
+    int get_restart(int *mode) override {
+        RN_CHECK(mode, RN_E_ARG, "rn_get_restart: null output");
+        *mode = restartMode;
+        return RN_OK;
+    }
+    int restart_info(long *counts, double *last) override {
+        RN_CHECK(counts && last, RN_E_ARG, "rn_get_restart_info: null output");
+        for (int i = 0; i < 4; i++) counts[i] = restartCounts[i];
+        for (int i = 0; i < 3; i++) last[i] = restartLast[i];
+        return RN_OK;
+    }
+    // rn_debug_restart_test (include/rapidnet_debug.h): the kernel alone, on the iterates as they stand (sharded contexts: collective)
+    int debug_restart_test(double *out) override {
+        RN_CHECK(out, RN_E_ARG, "rn_debug_restart_test: null output");
+        RN_CHECK(p_acc_view && p_upd && p_xi, RN_E_STATE, "rn_debug_restart_test before the factor step");
+        RN_CHECK(!poisoned, RN_E_STATE, "rn_debug_restart_test: an earlier batch failed half-way; call rn_apg_reset first");
+        RN_HIP(hipSetDevice(device));
+        if (int rc = restart_buffers()) return rc;
+        if (int rc = launch_restart_test(has_comm() && cutStage > 0)) return rc;
+        RN_HIP(hipMemcpyAsync(out, &d_state->rec.g, 3 * sizeof(double), hipMemcpyDeviceToHost, stream));
+        RN_HIP(hipStreamSynchronize(stream));
         return RN_OK;
     }
     int last_solve(long *out) override {
@@ -2935,8 +3048,8 @@ struct Ctx : CtxBase {
         const long long perNode = (long long)ny * (LD / (16 / block_elem()));
         const int gx = (int)std::min<long long>((perNode + PACK_THREADS - 1) / PACK_THREADS, (long long)numCUs * 4);
         const int gy = std::max(1, std::min(count, numCUs * 4 / gx));
-        if (toBlocks) hipLaunchKernelGGL(k_pack_operators<true>, dim3(gx, gy), dim3(PACK_THREADS), 0, stream, a);
-        else hipLaunchKernelGGL(k_pack_operators<false>, dim3(gx, gy), dim3(PACK_THREADS), 0, stream, a);
+        a.toBlocks = toBlocks ? 1 : 0;
+        hipLaunchKernelGGL(k_pack_operators<>, dim3(gx, gy), dim3(PACK_THREADS), 0, stream, a);
     }
     // a caller's device array: memory of this context's device (hipPointerGetAttributes) that holds `bytes` bytes from p on.  Anything
     // else -- a host pointer above all -- is refused here, before a kernel could see it
@@ -3324,6 +3437,9 @@ int rn_apg_solve(rn_ctx *ctx, int maxIt, double tol, int every, int *run, double
 int rn_set_stop_tolerance(rn_ctx *ctx, double tol, int every) { RN_GUARD(ctx); return ctx->impl->set_stop_tolerance(tol, every); }
 int rn_get_stop_tolerance(rn_ctx *ctx, double *tol, int *every) { RN_GUARD(ctx); return ctx->impl->get_stop_tolerance(tol, every); }
 int rn_get_last_solve(rn_ctx *ctx, long out[4]) { RN_GUARD(ctx); return ctx->impl->last_solve(out); }
+int rn_set_restart(rn_ctx *ctx, int mode) { RN_GUARD(ctx); return ctx->impl->set_restart(mode); }
+int rn_get_restart(rn_ctx *ctx, int *mode) { RN_GUARD(ctx); return ctx->impl->get_restart(mode); }
+int rn_get_restart_info(rn_ctx *ctx, long counts[4], double last[3]) { RN_GUARD(ctx); return ctx->impl->restart_info(counts, last); }
 int rn_control_action(rn_ctx *ctx, const double *x, const double *u, const double *dm, const double *dh, const double *ah, int maxIt,
                       int project, double *u0) { RN_GUARD(ctx); return ctx->impl->control_action(x, u, dm, dh, ah, maxIt, project, u0); }
 int rn_dual_extrapolation_step(rn_ctx *ctx, double l) { RN_GUARD(ctx); return ctx->impl->extrapolate(l); }
@@ -3473,6 +3589,7 @@ int rn_debug_inject_allocation(rn_ctx *ctx, size_t bytes) { RN_GUARD(ctx); retur
 int rn_debug_guard_poke(rn_ctx *ctx, int nbytes) { RN_GUARD(ctx); return ctx->impl->guard_poke(nbytes); }
 int rn_debug_set_knob(rn_ctx *ctx, int knob, int value) { RN_GUARD(ctx); return ctx->impl->set_knob(knob, value); }
 int rn_debug_stream_info(rn_ctx *ctx, int info[4]) { RN_GUARD(ctx); return ctx->impl->stream_info(info); }
+int rn_debug_restart_test(rn_ctx *ctx, double out[3]) { RN_GUARD(ctx); return ctx->impl->debug_restart_test(out); }
 int rn_debug_peer_seq(rn_ctx *ctx, unsigned int seq) { RN_GUARD(ctx); return ctx->impl->debug_peer_seq(seq); }
 int rn_guard_report(long out[2]) { if (!out) return RN_E_ARG; out[0] = rn::g_guardContexts.load(); out[1] = rn::g_guardBadBytes.load(); return RN_OK; }
 int rn_peer_inbox_create(rn_ctx *ctx, void *ipcHandle64) { RN_GUARD(ctx); return ctx->impl->peer_inbox_create(ipcHandle64); }
