@@ -71,10 +71,17 @@ def test_closed_loop_on_the_reference_fixture(tmp_path, disturbance):
     _compare(d, 2, disturbance)
 
 
+@pytest.mark.parametrize("mode", ["dense", "structured"])
+@pytest.mark.parametrize("name", ["small", "medium"])
 @pytest.mark.parametrize("disturbance", [False, True])
-def test_closed_loop_on_a_synthetic_problem(tmp_path, disturbance):
-    p = synth.make_problem("small", max_iterations=60, sim_horizon=3)
-    synth.write_problem(p, str(tmp_path))
+def test_closed_loop_on_a_synthetic_problem(tmp_path, disturbance, name, mode):
+    """the host classes with the operator form named by the configuration file's "operatorMode" key, on `small` (ny = 19: the flat dual
+    update) and `medium` (the stage-tiled kernels)"""
+    p = synth.make_problem(name, max_iterations=60, sim_horizon=3)
+    cfg_path = synth.write_problem(p, str(tmp_path))
+    cfg = load_json(cfg_path)
+    cfg["operatorMode"] = mode
+    json.dump(cfg, open(cfg_path, "w"))
     _compare(str(tmp_path), 3, disturbance)
 
 

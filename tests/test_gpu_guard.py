@@ -15,6 +15,7 @@ import test_gpu_apg_f32 as apg32
 import test_gpu_fbe_nama as fbe
 import test_gpu_fbe_nama_f32 as f32
 import test_gpu_parity as par
+import test_gpu_receding_horizon as rh
 import test_gpu_sharded_batched as shb
 import test_gpu_stream_split as spl
 from rapidnet_amd import capi, synth
@@ -117,6 +118,12 @@ def test_f32_apg_batches_under_guard(guard):
     of the fp64 loop's fp32-rounded states -- the re-derived w behind rn_set, the checkpoint copies and the batch close are where a vector
     body's last store or a tail would land in a red zone"""
     guard["contexts"] = apg32.guard_body()
+
+
+def test_control_steps_under_guard(guard):
+    """five warm control steps on one structured context and on 3 rank contexts of `medium`: the warm start's copy between the rotating
+    dual buffers, the checkpoints of the optimistic batches and the exchange buffers at the cut, step after step"""
+    guard["contexts"] = rh.guard_body()
 
 
 @pytest.mark.parametrize("cases", [(("b236", "three", "f64"), ("nv129", "two", "f64"))])
