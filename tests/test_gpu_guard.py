@@ -14,6 +14,7 @@ import pytest
 import test_gpu_apg_f32 as apg32
 import test_gpu_fbe_nama as fbe
 import test_gpu_fbe_nama_f32 as f32
+import test_gpu_first_principles as fpg
 import test_gpu_parity as par
 import test_gpu_receding_horizon as rh
 import test_gpu_sharded_batched as shb
@@ -124,6 +125,12 @@ def test_control_steps_under_guard(guard):
     """five warm control steps on one structured context and on 3 rank contexts of `medium`: the warm start's copy between the rotating
     dual buffers, the checkpoints of the optimistic batches and the exchange buffers at the cut, step after step"""
     guard["contexts"] = rh.guard_body()
+
+
+def test_first_principles_under_guard(guard):
+    """`small`, dense and structured, against the problem's definition (tests/first_principles.py): the solve step from random and from
+    9-iteration duals, and the state behind an exact iteration and an optimistic batch"""
+    guard["contexts"] = fpg.guard_body()
 
 
 @pytest.mark.parametrize("cases", [(("b236", "three", "f64"), ("nv129", "two", "f64"))])
