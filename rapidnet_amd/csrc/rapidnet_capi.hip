@@ -2573,224 +2573,8 @@ struct Ctx : CtxBase {
         return RN_OK;
     }
 
-    // ---- raw access --------------------------------------------------------------------------------------
-    // maps a buffer id to (y-layout base, offset, dim) or to a plain array
-    bool ymap(int id, T **base, int *off, int *dim) {
-        const int nx = d.nx, nu = d.nu;
-        switch (id) {
-            case RN_BUF_XI: *base = p_xi; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_PSI: *base = p_xi; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_ACC_XI: *base = p_acc_view; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_ACC_PSI: *base = p_acc_view; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_UPD_XI: *base = p_upd; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_UPD_PSI: *base = p_upd; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_PRIMAL_XI: *base = d_hx; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_PRIMAL_PSI: *base = d_hx; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_DUAL_XI: *base = d_z; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_DUAL_PSI: *base = d_z; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_RES_XI: *base = d_res; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_RES_PSI: *base = d_res; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_XMIN: *base = d_lo; *off = 0; *dim = nx; return true;
-            case RN_BUF_XMAX: *base = d_hi; *off = 0; *dim = nx; return true;
-            case RN_BUF_XS: *base = d_lo; *off = nx; *dim = nx; return true;
-            case RN_BUF_UMIN: *base = d_lo; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_UMAX: *base = d_hi; *off = 2 * nx; *dim = nu; return true;
-            default: break;
-        }
-        if (!d_matS) return false;   // the FBE / NAMA vectors exist once rn_set_algorithm selected one of them
-        switch (id) {
-            case RN_BUF_PREV_XI: *base = d_prevY; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_PREV_PSI: *base = d_prevY; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_LBFGS_CUR_YVEC_XI: *base = d_g; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_LBFGS_CUR_YVEC_PSI: *base = d_g; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_LBFGS_PREV_YVEC_XI: *base = d_gPrev; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_LBFGS_PREV_YVEC_PSI: *base = d_gPrev; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_LBFGS_DIR_XI: *base = d_dir; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_LBFGS_DIR_PSI: *base = d_dir; *off = 2 * nx; *dim = nu; return true;
-            case RN_BUF_PRIMAL_XI_DIR: *base = d_hxDir; *off = 0; *dim = 2 * nx; return true;
-            case RN_BUF_PRIMAL_PSI_DIR: *base = d_hxDir; *off = 2 * nx; *dim = nu; return true;
-            default: return false;
-        }
-    }
-    T *plain(int id, size_t *n) {
-        const size_t N_ = d.nodes;
-        switch (id) {
-            case RN_BUF_X: *n = N_ * d.nx; return d_x;
-            case RN_BUF_U: *n = N_ * d.nu; return d_u;
-            case RN_BUF_V: *n = N_ * d.nv; return d_v;
-            case RN_BUF_UHAT: *n = N_ * d.nu; return d_uhat;
-            case RN_BUF_E: *n = N_ * d.nx; return d_e;
-            case RN_BUF_BETA: *n = N_ * d.nv; return d_beta;
-            case RN_BUF_ALPHA: *n = N_ * d.nu; return d_alpha;
-            case RN_BUF_XDIR: *n = d_xdir ? N_ * d.nx : 0; return d_xdir;
-            case RN_BUF_UDIR: *n = d_udir ? N_ * d.nu : 0; return d_udir;
-            default: *n = 0; return nullptr;
-        }
-    }
-    // The scaled bounds (Engine.cuh:294-314 getSysXmin ... getSysUmax; Engine.cu:433-463) live interleaved in the dual layout here ([node][ny]: the
-    // fused dual update rebuilds them from tables).  A caller that asks for their device pointers gets node-major copies in the reference's layout,
-    // made on the first request (5 arrays, (3 nx + 2 nu) reals per node) and refreshed by every later factor step.
-    T *d_bnd[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    int refresh_bounds_copies() {
-        if (!d_bnd[0]) return RN_OK;
-        const int ids[5] = {RN_BUF_XMIN, RN_BUF_XMAX, RN_BUF_XS, RN_BUF_UMIN, RN_BUF_UMAX};
-        for (int i = 0; i < 5; i++) {
-            T *b; int off, dim;
-            if (!ymap(ids[i], &b, &off, &dim)) continue;
-            hipLaunchKernelGGL(k_pack<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, b, d_bnd[i], ny, off, dim, (long long)d.nodes, 0);
-        }
-        RN_HIP(hipGetLastError());
-        return RN_OK;
-    }
-    int device_pointer(int id, void **ptr, size_t *n, int *prec) override {
-        RN_CHECK(ptr && n && prec, RN_E_ARG, "rn_device_pointer: null output");
-        *ptr = nullptr; *n = 0; *prec = sizeof(T) == 8 ? RN_F64 : RN_F32;
-        if (id >= RN_BUF_XMIN && id <= RN_BUF_UMAX) {
-            RN_CHECK(factored, RN_E_STATE, "rn_device_pointer: the scaled bounds exist after rn_factor_step");
-            RN_HIP(hipSetDevice(device));
-            if (!d_bnd[0]) {
-                const size_t dims[5] = {(size_t)d.nx, (size_t)d.nx, (size_t)d.nx, (size_t)d.nu, (size_t)d.nu};
-                for (int i = 0; i < 5; i++) if (int rc = dalloc(&d_bnd[i], (size_t)d.nodes * dims[i])) return rc;
-                if (int rc = refresh_bounds_copies()) return rc;
-                RN_HIP(hipStreamSynchronize(stream));
-            }
-            const int i = id - RN_BUF_XMIN;
-            *ptr = d_bnd[i]; *n = (size_t)d.nodes * (i < 3 ? d.nx : d.nu);
-            return RN_OK;
-        }
-        size_t cnt = 0;
-        if (id == RN_BUF_V) { vEager = true; if (int rc = v_flush()) return rc; }      // from now on v is computed with every sweep that stores the primal iterates
-        T *p = plain(id, &cnt);
-        RN_CHECK(p != nullptr && cnt > 0, RN_E_ARG, "rn_device_pointer: this buffer is not kept in the reference's layout on the device (or not allocated yet): use rn_get");
-        *ptr = p; *n = cnt;
-        return RN_OK;
-    }
-    size_t buffer_size(int id) const override {
-        T *b; int off, dim; size_t n;
-        Ctx *self = const_cast<Ctx *>(this);
-        if (self->ymap(id, &b, &off, &dim)) return (size_t)d.nodes * dim;
-        self->plain(id, &n);
-        return n;
-    }
-    int get(int id, double *host, size_t n) override {
-        RN_CHECK(host, RN_E_ARG, "rn_get: null host pointer");
-        RN_HIP(hipSetDevice(device));
-        T *b; int off, dim; size_t cnt;
-        if (ymap(id, &b, &off, &dim)) {
-            RN_CHECK(n == (size_t)d.nodes * dim, RN_E_ARG, "rn_get: size mismatch");
-            hipLaunchKernelGGL(k_pack<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, b, d_tmp, ny, off, dim, (long long)d.nodes, 0);
-            RN_HIP(hipGetLastError());
-            return download(host, d_tmp, n);
-        }
-        if (id == RN_BUF_V) { if (int rc = v_flush()) return rc; }
-        T *p = plain(id, &cnt);
-        RN_CHECK(p != nullptr, RN_E_ARG, "rn_get: unknown buffer id");
-        RN_CHECK(n == cnt, RN_E_ARG, "rn_get: size mismatch");
-        return download(host, p, n);
-    }
-    int set(int id, const double *host, size_t n) override {
-        RN_CHECK(host, RN_E_ARG, "rn_set: null host pointer");
-        RN_HIP(hipSetDevice(device));
-        T *b; int off, dim; size_t cnt;
-        if (ymap(id, &b, &off, &dim)) {
-            RN_CHECK(id < RN_BUF_XMIN || id > RN_BUF_UMAX, RN_E_ARG, "rn_set: the scaled bounds are read-only");
-            RN_CHECK(n == (size_t)d.nodes * dim, RN_E_ARG, "rn_set: size mismatch");
-            if (int rc = upload(d_tmp, host, n)) return rc;
-            hipLaunchKernelGGL(k_pack<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, b, d_tmp, ny, off, dim, (long long)d.nodes, 1);
-            RN_HIP(hipGetLastError());
-            RN_HIP(hipStreamSynchronize(stream));
-            if (id == RN_BUF_ACC_XI || id == RN_BUF_ACC_PSI) {   // the view becomes the sweep input
-                if (p_acc_view != p_acc) std::swap(p_acc, p_acc_other);
-                acc_ready = true;
-            } else if (id == RN_BUF_XI || id == RN_BUF_PSI || id == RN_BUF_UPD_XI || id == RN_BUF_UPD_PSI) {
-                acc_ready = false;
-            }
-            return RN_OK;
-        }
-        if (id == RN_BUF_V) vPending = false;      // the caller's values replace it
-        T *p = plain(id, &cnt);
-        RN_CHECK(p != nullptr, RN_E_ARG, "rn_set: unknown buffer id");
-        RN_CHECK(n == cnt, RN_E_ARG, "rn_set: size mismatch");
-        if (id == RN_BUF_UHAT || id == RN_BUF_E || id == RN_BUF_BETA) { affine_ready = true; aux_dirty = true; }
-        return upload(p, host, n);
-    }
-    // elements [first, first + n) of a buffer in the reference's node-major layout; dual-shaped buffers: whole nodes only
-    int get_range(int id, size_t first, size_t n, double *host) override {
-        RN_CHECK(host, RN_E_ARG, "rn_get_range: null host pointer");
-        RN_HIP(hipSetDevice(device));
-        T *b; int off, dim; size_t cnt;
-        if (ymap(id, &b, &off, &dim)) {
-            RN_CHECK(first % dim == 0 && n % dim == 0 && first + n <= (size_t)d.nodes * dim, RN_E_ARG, "rn_get_range: dual-shaped buffers are addressed in whole nodes");
-            hipLaunchKernelGGL(k_pack<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, b + (first / dim) * ny, d_tmp, ny, off, dim, (long long)(n / dim), 0);
-            RN_HIP(hipGetLastError());
-            return download(host, d_tmp, n);
-        }
-        if (id == RN_BUF_V) { if (int rc = v_flush()) return rc; }
-        T *p = plain(id, &cnt);
-        RN_CHECK(p != nullptr, RN_E_ARG, "rn_get_range: unknown buffer id");
-        RN_CHECK(first + n <= cnt, RN_E_ARG, "rn_get_range: range outside the buffer");
-        return download(host, p + first, n);
-    }
-    int set_range(int id, size_t first, size_t n, const double *host) override {
-        RN_CHECK(host, RN_E_ARG, "rn_set_range: null host pointer");
-        RN_HIP(hipSetDevice(device));
-        T *b; int off, dim; size_t cnt;
-        if (ymap(id, &b, &off, &dim)) {
-            RN_CHECK(id < RN_BUF_XMIN || id > RN_BUF_UMAX, RN_E_ARG, "rn_set_range: the scaled bounds are read-only");
-            RN_CHECK(first % dim == 0 && n % dim == 0 && first + n <= (size_t)d.nodes * dim, RN_E_ARG, "rn_set_range: dual-shaped buffers are addressed in whole nodes");
-            if (int rc = upload(d_tmp, host, n)) return rc;
-            hipLaunchKernelGGL(k_pack<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, b + (first / dim) * ny, d_tmp, ny, off, dim, (long long)(n / dim), 1);
-            RN_HIP(hipGetLastError());
-            RN_HIP(hipStreamSynchronize(stream));
-            if (id == RN_BUF_ACC_XI || id == RN_BUF_ACC_PSI) { if (p_acc_view != p_acc) std::swap(p_acc, p_acc_other); acc_ready = true; }
-            else if (id == RN_BUF_XI || id == RN_BUF_PSI || id == RN_BUF_UPD_XI || id == RN_BUF_UPD_PSI) acc_ready = false;
-            return RN_OK;
-        }
-        if (id == RN_BUF_V) { if (int rc = v_flush()) return rc; }      // (the rest of the buffer must be the sweep's)
-        T *p = plain(id, &cnt);
-        RN_CHECK(p != nullptr, RN_E_ARG, "rn_set_range: unknown buffer id");
-        RN_CHECK(first + n <= cnt, RN_E_ARG, "rn_set_range: range outside the buffer");
-        if (id == RN_BUF_UHAT || id == RN_BUF_E || id == RN_BUF_BETA) { affine_ready = true; aux_dirty = true; }
-        return upload(p + first, host, n);
-    }
-    int get_operator(int op, int node, double *host, size_t n) override {
-        RN_CHECK(factored, RN_E_STATE, "rn_get_operator before rn_factor_step");
-        RN_CHECK(host && node >= 0 && node < d.nodes, RN_E_ARG, "rn_get_operator: bad node");
-        const int nx = d.nx, nu = d.nu, nv = d.nv;
-        if (int rc = refresh_h_prob()) return rc;
-        const double p = h_prob[node];
-        if (op == RN_OP_OMEGA) { RN_CHECK(n == (size_t)nv * nv, RN_E_ARG, "rn_get_operator: size"); for (size_t i = 0; i < n; i++) host[i] = h_Rinv[i] / p; return RN_OK; }
-        if (op == RN_OP_G) { RN_CHECK(n == (size_t)nv * nx, RN_E_ARG, "rn_get_operator: size"); for (size_t i = 0; i < n; i++) host[i] = h_Bbt[i]; return RN_OK; }
-        if (op == RN_OP_THETA) {
-            RN_CHECK(n == (size_t)nv * nx, RN_E_ARG, "rn_get_operator: size");
-            std::vector<double> t((size_t)nv * nx);
-            h_gemm(false, false, nv, nx, nv, h_Rinv.data(), nv, h_Bbt.data(), nv, t.data());
-            for (size_t i = 0; i < n; i++) host[i] = -0.5 * t[i] / p;
-            return RN_OK;
-        }
-        RN_CHECK(op == RN_OP_PHI || op == RN_OP_PSI || op == RN_OP_D || op == RN_OP_F, RN_E_ARG, "rn_get_operator: unknown operator id");
-        const bool xiCols = (op == RN_OP_PHI || op == RN_OP_D), top = (op == RN_OP_PHI || op == RN_OP_PSI);
-        const int cols = xiCols ? 2 * nx : nu, c0 = xiCols ? 0 : 2 * nx, r0 = top ? 0 : nv;
-        RN_CHECK(n == (size_t)nv * cols, RN_E_ARG, "rn_get_operator: size");
-        RN_HIP(hipSetDevice(device));
-        if (structured) {   // no stored blocks: evaluate the factor-step formula (kernels.hpp, k_expand_operators) on the host
-            const int k = h_stageOf[node];
-            const double sp = std::sqrt(p);
-            const double *dk = h_diag.data() + (size_t)k * (2 * nx + nu);
-            for (int c = 0; c < cols; c++) {
-                const int j = xiCols ? c % nx : c;
-                const double dc = xiCols ? dk[nu + c] : dk[c];
-                const double *m = top ? (xiCols ? h_T1.data() : h_T2.data()) + (size_t)j * nv : (xiCols ? h_Bbt.data() : h_Lt.data()) + (size_t)j * nv;
-                const double sc = top ? -0.5 * dc / sp : sp * dc;
-                for (int r = 0; r < nv; r++) host[r + (size_t)c * nv] = sc * m[r];
-            }
-            return RN_OK;
-        }
-        std::vector<double> blk((size_t)ny * LD);
-        if (int rc = download_block(node, blk.data())) return rc;
-        for (int c = 0; c < cols; c++) for (int r = 0; r < nv; r++) host[r + (size_t)c * nv] = blk[(size_t)(c0 + c) * LD + r0 + r];
-        return RN_OK;
-    }
+    // ---- caller data into and out of the context: raw access, operator blocks, tree data, bounds -----------
+#include "caller_data.inc"
 
     // ---- multi-GPU ---------------------------------------------------------------------------------------
     // The communicator of this context.  ncclCommInitRank blocks until every rank of the id has arrived -- for ever if one never does.
@@ -3013,326 +2797,6 @@ struct Ctx : CtxBase {
         keepBounds = false;
         if (rcf) { structured = 1; return rcf; }
         if (algorithm == RN_ALG_NAMA) return set_algorithm(algorithm, lbfgsSize);   // (its paired sweep needs buffers of its own in dense mode)
-        return RN_OK;
-    }
-    // One node's block as the caller wants it (the counterpart of rn_get_operator; the reference's Engine hands out the device pointers of
-    // these arrays, Engine.cuh:170-230, so a caller may overwrite any block): Phi_i, Psi_i, D_i, Ftil_i -- the blocks solveStep multiplies
-    // with at SmpcController.cu:617-638.  Omega / Theta / G are K identical copies of shared matrices in the reference: not per-node here.
-    int set_operator(int op, int node, const double *host, size_t n) override {
-        RN_CHECK(factored, RN_E_STATE, "rn_set_operator before rn_factor_step");
-        RN_CHECK(host && node >= 0 && node < d.nodes, RN_E_ARG, "rn_set_operator: bad node");
-        RN_CHECK(op == RN_OP_PHI || op == RN_OP_PSI || op == RN_OP_D || op == RN_OP_F, RN_E_ARG,
-                 "rn_set_operator: only the per-node blocks Phi, Psi, D, F can be handed in (Omega, Theta, G are shared matrices scaled by p_i)");
-        const int nx = d.nx, nu = d.nu, nv = d.nv;
-        const bool xiCols = (op == RN_OP_PHI || op == RN_OP_D), top = (op == RN_OP_PHI || op == RN_OP_PSI);
-        const int cols = xiCols ? 2 * nx : nu, c0 = xiCols ? 0 : 2 * nx, r0 = top ? 0 : nv;
-        RN_CHECK(n == (size_t)nv * cols, RN_E_ARG, "rn_set_operator: size");
-        RN_CHECK(opsMode != RN_OPS_STRUCTURED, RN_E_STATE, "rn_set_operator: the context was created with RN_OPS_STRUCTURED (no per-node blocks); use RN_OPS_AUTO or RN_OPS_DENSE");
-        RN_HIP(hipSetDevice(device));
-        if (structured) { if (int rc = materialise_dense()) return rc; }
-        std::vector<double> blk((size_t)ny * LD);
-        if (int rc = download_block(node, blk.data())) return rc;
-        for (int c = 0; c < cols; c++) for (int r = 0; r < nv; r++) blk[(size_t)(c0 + c) * LD + r0 + r] = host[r + (size_t)c * nv];
-        return upload_block(node, blk.data());      // (fp32 storage: the caller's values rounded to nearest)
-    }
-    // ---- all blocks at once (rn_set_operators / rn_get_operators and their _device forms; k_pack_operators, k_misc.hpp) ----
-    static constexpr size_t PACK_STAGING_BYTES = (size_t)64 << 20;   // the host forms' device staging buffer (rapidnet.h says so)
-    size_t op_cols(int i) const { return i == 0 || i == 2 ? 2 * (size_t)d.nx : (size_t)d.nu; }   // columns of phi, psi, D, F
-    // `count` nodes from `node0` on, to or from caller arrays that START at node0; one launch on the context's stream
-    void pack_launch(bool toBlocks, bool callerF64, void *const op[4], int node0, int count) {
-        PackOpsArgs a{};
-        a.A = store32() ? (void *)(d_A32 + (size_t)node0 * strideA) : (void *)(d_A + (size_t)node0 * strideA);
-        a.strideA = strideA; a.LD = LD; a.nv = d.nv; a.nx2 = 2 * d.nx; a.nu = d.nu; a.nodes = count;
-        for (int i = 0; i < 4; i++) a.op[i] = op[i];
-        a.callerF64 = callerF64 ? 1 : 0; a.storedF64 = block_elem() == 8 ? 1 : 0;
-        const long long perNode = (long long)ny * (LD / (16 / block_elem()));
-        const int gx = (int)std::min<long long>((perNode + PACK_THREADS - 1) / PACK_THREADS, (long long)numCUs * 4);
-        const int gy = std::max(1, std::min(count, numCUs * 4 / gx));
-        a.toBlocks = toBlocks ? 1 : 0;
-        hipLaunchKernelGGL(k_pack_operators<>, dim3(gx, gy), dim3(PACK_THREADS), 0, stream, a);
-    }
-    // a caller's device array: memory of this context's device (hipPointerGetAttributes) that holds `bytes` bytes from p on.  Anything
-    // else -- a host pointer above all -- is refused here, before a kernel could see it
-    int check_device_array(const void *p, size_t bytes, size_t elem, const std::string &what, const char *shape = "nodes x nv x columns") {
-        RN_CHECK(((uintptr_t)p & (elem - 1)) == 0, RN_E_ARG, what + ": a pointer is not aligned to its element type");
-        hipPointerAttribute_t at;
-        std::memset(&at, 0, sizeof at);
-        if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); err = what + ": a pointer is not device memory"; return RN_E_ARG; }
-        RN_CHECK(at.type == hipMemoryTypeDevice, RN_E_ARG, what + ": a pointer is not device memory");
-        RN_CHECK(at.device == device, RN_E_ARG, what + ": a pointer is memory of another device than the context's");
-        hipDeviceptr_t base = nullptr; size_t len = 0;
-        if (hipMemGetAddressRange(&base, &len, (hipDeviceptr_t)p) == hipSuccess)
-            RN_CHECK((const char *)p >= (const char *)base && (size_t)((const char *)p - (const char *)base) + bytes <= len, RN_E_ARG,
-                     what + ": an array is shorter than " + shape + " elements");
-        else (void)hipGetLastError();
-        return RN_OK;
-    }
-    int pack_args_ok(const char *what, size_t nodes, int callerPrec, bool dev, const void *const *op) {
-        RN_CHECK(factored, RN_E_STATE, std::string(what) + " before rn_factor_step");
-        RN_CHECK(nodes == (size_t)d.nodes, RN_E_ARG, std::string(what) + ": nodes must be the context's (local) node count");
-        RN_CHECK(callerPrec == RN_F64 || callerPrec == RN_F32, RN_E_ARG, std::string(what) + ": precision is RN_F32 or RN_F64");
-        RN_CHECK(op[0] || op[1] || op[2] || op[3], RN_E_ARG, std::string(what) + ": all four arrays are NULL");
-        (void)dev;
-        return RN_OK;
-    }
-    int set_operators(size_t nodes, int callerPrec, bool dev, const void *const *op) override {
-        const char *what = dev ? "rn_set_operators_device" : "rn_set_operators";
-        if (int rc = pack_args_ok(what, nodes, callerPrec, dev, op)) return rc;
-        RN_CHECK(opsMode != RN_OPS_STRUCTURED, RN_E_STATE, std::string(what) + ": the context was created with RN_OPS_STRUCTURED (no per-node blocks); use RN_OPS_AUTO or RN_OPS_DENSE");
-        RN_HIP(hipSetDevice(device));
-        const size_t elem = callerPrec == RN_F64 ? 8 : 4;
-        if (dev) for (int i = 0; i < 4; i++)
-            if (op[i]) { if (int rc = check_device_array(op[i], nodes * op_cols(i) * d.nv * elem, elem, what)) return rc; }
-        if (structured) { if (int rc = materialise_dense()) return rc; }     // (RN_OPS_AUTO, first block of the caller's: allocates and synchronises, once)
-        void *p[4] = {const_cast<void *>(op[0]), const_cast<void *>(op[1]), const_cast<void *>(op[2]), const_cast<void *>(op[3])};   // (read only: TO_BLOCKS)
-        if (!dev) return pack_staged(true, p);
-        pack_launch(true, callerPrec == RN_F64, p, 0, d.nodes);
-        RN_HIP(hipGetLastError());
-        return RN_OK;
-    }
-    int get_operators(size_t nodes, int callerPrec, bool dev, void *const *op) override {
-        const char *what = dev ? "rn_get_operators_device" : "rn_get_operators";
-        if (int rc = pack_args_ok(what, nodes, callerPrec, dev, op)) return rc;
-        RN_CHECK(!structured, RN_E_STATE, std::string(what) + ": the context holds no dense blocks (structured operator mode); rn_get_operator evaluates one node's block");
-        RN_HIP(hipSetDevice(device));
-        const size_t elem = callerPrec == RN_F64 ? 8 : 4;
-        if (dev) {
-            for (int i = 0; i < 4; i++)
-                if (op[i]) { if (int rc = check_device_array(op[i], nodes * op_cols(i) * d.nv * elem, elem, what)) return rc; }
-            pack_launch(false, callerPrec == RN_F64, op, 0, d.nodes);
-            RN_HIP(hipGetLastError());
-            return RN_OK;
-        }
-        return pack_staged(false, op);
-    }
-    // the host forms: the same kernel behind a device staging buffer of at most PACK_STAGING_BYTES (one node's arrays if those are larger),
-    // whole nodes per chunk; the buffer lives inside the call and is not one of the context's allocations
-    int pack_staged(bool toBlocks, void *const *host) {
-        size_t perNode = 0;
-        for (int i = 0; i < 4; i++) if (host[i]) perNode += op_cols(i) * d.nv * sizeof(double);
-        const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)d.nodes, PACK_STAGING_BYTES / perNode));
-        char *stage = nullptr;
-        RN_HIP(hipMalloc((void **)&stage, (size_t)chunk * perNode));
-        hipError_t e = hipSuccess;
-        for (int n0 = 0; n0 < d.nodes && e == hipSuccess; n0 += chunk) {
-            const int cnt = std::min(chunk, d.nodes - n0);
-            void *dv[4] = {nullptr, nullptr, nullptr, nullptr};
-            size_t at = 0;
-            for (int i = 0; i < 4; i++) if (host[i]) { dv[i] = stage + at; at += (size_t)chunk * op_cols(i) * d.nv * sizeof(double); }
-            if (toBlocks)
-                for (int i = 0; i < 4 && e == hipSuccess; i++) if (host[i]) {
-                    const size_t per = op_cols(i) * d.nv * sizeof(double);
-                    e = hipMemcpyAsync(dv[i], (const char *)host[i] + (size_t)n0 * per, (size_t)cnt * per, hipMemcpyHostToDevice, stream);
-                }
-            if (e == hipSuccess) { pack_launch(toBlocks, true, dv, n0, cnt); e = hipGetLastError(); }
-            if (!toBlocks)
-                for (int i = 0; i < 4 && e == hipSuccess; i++) if (host[i]) {
-                    const size_t per = op_cols(i) * d.nv * sizeof(double);
-                    e = hipMemcpyAsync((char *)host[i] + (size_t)n0 * per, dv[i], (size_t)cnt * per, hipMemcpyDeviceToHost, stream);
-                }
-        }
-        const hipError_t es = hipStreamSynchronize(stream);    // (before the buffer goes: everything that uses it is on this stream)
-        (void)hipFree(stage);
-        RN_HIP(e);
-        RN_HIP(es);
-        return RN_OK;
-    }
-    // ---- scenario probabilities and tree errors in place (rn_set_tree_data, rn_set_tree_data_device, rn_get_tree_data; k_tree_data, k_misc.hpp) ----
-    bool lib_sharded() const { return nranks > 1 && !globalNode.empty() && d_gmap != nullptr; }   // made by rn_create_sharded
-    int refresh_h_prob() {
-        if (!hProbStale) return RN_OK;
-        RN_HIP(hipSetDevice(device));
-        if (d_prob64) {
-            RN_HIP(hipMemcpyAsync(h_prob.data(), d_prob64, (size_t)d.nodes * sizeof(double), hipMemcpyDeviceToHost, stream));
-            RN_HIP(hipStreamSynchronize(stream));
-        } else if (int rc = download(h_prob.data(), d_prob, (size_t)d.nodes)) return rc;
-        hProbStale = false;
-        return RN_OK;
-    }
-    void tree_data_launch(bool callerF64, const void *prob, const void *errD, const void *errP) {
-        TreeDataArgs a{};
-        a.prob = prob; a.errD = errD; a.errP = errP; a.ctxF64 = sizeof(T) == 8 ? 1 : 0; a.callerF64 = callerF64 ? 1 : 0;
-        a.gmap = lib_sharded() ? d_gmap : nullptr;
-        a.nodes = d.nodes; a.nd = d.nd; a.nu = d.nu;
-        a.dprob = d_prob; a.dsqrtp = d_sqrtp; a.derrD = d_errD; a.derrP = d_errP; a.prob64 = d_prob64; a.bad = d_treeBad;
-        a.nPar = lib_sharded() ? nCutPar : 0; a.cutFirst = cutFirstFull; a.cutC0 = d_cutC0; a.cutNc = d_cutNc; a.fullP = d_fullP; a.fullE = d_fullE;
-        a.momE = d_momE; a.momP = d_momP;
-        const long long work = std::max<long long>((long long)d.nodes * std::max(std::max(d.nd, d.nu), 1), (long long)a.nPar * (d.nd + 1));
-        const int blocks = (int)std::max<long long>(1, std::min<long long>(TREE_MAX_BLOCKS, (work + TREE_THREADS - 1) / TREE_THREADS));
-        hipLaunchKernelGGL(k_tree_data<>, dim3(blocks), dim3(TREE_THREADS), 0, stream, a);
-    }
-    int set_tree_data(size_t nodes, int callerPrec, bool dev, const void *prob, const void *errD, const void *errP) override {
-        const std::string what = dev ? "rn_set_tree_data_device" : "rn_set_tree_data";
-        RN_CHECK(prob || errD || errP, RN_E_ARG, what + ": all three arrays are NULL");
-        RN_CHECK(callerPrec == RN_F64 || callerPrec == RN_F32, RN_E_ARG, what + ": precision is RN_F32 or RN_F64");
-        const bool lib = lib_sharded();
-        RN_CHECK(nodes == (size_t)(lib ? fullNodes : d.nodes), RN_E_ARG,
-                 what + (lib ? ": nodes must be the FULL tree's node count on a context made by rn_create_sharded" : ": nodes must be the context's node count"));
-        RN_CHECK(!lib || !(prob || errD) || (cutContiguous && d_momE), RN_E_STATE, what + ": the children of a cut parent are not contiguous in the full tree");
-        RN_HIP(hipSetDevice(device));
-        const size_t elem = callerPrec == RN_F64 ? 8 : 4;
-        const void *src[3] = {prob, errD, errP};
-        const size_t cnt[3] = {nodes, nodes * (size_t)d.nd, nodes * (size_t)d.nu};
-        const char *shape[3] = {"nodes", "nodes x nd", "nodes x nu"};
-        if (dev) {
-            for (int i = 0; i < 3; i++)
-                if (src[i]) { if (int rc = check_device_array(src[i], cnt[i] * elem, elem, what, shape[i])) return rc; }
-        } else if (prob) {
-            const double *p = static_cast<const double *>(prob);
-            for (size_t i = 0; i < nodes; i++) RN_CHECK(p[i] > 0.0 && std::isfinite(p[i]), RN_E_ARG, what + ": probNode must be positive and finite");
-        }
-        if (prob && factored) { if (int rc = v_flush()) return rc; }      // (a pending v is the previous probabilities')
-        char *stage = nullptr;
-        if (dev) {
-            tree_data_launch(callerPrec == RN_F64, prob, errD, errP);
-        } else {   // the same kernel behind a staging copy that lives inside the call (not one of the context's allocations)
-            size_t bytes = 0, at[3] = {0, 0, 0};
-            for (int i = 0; i < 3; i++) if (src[i]) { at[i] = bytes; bytes += (cnt[i] * sizeof(double) + 255) / 256 * 256; }
-            RN_HIP(hipMalloc((void **)&stage, bytes));
-            const void *dv[3] = {nullptr, nullptr, nullptr};
-            hipError_t e = hipSuccess;
-            for (int i = 0; i < 3 && e == hipSuccess; i++) if (src[i]) {
-                dv[i] = stage + at[i];
-                e = hipMemcpyAsync(stage + at[i], src[i], cnt[i] * sizeof(double), hipMemcpyHostToDevice, stream);
-            }
-            if (e != hipSuccess) { (void)hipStreamSynchronize(stream); (void)hipFree(stage); RN_HIP(e); }
-            tree_data_launch(true, dv[0], dv[1], dv[2]);
-        }
-        hipError_t e = hipGetLastError();
-        int rcx = RN_OK;
-        if (e == hipSuccess && prob && factored) {      // what of the factor step depends on p, in the storage type in force
-            rcx = launch_expand();
-            if (rcx == RN_OK) rcx = refresh_bounds_copies();
-        }
-        if (!dev) {
-            const hipError_t es = hipStreamSynchronize(stream);    // (before the staging goes: everything that uses it is on this stream)
-            (void)hipFree(stage);
-            if (e == hipSuccess) e = es;
-        }
-        RN_HIP(e);
-        if (rcx != RN_OK) return rcx;
-        if (prob) {
-            if (dev) { treeCheckPending = true; hProbStale = true; }
-            else {
-                const double *p = static_cast<const double *>(prob);
-                for (int i = 0; i < d.nodes; i++) h_prob[i] = p[lib ? globalNode[i] : i];
-                treeCheckPending = false; treeBad = false; treeBadCount = 0; hProbStale = false;
-            }
-            affine_ready = false; linConstValid = false; aux_dirty = true;      // the affine terms and every control-step constant read p
-        }
-        if ((prob || errD) && cutStage > 0 && nranks > 1 && !lib) moments_set = false;   // sharded by hand: the caller's moments are the old tree's
-        return RN_OK;
-    }
-    int get_tree_data(size_t nodes, double *prob, double *errD, double *errP) override {
-        RN_CHECK(prob || errD || errP, RN_E_ARG, "rn_get_tree_data: all three arrays are NULL");
-        RN_CHECK(nodes == (size_t)d.nodes, RN_E_ARG, "rn_get_tree_data: nodes must be the context's (local) node count");
-        RN_HIP(hipSetDevice(device));
-        if (prob) {
-            if (d_prob64) {
-                RN_HIP(hipMemcpyAsync(prob, d_prob64, nodes * sizeof(double), hipMemcpyDeviceToHost, stream));
-                RN_HIP(hipStreamSynchronize(stream));
-            } else if (int rc = download(prob, d_prob, nodes)) return rc;
-        }
-        if (errD) { if (int rc = download(errD, d_errD, nodes * d.nd)) return rc; }
-        if (errP) { if (int rc = download(errP, d_errP, nodes * d.nu)) return rc; }
-        return RN_OK;
-    }
-    // ---- box and safety bounds per stage or per node in place (rn_set_bounds, rn_set_bounds_device, rn_get_bounds; k_tree_data, k_misc.hpp;
-    // replaces Engine.cuh:294-314 getSysXmin() ... getSysUmax() and Engine.cu preconditionConstraintX/U) ----
-    void bounds_launch(int gran, bool callerF64, const void *const *b) {
-        TreeDataArgs a{};
-        a.ctxF64 = sizeof(T) == 8 ? 1 : 0; a.callerF64 = callerF64 ? 1 : 0;
-        a.nodes = d.nodes; a.nd = d.nd; a.nu = d.nu; a.nx = d.nx; a.ny = ny;
-        for (int i = 0; i < 5; i++) { a.bnd[i] = b[i]; a.bndCopy[i] = d_bnd[i]; }
-        a.bRows = (int)bounds_rows(gran); a.bRowStage = gran == RN_BOUNDS_PER_STAGE ? 1 : 0; a.bRowNode = gran == RN_BOUNDS_PER_NODE ? 1 : 0;
-        a.stageOf = d_stageOf; a.sqrtpIn = d_sqrtp; a.dy = d_dy;
-        a.blo = d_bloG[gran]; a.bhi = d_bhiG[gran]; a.lo = d_lo; a.hi = d_hi;
-        const long long work = (long long)d.nodes * ny;
-        const int blocks = (int)std::max<long long>(1, std::min<long long>(BOUNDS_MAX_BLOCKS, (work + TREE_THREADS - 1) / TREE_THREADS));
-        hipLaunchKernelGGL(k_tree_data<>, dim3(blocks), dim3(TREE_THREADS), 0, stream, a);
-    }
-    int set_bounds(int gran, size_t rows, int callerPrec, bool dev, const void *const *b) override {
-        const std::string what = dev ? "rn_set_bounds_device" : "rn_set_bounds";
-        RN_CHECK(factored, RN_E_STATE, what + " before rn_factor_step");
-        RN_CHECK(bounds::known(gran), RN_E_ARG, what + ": granularity is RN_BOUNDS_SHARED, _PER_STAGE or _PER_NODE");
-        RN_CHECK(callerPrec == RN_F64 || callerPrec == RN_F32, RN_E_ARG, what + ": precision is RN_F32 or RN_F64");
-        RN_CHECK(rows == bounds_rows(gran), RN_E_ARG, what + ": rows must be 1 (shared), dims.N (per stage) or the context's (local) node count (per node)");
-        RN_CHECK(bounds::table_fits(rows, ny), RN_E_ARG, what + ": the table does not fit a 32-bit index");
-        int given = 0;
-        for (int i = 0; i < 5; i++) given += b[i] != nullptr;
-        RN_CHECK(given > 0, RN_E_ARG, what + ": all five arrays are NULL");
-        RN_CHECK(gran == boundsGran || given == 5, RN_E_ARG, what + ": a call that changes the granularity needs all five arrays");
-        RN_HIP(hipSetDevice(device));
-        const int nx = d.nx, nu = d.nu;
-        const size_t elem = callerPrec == RN_F64 ? 8 : 4;
-        const size_t cnt[5] = {rows * nx, rows * nx, rows * nx, rows * nu, rows * nu};
-        const char *shape[5] = {"rows x nx", "rows x nx", "rows x nx", "rows x nu", "rows x nu"};
-        if (dev) {
-            for (int i = 0; i < 5; i++)
-                if (b[i]) { if (int rc = check_device_array(b[i], cnt[i] * elem, elem, what, shape[i])) return rc; }
-        } else {
-            // every value finite, lower <= upper pair by pair; the half of a pair that was not given as the context holds it (bounds.hpp)
-            const double *hb[5], *cur[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-            for (int i = 0; i < 5; i++) hb[i] = static_cast<const double *>(b[i]);
-            bool need[5];
-            bounds::needed_from_context(hb, need);
-            std::vector<double> held[5];
-            if (need[0] || need[1] || need[3] || need[4]) {
-                double *out[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-                for (int i = 0; i < 5; i++) if (need[i]) { held[i].resize(cnt[i]); out[i] = held[i].data(); cur[i] = out[i]; }
-                if (int rc = get_bounds(rows, out)) return rc;
-            }
-            const int bad = bounds::validate(rows, nx, nu, hb, cur);
-            RN_CHECK(bad != bounds::NOT_FINITE, RN_E_ARG, what + ": a bound is not finite");
-            RN_CHECK(bad != bounds::XMIN_ABOVE_XMAX, RN_E_ARG, what + ": xmin > xmax");
-            RN_CHECK(bad != bounds::UMIN_ABOVE_UMAX, RN_E_ARG, what + ": umin > umax");
-        }
-        if (!d_bloG[gran]) {      // the first set at this granularity: its table, kept from here on
-            if (int rc = dalloc(&d_bloG[gran], rows * (size_t)ny)) return rc;
-            if (int rc = dalloc(&d_bhiG[gran], rows * (size_t)ny)) return rc;
-        }
-        char *stage = nullptr;
-        if (dev) {
-            bounds_launch(gran, callerPrec == RN_F64, b);
-        } else {   // the same kernel behind a staging copy that lives inside the call (not one of the context's allocations)
-            size_t bytes = 0, at[5] = {0, 0, 0, 0, 0};
-            for (int i = 0; i < 5; i++) if (b[i]) { at[i] = bytes; bytes += (cnt[i] * sizeof(double) + 255) / 256 * 256; }
-            RN_HIP(hipMalloc((void **)&stage, bytes));
-            const void *dv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-            hipError_t e = hipSuccess;
-            for (int i = 0; i < 5 && e == hipSuccess; i++) if (b[i]) {
-                dv[i] = stage + at[i];
-                e = hipMemcpyAsync(stage + at[i], b[i], cnt[i] * sizeof(double), hipMemcpyHostToDevice, stream);
-            }
-            if (e != hipSuccess) { (void)hipStreamSynchronize(stream); (void)hipFree(stage); RN_HIP(e); }
-            bounds_launch(gran, true, dv);
-        }
-        hipError_t e = hipGetLastError();
-        if (!dev) {
-            const hipError_t es = hipStreamSynchronize(stream);    // (before the staging goes: everything that uses it is on this stream)
-            (void)hipFree(stage);
-            if (e == hipSuccess) e = es;
-        }
-        RN_HIP(e);
-        d_blo = d_bloG[gran]; d_bhi = d_bhiG[gran]; boundsGran = gran;
-        return RN_OK;
-    }
-    int get_bounds_layout(int *gran, size_t *rows) override {
-        RN_CHECK(gran && rows, RN_E_ARG, "rn_get_bounds_layout: null output");
-        RN_CHECK(factored, RN_E_STATE, "rn_get_bounds_layout before rn_factor_step");
-        *gran = boundsGran; *rows = bounds_rows(boundsGran);
-        return RN_OK;
-    }
-    int get_bounds(size_t rows, double *const *out) override {
-        RN_CHECK(factored, RN_E_STATE, "rn_get_bounds before rn_factor_step");
-        RN_CHECK(out[0] || out[1] || out[2] || out[3] || out[4], RN_E_ARG, "rn_get_bounds: all five arrays are NULL");
-        RN_CHECK(rows == bounds_rows(boundsGran), RN_E_ARG, "rn_get_bounds: rows must be what rn_get_bounds_layout reports");
-        RN_HIP(hipSetDevice(device));
-        const int nx = d.nx, nu = d.nu;
-        std::vector<double> lo(rows * (size_t)ny), hi(rows * (size_t)ny);
-        if (int rc = download(lo.data(), d_blo, lo.size())) return rc;
-        if (int rc = download(hi.data(), d_bhi, hi.size())) return rc;
-        bounds::unpack_tables(rows, nx, nu, lo.data(), hi.data(), out);
         return RN_OK;
     }
     // rn_create_sharded, after the moments: what k_tree_data needs to recompute them (and the full-tree row of every local node)
