@@ -379,7 +379,10 @@ int rn_get_operator(rn_ctx *ctx, int op_id, int node, double *host, size_t n);
  * blocks solveStep multiplies with (SmpcController.cu:617-638); the next sweep uses them.  After rn_factor_step; a later rn_factor_step
  * recomputes every block, and so does a later rn_set_tree_data / rn_set_tree_data_device that gives probNode.  RN_OPS_AUTO contexts switch to dense storage on the first call; RN_OPS_STRUCTURED contexts (no per-node
  * blocks by request): RN_E_STATE.  Omega_i, Theta_i, G_i are shared matrices scaled by p_i here (K identical copies in the reference,
- * Engine.cu:306-308): RN_E_ARG.  A context with RN_STORE_F32 blocks rounds the caller's values to the nearest fp32 on upload. */
+ * Engine.cu:306-308): RN_E_ARG.  A context with RN_STORE_F32 blocks rounds the caller's values to the nearest fp32 on upload.
+ * Block entries must be finite.  The sweep does not read the operator columns whose entry of the dual vector is zero -- in spans of G columns
+ * (rn_get_kernel_info), and only spans in which every entry is +-0: for finite blocks that changes no bit of any result; an Inf / NaN entry in
+ * such a column, which used to turn the node's products into NaN (Inf * 0), is not seen and the sums stay finite. */
 int rn_set_operator(rn_ctx *ctx, int op_id, int node, const double *host, size_t n);
 /* ALL per-node blocks in one call, as the reference's four arrays (Engine.cuh getMatPhi(), getMatPsi(), getMatD(), getMatF(): devMatPhi
  * and devMatD are [node][2nx columns][nv], devMatPsi and devMatF [node][nu columns][nv], col-major, ld = nv, Engine.cu:166-205) -- for
@@ -431,7 +434,11 @@ int rn_profile_read(rn_ctx *ctx, double ms[4], long launches[4]);
  * class 1 of rn_profile_read. */
 int rn_profile_read_collective(rn_ctx *ctx, double *ms, long *launches);
 /* algorithmic HBM bytes of ONE launch of the dominant kernels, as defined in DESIGN.md (RN_STORE_F32 blocks under fp64 iterates: the
- * block entries at 4 bytes, the vectors at 8) */
+ * block entries at 4 bytes, the vectors at 8).  backwardStageBytesTotal: the streaming sweep reads only the operator spans (G consecutive
+ * columns, rn_get_kernel_info) that meet a nonzero entry of the dual vector, so its block bytes are a property of the data -- the figure is that of
+ * the context's MOST RECENT streaming launch: live whole spans x G x LD x bytes per block entry (LD: the column's rows padded to 16 bytes), a live
+ * ragged last span at its ny % G columns, plus the vectors (ny + 2 nv + nx reals per node).  Before the first sweep of a context the dense figure
+ * (every column of every block).  Synchronises the context's stream and copies one small record per workgroup. */
 int rn_algorithmic_bytes(const rn_ctx *ctx, double *backwardStageBytesTotal, double *dualUpdateBytes);
 /* which kernels an iteration of this context launches: info = {1 if k_dual_stage is the main pass of the fused dual update
  * (0: the flat k_dual_fused), its workgroups, vectors per thread, pipeline depth, k_stream_gemv columns per span, slots per

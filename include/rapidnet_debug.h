@@ -66,7 +66,8 @@ enum {
     RN_KNOB_TUNE_BIAS_US = 11,     /* rn_exchange_autotune, test of the selection: microseconds per iteration added to THIS rank's measured one-shot time */
     RN_KNOB_STRUCT_LINEAR = 12,    /* structured mode: 0 = the first product k_gemm_prep_m2 in front of the chain walks instead of the linear form (k_up_chain_lin); 2 = the linear form without the chain walk riding in the fused walk + dual update; 3 = the linear form with the subtree sums of beta walked and multiplied in every iteration instead of once per control step; 4 = that constant, but v_i and [L v_i; B L v_i] as two products instead of one with the composite operator; 5 = the composite operator without the forward walk's affine terms in its constant operand */
     RN_KNOB_FUSE_SPLIT = 13,       /* fused forward walk + dual update: workgroups per chain (1 .. chain length); 0 = one per chain and only where the chains fill 3/4 of the CUs (round 6's first rule) */
-    RN_KNOB_COUNT = 14
+    RN_KNOB_STREAM_SKIP = 14,      /* k_stream_gemv: 0 = every span of every operator block is walked; 1 (default) = only the spans that meet a nonzero entry of the dual vector (bitwise the same results) */
+    RN_KNOB_COUNT = 15
 };
 int rn_debug_set_knob(rn_ctx *ctx, int knob, int value);
 
@@ -76,6 +77,13 @@ int rn_debug_set_knob(rn_ctx *ctx, int knob, int value);
  * span at which the second workgroup starts (0 without a split).  twoPerCU: 1 = the instantiation that leaves room for two workgroups
  * per CU.  numCUs: the device's compute units, valid from rn_create on.  Reads only: nothing that is computed changes. */
 int rn_debug_stream_info(rn_ctx *ctx, int info[4]);
+
+/* What the context's most recent launch of k_stream_gemv walked: out = {live spans, spans, live columns, columns}, summed over the blocks of the
+ * context.  A span (G consecutive operator columns, rn_get_kernel_info) is live when one of its entries of the dual vector the sweep is evaluated at
+ * has any bit but the sign set (-0.0 is zero, a denormal is live; a pair of sweeps in one pass: in either vector); a live column likewise.  With
+ * RN_KNOB_STREAM_SKIP = 0 every span is walked and counted.  Synchronises the context's stream, copies one record per workgroup and sums on the host.
+ * RN_E_STATE before the first sweep and in the structured mode (no blocks). */
+int rn_debug_stream_live(rn_ctx *ctx, long long out[4]);
 
 /* The gradient restart test (rn_set_restart, rapidnet.h) alone: runs k_restart_test on the context's current w (the last sweep's input, what
  * RN_BUF_ACC_* shows), y+ and y and returns out = {g, na2, nb2} -- the kernel can be checked without running a solve.  Allocates the kernel's

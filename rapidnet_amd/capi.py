@@ -31,7 +31,7 @@ BOUNDS_SHARED, BOUNDS_PER_STAGE, BOUNDS_PER_NODE = 0, 1, 2      # rn_set_bounds
 BOUNDS = {"shared": BOUNDS_SHARED, "stage": BOUNDS_PER_STAGE, "node": BOUNDS_PER_NODE}
 # include/rapidnet_debug.h, RN_KNOB_*
 KNOBS = {k: i for i, k in enumerate(("dual_trips", "dual_pipe", "vlv_wide", "slab_pipe", "slab_frag", "unscaled_walk", "stream_two_per_cu",
-                                     "stream_split", "nama_pair", "ls_sequential", "value_mfma", "tune_bias_us", "struct_linear", "fuse_split"))}
+                                     "stream_split", "nama_pair", "ls_sequential", "value_mfma", "tune_bias_us", "struct_linear", "fuse_split", "stream_skip"))}
 EXCHANGE_COLLECTIVE, EXCHANGE_ONESHOT, EXCHANGE_AUTO = 0, 1, 2
 
 # every symbol include/rapidnet.h (the boundary) and include/rapidnet_debug.h (test hooks, rn_debug_*) declare
@@ -51,7 +51,7 @@ SYMBOLS = [
     "rn_debug_set_allreduce", "rn_debug_local_group_create", "rn_debug_local_group_join", "rn_debug_local_group_destroy",
     "rn_guard_check", "rn_device_memory_info", "rn_reserve_iterations", "rn_profile_read_collective", "rn_debug_inject_allocation", "rn_guard_report", "rn_debug_guard_poke",
     "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_set_bounds", "rn_set_bounds_device", "rn_get_bounds_layout", "rn_get_bounds", "rn_debug_cut_moments",
-    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test",
+    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live",
 ]
 
 
@@ -242,6 +242,7 @@ def load():
     lib.rn_set_fused_walk_dual.argtypes = [vp, ip]
     lib.rn_debug_set_knob.argtypes = [vp, ip, ip]
     lib.rn_debug_stream_info.argtypes = [vp, dp]
+    lib.rn_debug_stream_live.argtypes = [vp, dp]
     lib.rn_profile_read_collective.argtypes = [vp, dp, dp]
     lib.rn_set_tree_data.argtypes = [vp, C.c_size_t, dp, dp, dp]
     lib.rn_set_tree_data_device.argtypes = [vp, C.c_size_t, ip, vp, vp, vp]
@@ -811,6 +812,12 @@ class Solver:
         out = np.zeros(4, dtype=np.int32)
         self._check(self.lib.rn_debug_stream_info(self.h, out.ctypes.data))
         return dict(zip(("splitFirst", "splitSpanHalf", "twoPerCU", "numCUs"), (int(v) for v in out)))
+
+    def streamLive(self):
+        """rn_debug_stream_live (include/rapidnet_debug.h): what the most recent launch of k_stream_gemv walked, summed over the blocks."""
+        out = np.zeros(4, dtype=np.int64)
+        self._check(self.lib.rn_debug_stream_live(self.h, out.ctypes.data))
+        return dict(zip(("liveSpans", "spans", "liveColumns", "columns"), (int(v) for v in out)))
 
     def debugGuardPoke(self, nbytes):
         self._check(self.lib.rn_debug_guard_poke(self.h, int(nbytes)))

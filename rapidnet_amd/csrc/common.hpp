@@ -418,6 +418,9 @@ struct StreamSplit {
     int first;        // first block of the split round (= the number of blocks: no split)
     int spanHalf;     // spans of the first half (a whole number of groups)
     T *my2;           // [blocks - first][2 nv] partial sums of the second halves
+    // the skip of spans that meet no nonzero entry of w (k_stream.hpp, stream_walk): 0 = every span is walked
+    int skip;
+    int2 *live;       // [workgroups] what each workgroup walked: {spans, columns | ragged last span among them << 30} (nullptr: not recorded)
 };
 
 // Bookkeeping of the PREVIOUS iteration's fused dual update (optimistic modes: no decision launch of its own): folds the

@@ -22,7 +22,7 @@ namespace rn {
 // FETCH_SIZE showed 4.35 GB per launch against 4.09 GB algorithmic; with G = 8 (784 slots = 98 lines, NL = 2, 77 % of
 // the lanes busy) it is 4.14 GB and the kernel 6 % faster.  Loads are non-temporal (A is read once per iteration and is
 // far larger than the 256 MiB Infinity Cache) and double-buffered in groups of D spans (one 8-wave workgroup per CU
-// with 10 x 16 B per lane in flight measured best: 512 threads, D = 5).  Also emits a_i = F_i' xi_i (F_i is diagonal:
+// with 10 x 16 B per lane in flight measured best: 512 threads, D = 5; the two-per-CU instantiation: D = 4).  Also emits a_i = F_i' xi_i (F_i is diagonal:
 // Utilities.cu:33-58).
 // HBM bytes per node: LD*ny*sizeof(T) + (ny + 2nv + nx)*sizeof(T).
 // SPLIT = false is the kernel as it always was (span0 = 0, every block one workgroup): the instantiation the unsplit launches run --
@@ -32,6 +32,173 @@ namespace rn {
 // bound by the blocks' bytes, so the second product rides for free): the second vector r2.w, its results in r2.my / r2.qa.  Each
 // right-hand side's sums are formed exactly as the one-vector kernel forms them (same order over the columns): bitwise the results
 // of two launches.  Unsplit launches with w in memory only.
+// THE SKIP (sp.skip != 0).  Column c of A_i only ever meets w_i[c], and most entries of an accelerated dual are exact zeros (constraints that
+// were never violated: the sparse active set of the problem).  A span whose G entries of w are all +-0 adds a * (+-0) = +-0 to partial sums
+// that started at +0 -- x + (+-0) = x for every x but -0, and a partial cannot become -0 from a +0 start -- so the walk leaves such spans
+// out: for finite block entries the outputs are the bits of the walk over every span.  (An Inf / NaN block entry against a zero dual gave NaN
+// and now gives the finite sum.)  Any bit but the sign makes an entry live: -0.0 is zero, a denormal is not.
+//   While the workgroup copies w into LDS every wave ballots "entry is live" over its 64 columns into sh_nz (one word per 64 columns, one zero
+// word of padding); behind the barrier every wave derives for itself, one lane per span, which spans of [span0, span1) are live: one ballot
+// per chunk of 64 spans, a wave-uniform mask -- no second barrier, no list in LDS.  Groups of D LIVE spans are double-buffered as the
+// groups of D consecutive spans were (scalar span index, steady state without a branch); the live count mod D is a partial group in FRONT of the
+// full ones, and the ragged last span of ny % G columns, where live, a guarded load by itself behind them.  A thread keeps its slots and its rows
+// and meets the live spans in increasing order.  The first group cannot be requested before
+// w has arrived any more.  sp.skip == 0: every span is walked (the mask is "span exists").
+// Returns what was walked: spans, columns, and whether the ragged last span was among them.
+__device__ __forceinline__ bool stream_nz(double v) { return ((unsigned long long)__double_as_longlong(v) << 1) != 0ull; }
+__device__ __forceinline__ bool stream_nz(float v) { return (__float_as_uint(v) << 1) != 0u; }
+template <typename T, typename VT, int VPL, int NL, int D, int NR>
+__device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *sh_y, const T *sh_y2, const unsigned long long *sh_nz, int skip, int span0, int span1, int G, int ny,
+                                            int spanSlots, long long blockSlots, const int (&off)[NL], const int (&cj)[NL], const T (&msk)[NL], T (&part)[NL][VPL],
+                                            T (&part2)[NR == 2 ? NL : 1][VPL], int &liveSpans, int &liveCols, int &liveRagged) {
+    const int lane = threadIdx.x & 63;
+    const int rag = (ny % G != 0 && span1 * G > ny) ? ny / G : -1;      // the ragged last span, where this range holds it
+    VT bufA[D][NL], bufB[D][NL];
+    int sA[D], sB[D];
+    liveSpans = 0; liveCols = 0; liveRagged = 0;
+    // a load's address is (scalar) start of the span + (32-bit, per lane) byte offset of the slot: one address register per slot, whatever the span
+    const char *const Abb = reinterpret_cast<const char *>(Ab);
+    const unsigned spanBytes = (unsigned)spanSlots * 16u;
+    unsigned offB[NL];
+#pragma unroll
+    for (int j = 0; j < NL; j++) offB[j] = (unsigned)off[j] * 16u;
+#define RN_POP(sv, d) { sv[d] = __builtin_amdgcn_readfirstlane(cb + __builtin_ctzll(mf)); mf &= mf - 1ull; }
+#define RN_LOADG(buf, sv)                                                                                              \
+    _Pragma("unroll") for (int d = 0; d < D; d++) {                                                                    \
+        RN_POP(sv, d)                                                                                                  \
+        _Pragma("unroll") for (int j = 0; j < NL; j++)                                                                 \
+            buf[d][j] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (size_t)sv[d] * spanBytes + offB[j])); \
+    }
+#define RN_USEG(buf, sv)                                                                                               \
+    _Pragma("unroll") for (int d = 0; d < D; d++)                                                                      \
+        _Pragma("unroll") for (int j = 0; j < NL; j++) {                                                               \
+            const T yc = sh_y[sv[d] * G + cj[j]] * msk[j];                                                             \
+            _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] += (T)buf[d][j][e] * yc;                        \
+            if (NR == 2) {      /* (fp32 blocks under fp64 sums: the lane's values are converted once and meet both columns) */ \
+                const T yc2 = sh_y2[sv[d] * G + cj[j]] * msk[j];                                                       \
+                _Pragma("unroll") for (int e = 0; e < VPL; e++) part2[j][e] += (T)buf[d][j][e] * yc2;                  \
+            }                                                                                                          \
+        }
+    // the partial group a chunk STARTS with: its first nHead (< D) live spans, whole ones
+#define RN_LOADH(buf, sv)                                                                                              \
+    _Pragma("unroll") for (int d = 0; d < D - 1; d++)                                                                  \
+        if (d < nHead) {                                                                                               \
+            RN_POP(sv, d)                                                                                              \
+            _Pragma("unroll") for (int j = 0; j < NL; j++)                                                             \
+                buf[d][j] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (size_t)sv[d] * spanBytes + offB[j])); \
+        }
+#define RN_USEH(buf, sv)                                                                                               \
+    _Pragma("unroll") for (int d = 0; d < D - 1; d++)                                                                  \
+        if (d < nHead) {                                                                                               \
+            _Pragma("unroll") for (int j = 0; j < NL; j++) {                                                           \
+                const T yc = sh_y[sv[d] * G + cj[j]] * msk[j];                                                         \
+                _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] += (T)buf[d][j][e] * yc;                    \
+                if (NR == 2) {                                                                                         \
+                    const T yc2 = sh_y2[sv[d] * G + cj[j]] * msk[j];                                                   \
+                    _Pragma("unroll") for (int e = 0; e < VPL; e++) part2[j][e] += (T)buf[d][j][e] * yc2;              \
+                }                                                                                                      \
+            }                                                                                                          \
+        }
+    for (int cb = span0; cb < span1; cb += 64) {      // chunks of 64 spans: a group never crosses a chunk
+        const int s = cb + lane;
+        int cols = 0;
+        if (s < span1) {
+            const int c0 = s * G;
+            if (skip) {      // the span's G bits of the column mask (they may straddle two words)
+                const int sh = c0 & 63;
+                const unsigned long long lo = sh_nz[c0 >> 6], hi = sh_nz[(c0 >> 6) + 1];
+                unsigned long long bits = (lo >> sh) | (sh ? hi << (64 - sh) : 0ull);
+                if (G < 64) bits &= (1ull << G) - 1ull;
+                cols = __popcll(bits);
+            } else {
+                cols = ny - c0 < G ? ny - c0 : G;
+            }
+        }
+        const unsigned long long m = __ballot(cols > 0);
+        liveSpans += __popcll(m);
+        if (threadIdx.x < 64) {      // (the record: the first wave's lane 0 keeps it)
+            int t = cols;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+            liveCols += t;
+        }
+        const unsigned long long ragBit = (rag >= cb && rag < cb + 64) ? (m & (1ull << (rag - cb))) : 0ull;
+        unsigned long long mf = m & ~ragBit;
+        const int nLive = __popcll(mf), nGroups = nLive / D, nHead = nLive - nGroups * D;
+        // the live count mod D goes FIRST (the spans are met in increasing order either way), as a partial group in the second buffer, with the
+        // first full group requested right behind it: the chunk's last loads are then those of a full group
+        RN_LOADH(bufB, sB)
+        if (nGroups > 0) RN_LOADG(bufA, sA)
+        RN_USEH(bufB, sB)
+        if (nGroups > 0) {
+            int g = 0;
+            // steady state has no branch inside, so the compiler's vmcnt waits are exact: while group g is consumed, group
+            // g+1 (and then g+2) is in flight
+            for (; g + 2 < nGroups; g += 2) {
+                RN_LOADG(bufB, sB)
+                RN_USEG(bufA, sA)
+                RN_LOADG(bufA, sA)
+                RN_USEG(bufB, sB)
+            }
+            if (g + 1 < nGroups) {
+                RN_LOADG(bufB, sB)
+                RN_USEG(bufA, sA)
+                RN_USEG(bufB, sB)
+            } else {
+                RN_USEG(bufA, sA)
+            }
+        }
+        if (ragBit) {      // the ragged last span (ny % G columns), where it is live: guarded, by itself, last
+            liveRagged = 1;
+            VT bufR[NL];
+#pragma unroll
+            for (int j = 0; j < NL; j++) {
+                const bool ok = msk[j] != (T)0 && rag * G + cj[j] < ny;      // (a column of the block: the slot lies inside it)
+                bufR[j] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (size_t)rag * spanBytes + (ok ? offB[j] : 0u)));
+            }
+#pragma unroll
+            for (int j = 0; j < NL; j++) {
+                const int c = rag * G + cj[j];
+                const bool ok = msk[j] != (T)0 && c < ny;
+                const T yc = ok ? sh_y[c] : (T)0;
+#pragma unroll
+                for (int e = 0; e < VPL; e++) part[j][e] += (T)bufR[j][e] * yc;
+                if (NR == 2) {
+                    const T yc2 = ok ? sh_y2[c] : (T)0;
+#pragma unroll
+                    for (int e = 0; e < VPL; e++) part2[j][e] += (T)bufR[j][e] * yc2;
+                }
+            }
+        }
+    }
+#undef RN_POP
+#undef RN_LOADG
+#undef RN_USEG
+#undef RN_LOADH
+#undef RN_USEH
+}
+// the workgroup's copy of w (and of the second right-hand side) into LDS, and the column mask sh_nz of the skip beside it: every wave ballots its
+// 64 columns (trip count the same for every thread: (ny + 63) / 64 + 1 words, the last one zero).  w0 / w20: the first STREAM_THREADS entries,
+// requested by the caller in front of everything else.
+template <typename T, int NR>
+__device__ __forceinline__ void stream_stage_w(const T *__restrict__ w, const T *__restrict__ w2, T w0, T w20, T *sh_y, T *sh_y2, unsigned long long *sh_nz, int ny) {
+    const int tid = threadIdx.x, nzWords = (ny + 63) / 64 + 1;
+    for (int c0 = 0; (c0 >> 6) < nzWords; c0 += STREAM_THREADS) {
+        const int c = c0 + tid;
+        T v = 0, v2 = 0;
+        if (c < ny) {
+            v = c0 == 0 ? w0 : w[c];
+            sh_y[c] = v;
+            if (NR == 2) { v2 = c0 == 0 ? w20 : w2[c]; sh_y2[c] = v2; }
+        }
+        const unsigned long long b = __ballot(stream_nz(v) || (NR == 2 && stream_nz(v2)));
+        if ((tid & 63) == 0 && (c >> 6) < nzWords) sh_nz[c >> 6] = b;
+    }
+}
+// what a workgroup walked, for rn_debug_stream_live / rn_algorithmic_bytes: one 8-byte store per workgroup, overwritten by every launch
+__device__ __forceinline__ void stream_record(int2 *live, int liveSpans, int liveCols, int liveRagged) {
+    if (threadIdx.x == 0 && live) live[blockIdx.x] = make_int2(liveSpans, liveCols | (liveRagged << 30));
+}
 template <typename T>
 struct StreamRhs2 { const T *w; T *my; T *qa; };
 template <typename T, int NL, bool SPLIT, int NR = 1>
@@ -41,7 +208,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
     // (two right-hand sides in fp32: 4 values per slot x 2 accumulator sets -- a group one span shorter (NL = 4: one span per group)
     //  keeps the kernel inside its registers: 150-172 instead of 256 + 20-28 bytes of scratch per lane with the full depth.  The
     //  order in which a thread meets its columns does not depend on the depth: same sums, bit for bit)
-    constexpr int VPL = Slot<T>::N, D0 = NL <= 2 ? RN_STREAM_D : RN_STREAM_D_WIDE, D = (NR == 2 && sizeof(T) == 4) ? (NL == 4 ? 1 : D0 - 1) : D0;
+    constexpr int VPL = Slot<T>::N, D0 = NL <= 2 ? (SPLIT ? RN_STREAM_D - 1 : RN_STREAM_D) : RN_STREAM_D_WIDE, D = (NR == 2 && sizeof(T) == 4) ? (NL == 4 ? 1 : D0 - 1) : D0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *sh_y = reinterpret_cast<T *>(smem_raw);          // ny (+ G of zero padding is not needed: guarded reads)
     T *sh_red = sh_y + ((a.ny + 3) & ~3);               // G * LD
@@ -74,28 +241,8 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
     for (int j = 0; j < NL; j++)
 #pragma unroll
         for (int e = 0; e < VPL; e++) { part[j][e] = 0; if (NR == 2) part2[j][e] = 0; }
-    const int nFull = (ny / G < span1 ? ny / G : span1) - span0;   // spans of this workgroup made of G whole columns
-    const int nGroups = nFull / D;
-    VT bufA[D][NL], bufB[D][NL];
-#define RN_LOADG(buf, g_)                                                                                              \
-    _Pragma("unroll") for (int d = 0; d < D; d++)                                                                      \
-        _Pragma("unroll") for (int j = 0; j < NL; j++)                                                                 \
-            buf[d][j] = __builtin_nontemporal_load(Ab + (size_t)(span0 + (g_) * D + d) * spanSlots + off[j]);
-#define RN_USEG(buf, g_)                                                                                               \
-    _Pragma("unroll") for (int d = 0; d < D; d++)                                                                      \
-        _Pragma("unroll") for (int j = 0; j < NL; j++) {                                                               \
-            const T yc = sh_y[(span0 + (g_) * D + d) * G + cj[j]] * msk[j];                                            \
-            _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] += buf[d][j][e] * yc;                           \
-            if (NR == 2) {                                                                                             \
-                const T yc2 = sh_y2[(span0 + (g_) * D + d) * G + cj[j]] * msk[j];                                      \
-                _Pragma("unroll") for (int e = 0; e < VPL; e++) part2[j][e] += buf[d][j][e] * yc2;                     \
-            }                                                                                                          \
-        }
-    // Prologue.  A wave's loads return in order, so everything the prologue needs is requested FIRST and the first group of
-    // A_i (which does not depend on y) right behind it: the prologue's arithmetic then runs while that group streams in, and
-    // nothing after the barrier has to queue a small load behind the stream.  The first group is requested unconditionally
-    // (clamped into the block when the block is shorter than a group): a branch around it makes the compiler's wait-count
-    // bookkeeping merge two paths and fall back to "wait for everything" in front of the prologue's arithmetic.
+    // Prologue.  A wave's loads return in order, so everything the prologue needs is requested first; the blocks' first group follows once w has
+    // said which spans are live (stream_walk).
     const bool has0 = tid < ny;
     const size_t i0 = (size_t)node * ny + (has0 ? tid : 0);
     // stage of the node by arithmetic in the chain region (every stage >= chainStage has K nodes: no table load in front of
@@ -108,27 +255,11 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
     const T w0a = a.w[i0];      // the y column: the accelerated dual the sweep is evaluated at
     T w20 = 0;
     if (NR == 2) w20 = r2.w[i0];
-    asm volatile("" ::: "memory");   // keep the request order: the compiler otherwise hoists the group's loads above the small ones
-    {
-        const int lastSlot = (int)blockSlots - 1;
-#pragma unroll
-        for (int d = 0; d < D; d++)
-#pragma unroll
-            for (int j = 0; j < NL; j++) {
-                const int sl = (span0 + d) * spanSlots + off[j];
-                bufA[d][j] = __builtin_nontemporal_load(Ab + (sl < lastSlot ? sl : lastSlot));
-            }
-    }
-    asm volatile("" ::: "memory");
     // a_i is STORED AT THE END of the kernel: stores count in the same in-order counter as the loads, so a store issued
     // here has to be acknowledged before the wave may consume any group of A_i requested after it
     T qa0 = 0, qa02 = 0;
-    if (has0) sh_y[tid] = w0a;
-    for (int c = tid + STREAM_THREADS; c < ny; c += STREAM_THREADS) sh_y[c] = a.w[(size_t)node * ny + c];
-    if (NR == 2) {
-        if (has0) sh_y2[tid] = w20;
-        for (int c = tid + STREAM_THREADS; c < ny; c += STREAM_THREADS) sh_y2[c] = r2.w[(size_t)node * ny + c];
-    }
+    unsigned long long *sh_nz = reinterpret_cast<unsigned long long *>(sh_y + (size_t)NR * (((ny + 3) & ~3) + (size_t)G * LD));   // (ny + 63) / 64 + 1 words
+    stream_stage_w<T, NR>(a.w + (size_t)node * ny, NR == 2 ? r2.w + (size_t)node * ny : nullptr, w0a, w20, sh_y, sh_y2, sh_nz, ny);
     __syncthreads();
     // a_i = F_i' xi_i = sqrt(p_i) (d_x o xi_box + d_xs o xi_safe)      (a split block: written by its first half)
     if (tid < nx) qa0 = stream_qa_elem(spn, dq0, sh_y[tid], dq1, sh_y[nx + tid]);
@@ -139,44 +270,8 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
         for (int t = tid + STREAM_THREADS; t < nx; t += STREAM_THREADS)
             r2.qa[(size_t)node * nx + t] = stream_qa_elem(spn, dyRow[t], sh_y2[t], dyRow[nx + t], sh_y2[nx + t]);
     }
-    if (nGroups > 0) {
-        int g = 0;
-        // steady state has no branch inside, so the compiler's vmcnt waits are exact: while group g is consumed, group
-        // g+1 (and then g+2) is in flight
-        for (; g + 2 < nGroups; g += 2) {
-            RN_LOADG(bufB, g + 1)
-            RN_USEG(bufA, g)
-            RN_LOADG(bufA, g + 2)
-            RN_USEG(bufB, g + 1)
-        }
-        if (g + 1 < nGroups) {
-            RN_LOADG(bufB, g + 1)
-            RN_USEG(bufA, g)
-            RN_USEG(bufB, g + 1)
-        } else {
-            RN_USEG(bufA, g)
-        }
-    }
-#undef RN_LOADG
-#undef RN_USEG
-    // remaining whole spans and the last, partial one (ny % G columns): guarded
-    for (int s = span0 + nGroups * D; s < span1; s++) {
-#pragma unroll
-        for (int j = 0; j < NL; j++) {
-            const int c = s * G + cj[j];
-            const long long slot = (long long)s * spanSlots + off[j];
-            const bool live = msk[j] != (T)0 && c < ny && slot < blockSlots;
-            const VT v = __builtin_nontemporal_load(Ab + (live ? slot : 0));
-            const T yc = live ? sh_y[c] : (T)0;
-#pragma unroll
-            for (int e = 0; e < VPL; e++) part[j][e] += v[e] * yc;
-            if (NR == 2) {
-                const T yc2 = live ? sh_y2[c] : (T)0;
-#pragma unroll
-                for (int e = 0; e < VPL; e++) part2[j][e] += v[e] * yc2;
-            }
-        }
-    }
+    int liveSpans, liveCols, liveRagged;
+    stream_walk<T, VT, VPL, NL, D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, span0, span1, G, ny, spanSlots, blockSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged);
 #pragma unroll
     for (int j = 0; j < NL; j++)
         if (msk[j] != (T)0) {
@@ -185,6 +280,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
         }
     if (tid < nx && !second) stream_out(qa0, a.qa + (size_t)node * nx + tid);
     if (NR == 2 && tid < nx) stream_out(qa02, r2.qa + (size_t)node * nx + tid);
+    stream_record(sp.live, liveSpans, liveCols, liveRagged);
     __syncthreads();
     T *const myOut = second ? sp.my2 + (size_t)(node - sp.first) * 2 * nv : a.my + (size_t)node * 2 * nv;
     if (NR == 2) {      // both right-hand sides' partials folded in one walk (each in the order of the one-vector kernel): the LDS round trips overlap
@@ -213,7 +309,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
 // is everything behind the load: the lane converts its four floats (exact) and accumulates part[NL][4] in double against the double
 // sh_y; the fold over the span's columns and the outputs my / my2 / qa are double and go where k_stream_gemv<double> puts them, so no
 // consumer knows about the storage.  The order in which a row meets its columns is that of the fp32 context's kernel (same G).
-// Prologue order, the clamp of the first group and the branch-free steady state: as above, for the reasons given there.
+// Prologue order, the skip of spans that meet no nonzero dual entry (stream_walk) and the branch-free steady state: as above, for the reasons given there.
 // NR = 2 (unsplit only): the quasi-Newton loops' two Hessian sweeps in one pass over the fp32 blocks, as k_stream_gemv NR = 2 does for native
 // blocks -- behind rn_set_sweep_pairing(RN_PAIR_ON) (Ctx::stream_pair_ok); not measured on an MI355X yet.  The second accelerated dual r2.w is
 // requested with the small loads in front of the first group and kept in a second LDS set (sh_y2 / sh_red2, doubles); the lane converts its
@@ -222,15 +318,16 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
 // same fold over k): bitwise the results of two unsplit launches.  NL >= 3 runs groups one span shorter (D = 2) to stay inside the registers;
 // the depth does not change the order in which a thread meets its columns.
 // LDS: NR * (ny + G * LD) doubles (NR = 2: up to the CU's 160 KB, Ctx::launch_stream).  HBM bytes per node: LD*ny*4 + NR*(ny + 2nv + nx)*8.
-// Registers (hipcc's resource report, SPLIT = false | true): NL = 1: 72 | 70 VGPRs, NL = 2: 154 | 146, NL = 3: 156 | 156, NL = 4: 208 | 210; no scratch --
-// three waves per SIMD at NL = 2, like k_stream_gemv<float, 2, *> (146 | 130).  NR = 2 (SPLIT = false): NL = 1: 108, NL = 2: 198, NL = 3: 208,
-// NL = 4: 232; no scratch, two waves per SIMD from NL = 2 on (one workgroup per CU).
+// Registers (hipcc's resource report, SPLIT = false | true; with the walk over live spans): NL = 1: 120 | 72 VGPRs, NL = 2: 184 | 156, NL = 3: 193 | 188,
+// NL = 4: 255 | 248; no scratch (k_stream_gemv<float, 2, *>: 160 | 122, <double, 2, *>: 147 | 123 -- the SPLIT instantiations with NL <= 2 walk groups of
+// RN_STREAM_D - 1 spans, which is what fits two workgroups per CU in the native types).  NR = 2 (SPLIT = false): NL = 1: 138, NL = 2: 215, NL = 3: 210,
+// NL = 4: 229 (groups of one span); no scratch, two waves per SIMD from NL = 2 on (one workgroup per CU).
 template <int NL, bool SPLIT, int NR = 1>
 __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_mixed(SweepArgs<double> a, int G, int node0, StreamSplit<double> sp, StreamRhs2<double> r2) {
     static_assert(NR == 1 || !SPLIT, "two right-hand sides: unsplit launches only");
     typedef double T;
     typedef nat_f4 VT;
-    constexpr int VPL = 4, D0 = NL <= 2 ? RN_STREAM_D : RN_STREAM_D_WIDE, D = (NR == 2 && NL >= 3) ? D0 - 1 : D0;
+    constexpr int VPL = 4, D0 = NL <= 2 ? (SPLIT ? RN_STREAM_D - 1 : RN_STREAM_D) : RN_STREAM_D_WIDE, D = (NR == 2 && NL >= 3) ? (NL == 4 ? 1 : D0 - 1) : D0;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *sh_y = reinterpret_cast<T *>(smem_raw);          // ny
     T *sh_red = sh_y + ((a.ny + 3) & ~3);               // G * LD
@@ -261,23 +358,6 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
     for (int j = 0; j < NL; j++)
 #pragma unroll
         for (int e = 0; e < VPL; e++) { part[j][e] = 0; if (NR == 2) part2[j][e] = 0; }
-    const int nFull = (ny / G < span1 ? ny / G : span1) - span0;   // spans of this workgroup made of G whole columns
-    const int nGroups = nFull / D;
-    VT bufA[D][NL], bufB[D][NL];
-#define RN_LOADG(buf, g_)                                                                                              \
-    _Pragma("unroll") for (int d = 0; d < D; d++)                                                                      \
-        _Pragma("unroll") for (int j = 0; j < NL; j++)                                                                 \
-            buf[d][j] = __builtin_nontemporal_load(Ab + (size_t)(span0 + (g_) * D + d) * spanSlots + off[j]);
-#define RN_USEG(buf, g_)                                                                                               \
-    _Pragma("unroll") for (int d = 0; d < D; d++)                                                                      \
-        _Pragma("unroll") for (int j = 0; j < NL; j++) {                                                               \
-            const T yc = sh_y[(span0 + (g_) * D + d) * G + cj[j]] * msk[j];                                            \
-            _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] += (T)buf[d][j][e] * yc;                        \
-            if (NR == 2) {      /* the lane's four floats are converted once and meet both columns */                  \
-                const T yc2 = sh_y2[(span0 + (g_) * D + d) * G + cj[j]] * msk[j];                                      \
-                _Pragma("unroll") for (int e = 0; e < VPL; e++) part2[j][e] += (T)buf[d][j][e] * yc2;                  \
-            }                                                                                                          \
-        }
     const bool has0 = tid < ny;
     const size_t i0 = (size_t)node * ny + (has0 ? tid : 0);
     const int stage = node >= node0 ? a.chainStage + (node - node0) / a.K : a.tr.stageOf[node];
@@ -288,25 +368,11 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
     const T w0a = a.w[i0];      // the y column: the accelerated dual the sweep is evaluated at
     T w20 = 0;
     if (NR == 2) w20 = r2.w[i0];      // the second right-hand side: with the small loads, in front of the first group
-    asm volatile("" ::: "memory");   // keep the request order: the small loads first, the group right behind them
-    {
-        const int lastSlot = (int)blockSlots - 1;
-#pragma unroll
-        for (int d = 0; d < D; d++)
-#pragma unroll
-            for (int j = 0; j < NL; j++) {
-                const int sl = (span0 + d) * spanSlots + off[j];
-                bufA[d][j] = __builtin_nontemporal_load(Ab + (sl < lastSlot ? sl : lastSlot));   // clamped into the block: never behind its last slot
-            }
-    }
-    asm volatile("" ::: "memory");
-    T qa0 = 0, qa02 = 0;      // a_i is stored at the end of the kernel (stores count in the loads' in-order counter)
-    if (has0) sh_y[tid] = w0a;
-    for (int c = tid + STREAM_THREADS; c < ny; c += STREAM_THREADS) sh_y[c] = a.w[(size_t)node * ny + c];
-    if (NR == 2) {
-        if (has0) sh_y2[tid] = w20;
-        for (int c = tid + STREAM_THREADS; c < ny; c += STREAM_THREADS) sh_y2[c] = r2.w[(size_t)node * ny + c];
-    }
+    // a_i is STORED AT THE END of the kernel: stores count in the same in-order counter as the loads, so a store issued
+    // here has to be acknowledged before the wave may consume any group of A_i requested after it
+    T qa0 = 0, qa02 = 0;
+    unsigned long long *sh_nz = reinterpret_cast<unsigned long long *>(sh_y + (size_t)NR * (((ny + 3) & ~3) + (size_t)G * LD));   // (ny + 63) / 64 + 1 words
+    stream_stage_w<T, NR>(a.w + (size_t)node * ny, NR == 2 ? r2.w + (size_t)node * ny : nullptr, w0a, w20, sh_y, sh_y2, sh_nz, ny);
     __syncthreads();
     // a_i = F_i' xi_i = sqrt(p_i) (d_x o xi_box + d_xs o xi_safe)      (a split block: written by its first half)
     if (tid < nx) qa0 = stream_qa_elem(spn, dq0, sh_y[tid], dq1, sh_y[nx + tid]);
@@ -317,42 +383,8 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
         for (int t = tid + STREAM_THREADS; t < nx; t += STREAM_THREADS)
             r2.qa[(size_t)node * nx + t] = stream_qa_elem(spn, dyRow[t], sh_y2[t], dyRow[nx + t], sh_y2[nx + t]);
     }
-    if (nGroups > 0) {
-        int g = 0;
-        for (; g + 2 < nGroups; g += 2) {      // no branch inside: exact vmcnt waits, group g+1 (then g+2) in flight while g is consumed
-            RN_LOADG(bufB, g + 1)
-            RN_USEG(bufA, g)
-            RN_LOADG(bufA, g + 2)
-            RN_USEG(bufB, g + 1)
-        }
-        if (g + 1 < nGroups) {
-            RN_LOADG(bufB, g + 1)
-            RN_USEG(bufA, g)
-            RN_USEG(bufB, g + 1)
-        } else {
-            RN_USEG(bufA, g)
-        }
-    }
-#undef RN_LOADG
-#undef RN_USEG
-    // remaining whole spans and the last, partial one (ny % G columns): guarded
-    for (int s = span0 + nGroups * D; s < span1; s++) {
-#pragma unroll
-        for (int j = 0; j < NL; j++) {
-            const int c = s * G + cj[j];
-            const long long slot = (long long)s * spanSlots + off[j];
-            const bool live = msk[j] != (T)0 && c < ny && slot < blockSlots;
-            const VT v = __builtin_nontemporal_load(Ab + (live ? slot : 0));
-            const T yc = live ? sh_y[c] : (T)0;
-#pragma unroll
-            for (int e = 0; e < VPL; e++) part[j][e] += (T)v[e] * yc;
-            if (NR == 2) {
-                const T yc2 = live ? sh_y2[c] : (T)0;
-#pragma unroll
-                for (int e = 0; e < VPL; e++) part2[j][e] += (T)v[e] * yc2;
-            }
-        }
-    }
+    int liveSpans, liveCols, liveRagged;
+    stream_walk<T, VT, VPL, NL, D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, span0, span1, G, ny, spanSlots, blockSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged);
 #pragma unroll
     for (int j = 0; j < NL; j++)
         if (msk[j] != (T)0) {
@@ -361,6 +393,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
         }
     if (tid < nx && !second) stream_out(qa0, a.qa + (size_t)node * nx + tid);
     if (NR == 2 && tid < nx) stream_out(qa02, r2.qa + (size_t)node * nx + tid);
+    stream_record(sp.live, liveSpans, liveCols, liveRagged);
     __syncthreads();
     T *const myOut = second ? sp.my2 + (size_t)(node - sp.first) * 2 * nv : a.my + (size_t)node * 2 * nv;
     if (NR == 2) {      // both right-hand sides' partials folded in one walk, each in the order of the one-vector kernel

@@ -177,6 +177,7 @@ struct CtxBase {
     virtual int profile_reset() = 0;
     virtual int profile_read(double *, long *) = 0;
     virtual int algorithmic_bytes(double *, double *) const = 0;
+    virtual int stream_live(long long *) = 0;
     virtual int synchronize() = 0;
     virtual void *stream_handle() = 0;
     virtual int comm_init(int, int, const void *, double timeoutSeconds = -1.0) = 0;
@@ -1145,8 +1146,19 @@ struct Ctx : CtxBase {
     int algorithmic_bytes(double *bwd, double *dual) const override {
         // k_stream_gemv, one launch = the whole tree: A_i (2nv x ny, unpadded) read once + y_i read + m1,m2,a_i written
         // (fp32 storage under fp64 iterates: the block at 4 bytes per entry, the vectors at 8)
+        // With the skip of spans that meet no nonzero dual entry (stream_walk) the block bytes are those of the spans the MOST RECENT launch walked:
+        // whole spans at G * LD entries, the ragged last span at its ny % G columns; before any launch and with RN_KNOB_STREAM_SKIP = 0 the dense figure
         const double s = sizeof(T), n = d.nodes, sa = block_elem();
-        if (bwd) *bwd = structured ? 0.0 : n * ((double)2 * d.nv * ny * sa + (ny + 2.0 * d.nv + d.nx) * s);
+        if (bwd) {
+            *bwd = structured ? 0.0 : n * ((double)2 * d.nv * ny * sa + (ny + 2.0 * d.nv + d.nx) * s);
+            if (!structured && stream_skip() && lastStreamGrid > 0) {
+                long long live[4], ragged = 0;
+                if (int rc = const_cast<Ctx *>(this)->stream_live_sum(live, &ragged)) return rc;      // (a copy from the device: changes nothing the context computes)
+                int G, NL;
+                stream_shape(&G, &NL);
+                *bwd = ((double)(live[0] - ragged) * G + (double)ragged * (ny % G)) * LD * sa + n * (ny + 2.0 * d.nv + d.nx) * s;
+            }
+        }
         // fused dual update: Hx, w, y+prev read, y+, w_next written (+ the two scaled-bound streams unless they are regenerated)
         // (RN_BOUNDS_PER_NODE, rn_set_bounds: the unscaled tables are two streams of their own again)
         if (dual) *dual = (RN_DUAL_REGEN && boundsGran != RN_BOUNDS_PER_NODE ? 5.0 : 7.0) * (double)ntot() * s;
@@ -1188,7 +1200,14 @@ struct Ctx : CtxBase {
     T *d_my2 = nullptr;
     int splitFirst = -1, splitSpanHalf = 0;
     bool streamTwoPerCU = false;
+    // the skip of operator spans that meet no nonzero entry of w (k_stream.hpp, stream_walk; RN_KNOB_STREAM_SKIP = 0: every span): what every workgroup of
+    // the most recent launch walked is in d_streamLive (rn_debug_stream_live, rn_algorithmic_bytes); lastStreamGrid = 0: no launch yet
+    int2 *d_streamLive = nullptr;
+    int lastStreamGrid = 0, lastStreamSplitFirst = 0;
+    bool stream_skip() const { return knob[RN_KNOB_STREAM_SKIP] != 0; }
+    size_t stream_nz_bytes() const { return (size_t)((ny + 63) / 64 + 1) * 8; }      // the column mask behind the kernel's LDS sets
     int stream_split_setup() {
+        if (!d_streamLive && !structured) { if (int rc = dalloc(&d_streamLive, (size_t)2 * d.nodes)) return rc; }
         if (splitFirst >= 0) return RN_OK;
         splitFirst = d.nodes;
         const int mode = knob[RN_KNOB_STREAM_SPLIT] != 0;
@@ -1201,10 +1220,18 @@ struct Ctx : CtxBase {
         // FASTER in fp32 (half-size blocks: the per-workgroup prologue and epilogue weigh double there).  Same-box A/B, one | two per
         // CU, ms per iteration: fp64 whole tree (42 rounds) 0.6733 | 0.6854, 1/2 shard 0.3712 | 0.3736, 1/4 shard (10.7 rounds)
         // 0.2101 | 0.2119, 1/8 shard (5.4 rounds) 0.1352 | 0.1318; fp32 whole tree 0.3838 | 0.3752 (the streaming kernel 313 -> 303 us
-        // = 0.84 of the HBM peak).  So: fp32 always, fp64 for launches of fewer than 8 rounds.
-        streamTwoPerCU = sizeof(T) == 4 || store32() || d.nodes < 8 * numCUs;      // (fp32 storage: the fp32 context's block bytes, its rule)
-        if (knob[RN_KNOB_STREAM_TWO_PER_CU] >= 0) streamTwoPerCU = knob[RN_KNOB_STREAM_TWO_PER_CU] != 0;
-        if (!mode || !streamTwoPerCU || structured || d.nodes <= numCUs || r == 0 || 2 * r > numCUs || groups < 2) return RN_OK;
+        // = 0.84 of the HBM peak).  So the rule was: fp32 always, fp64 for launches of fewer than 8 rounds.
+        // With the skip of spans that meet no nonzero dual entry (stream_walk) a workgroup's first group waits for w and a block is about half
+        // its bytes: the per-workgroup start-up weighs in fp64 as it did in fp32, and the instantiation is 123 VGPRs with groups of four spans
+        // (four waves per SIMD: two workgroups do share a CU).  Same-box A/B on the whole fp64 tree (tools/ab_stream_skip.py), one | two per CU,
+        // ms per iteration: with the skip 0.4073 | 0.3778 (the streaming launch 336 -> 305 us), every span walked (knob 0) 0.7000 | 0.6659.
+        // So: always.  (The 1/2 and 1/4 shards were not measured again with the skip.)
+        // The SPLIT of the last round stays with the launches that had it before (it changes the order of the sums in the last stages, so a
+        // context of the old one-per-CU rule keeps the bits it always computed), or follows the knob.
+        bool splitOk = sizeof(T) == 4 || store32() || d.nodes < 8 * numCUs;      // (fp32 storage: the fp32 context's block bytes, its rule)
+        streamTwoPerCU = true;
+        if (knob[RN_KNOB_STREAM_TWO_PER_CU] >= 0) splitOk = streamTwoPerCU = knob[RN_KNOB_STREAM_TWO_PER_CU] != 0;
+        if (!mode || !streamTwoPerCU || !splitOk || structured || d.nodes <= numCUs || r == 0 || 2 * r > numCUs || groups < 2) return RN_OK;
         if (d.N - cs < STREAM_SPLIT_STAGES || r > STREAM_SPLIT_STAGES * K) return RN_OK;     // (the cut never moves the chain region's END)
         if (int rc = dalloc(&d_my2, (size_t)r * 2 * d.nv)) return rc;
         splitFirst = d.nodes - r;
@@ -1231,11 +1258,12 @@ struct Ctx : CtxBase {
         int G, NL;
         stream_shape(&G, &NL);
         RN_CHECK(NL <= STREAM_NLMAX, RN_E_ARG, "k_stream_gemv: more than 4096 values per operator column are not supported (2*nv too large)");
-        const size_t lds = stream_lds(G);
-        RN_CHECK(lds <= 64 * 1024 || (lds <= 160 * 1024 && ensure_stream_lds()), RN_E_ARG, "k_stream_gemv: a span of operator columns does not fit the CU's LDS");
+        const size_t lds = stream_lds(G), nzb = stream_nz_bytes();
+        RN_CHECK(lds + nzb <= 64 * 1024 || (lds + nzb <= 160 * 1024 && ensure_stream_lds()), RN_E_ARG, "k_stream_gemv: a span of operator columns does not fit the CU's LDS");
         const int node0 = h_stageCum[a.chainStage];   // first node of the chain region as this sweep sees it
-        const StreamSplit<T> sp{a.splitFirst, splitSpanHalf, d_my2};
+        const StreamSplit<T> sp{a.splitFirst, splitSpanHalf, d_my2, stream_skip() ? 1 : 0, d_streamLive};
         const int grid = d.nodes + (d.nodes - a.splitFirst);      // two workgroups for every block of the split round
+        lastStreamGrid = grid; lastStreamSplitFirst = a.splitFirst;
         const StreamRhs2<T> none{nullptr, nullptr, nullptr};
         if constexpr (sizeof(T) == 8) {
             if (store32()) {   // fp32 blocks under fp64 iterates (k_stream_gemv_mixed): one right-hand side, split or not, or two, unsplit
@@ -1243,52 +1271,52 @@ struct Ctx : CtxBase {
                     // (both sets are doubles over a span chosen for 4-byte entries: twice the native pair's LDS for the same operator width, so
                     //  past 64 KB the launch takes the function attribute like the one-vector launch does)
                     RN_CHECK(a.splitFirst >= d.nodes, RN_E_STATE, "k_stream_gemv_mixed with two right-hand sides: unsplit launches only");
-                    RN_CHECK(2 * lds <= 64 * 1024 || (2 * lds <= 160 * 1024 && ensure_stream_lds()), RN_E_ARG, "k_stream_gemv_mixed with two right-hand sides: the two LDS sets do not fit the CU's LDS");
+                    RN_CHECK(2 * lds + nzb <= 64 * 1024 || (2 * lds + nzb <= 160 * 1024 && ensure_stream_lds()), RN_E_ARG, "k_stream_gemv_mixed with two right-hand sides: the two LDS sets do not fit the CU's LDS");
                     switch (NL) {
-                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
-                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
-                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
-                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
+                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
+                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
+                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
+                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
                     }
                 } else if (streamTwoPerCU) {
                     switch (NL) {
-                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
+                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
                     }
                 } else {
                     switch (NL) {
-                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
+                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
                     }
                 }
                 return RN_OK;
             }
         }
         if (second) {
-            RN_CHECK(a.splitFirst >= d.nodes && 2 * lds <= 64 * 1024, RN_E_STATE, "k_stream_gemv with two right-hand sides: unsplit launches only");
+            RN_CHECK(a.splitFirst >= d.nodes && 2 * lds + nzb <= 64 * 1024, RN_E_STATE, "k_stream_gemv with two right-hand sides: unsplit launches only");
             switch (NL) {
-                case 1: hipLaunchKernelGGL((k_stream_gemv<T, 1, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
-                case 2: hipLaunchKernelGGL((k_stream_gemv<T, 2, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
-                case 3: hipLaunchKernelGGL((k_stream_gemv<T, 3, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
-                default: hipLaunchKernelGGL((k_stream_gemv<T, 4, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds, stream, a, G, node0, sp, *second); break;
+                case 1: hipLaunchKernelGGL((k_stream_gemv<T, 1, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
+                case 2: hipLaunchKernelGGL((k_stream_gemv<T, 2, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
+                case 3: hipLaunchKernelGGL((k_stream_gemv<T, 3, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
+                default: hipLaunchKernelGGL((k_stream_gemv<T, 4, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
             }
         } else if (streamTwoPerCU) {
             switch (NL) {
-                case 1: hipLaunchKernelGGL((k_stream_gemv<T, 1, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                case 2: hipLaunchKernelGGL((k_stream_gemv<T, 2, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                case 3: hipLaunchKernelGGL((k_stream_gemv<T, 3, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                default: hipLaunchKernelGGL((k_stream_gemv<T, 4, true>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
+                case 1: hipLaunchKernelGGL((k_stream_gemv<T, 1, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                case 2: hipLaunchKernelGGL((k_stream_gemv<T, 2, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                case 3: hipLaunchKernelGGL((k_stream_gemv<T, 3, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                default: hipLaunchKernelGGL((k_stream_gemv<T, 4, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
             }
         } else {
             switch (NL) {
-                case 1: hipLaunchKernelGGL((k_stream_gemv<T, 1, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                case 2: hipLaunchKernelGGL((k_stream_gemv<T, 2, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                case 3: hipLaunchKernelGGL((k_stream_gemv<T, 3, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
-                default: hipLaunchKernelGGL((k_stream_gemv<T, 4, false>), dim3(grid), dim3(STREAM_THREADS), lds, stream, a, G, node0, sp, none); break;
+                case 1: hipLaunchKernelGGL((k_stream_gemv<T, 1, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                case 2: hipLaunchKernelGGL((k_stream_gemv<T, 2, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                case 3: hipLaunchKernelGGL((k_stream_gemv<T, 3, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
+                default: hipLaunchKernelGGL((k_stream_gemv<T, 4, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
             }
         }
         return RN_OK;
@@ -1305,8 +1333,8 @@ struct Ctx : CtxBase {
         if (structured || pairReq == RN_PAIR_OFF) return false;
         int G, NL;
         stream_shape(&G, &NL);
-        if (store32()) return pairReq == RN_PAIR_ON && 2 * stream_lds(G) <= 160 * 1024;
-        return !(splitFirst >= 0 && splitFirst < d.nodes) && 2 * stream_lds(G) <= 64 * 1024;
+        if (store32()) return pairReq == RN_PAIR_ON && 2 * stream_lds(G) + stream_nz_bytes() <= 160 * 1024;
+        return !(splitFirst >= 0 && splitFirst < d.nodes) && 2 * stream_lds(G) + stream_nz_bytes() <= 64 * 1024;
     }
     static int slab_stride(int kp) { return (kp + 59) / 64 * 64 + 4; }   // >= kp, = 4 (mod 64): conflict-free MFMA B reads
     // waves per slab workgroup.  Many slabs (more workgroups than CUs): the count in {4, 6, 8} that wastes the least SIMD
@@ -2464,6 +2492,26 @@ struct Ctx : CtxBase {
         out[2] = streamTwoPerCU ? 1 : 0; out[3] = numCUs;
         return RN_OK;
     }
+    // {live spans, spans, live columns, columns} of the most recent streaming launch, summed over its workgroups' records; ragged: how many of the
+    // live spans were ragged last spans (ny % G columns)
+    int stream_live_sum(long long *out, long long *ragged) {
+        RN_HIP(hipSetDevice(device));
+        RN_HIP(hipStreamSynchronize(stream));
+        std::vector<int2> h((size_t)lastStreamGrid);
+        RN_HIP(hipMemcpy(h.data(), d_streamLive, h.size() * sizeof(int2), hipMemcpyDeviceToHost));
+        int G, NL;
+        stream_shape(&G, &NL);
+        long long ls = 0, lc = 0, rg = 0;
+        for (const int2 &e : h) { ls += e.x; lc += e.y & ((1 << 30) - 1); rg += (e.y >> 30) & 1; }
+        out[0] = ls; out[1] = (long long)d.nodes * ((ny + G - 1) / G); out[2] = lc; out[3] = (long long)d.nodes * ny;
+        if (ragged) *ragged = rg;
+        return RN_OK;
+    }
+    int stream_live(long long *out) override {
+        RN_CHECK(out, RN_E_ARG, "rn_debug_stream_live: null output");
+        RN_CHECK(!structured && lastStreamGrid > 0 && d_streamLive, RN_E_STATE, "rn_debug_stream_live: no streaming launch yet");
+        return stream_live_sum(out, nullptr);
+    }
     int counters(long *out) override {
         RN_CHECK(out, RN_E_ARG, "rn_get_counters: null output");
         out[0] = optBatches; out[1] = exactBatches; out[2] = fallbacks; out[3] = optHold;
@@ -3053,6 +3101,7 @@ int rn_debug_inject_allocation(rn_ctx *ctx, size_t bytes) { RN_GUARD(ctx); retur
 int rn_debug_guard_poke(rn_ctx *ctx, int nbytes) { RN_GUARD(ctx); return ctx->impl->guard_poke(nbytes); }
 int rn_debug_set_knob(rn_ctx *ctx, int knob, int value) { RN_GUARD(ctx); return ctx->impl->set_knob(knob, value); }
 int rn_debug_stream_info(rn_ctx *ctx, int info[4]) { RN_GUARD(ctx); return ctx->impl->stream_info(info); }
+int rn_debug_stream_live(rn_ctx *ctx, long long out[4]) { RN_GUARD(ctx); return ctx->impl->stream_live(out); }
 int rn_debug_restart_test(rn_ctx *ctx, double out[3]) { RN_GUARD(ctx); return ctx->impl->debug_restart_test(out); }
 int rn_debug_peer_seq(rn_ctx *ctx, unsigned int seq) { RN_GUARD(ctx); return ctx->impl->debug_peer_seq(seq); }
 int rn_guard_report(long out[2]) { if (!out) return RN_E_ARG; out[0] = rn::g_guardContexts.load(); out[1] = rn::g_guardBadBytes.load(); return RN_OK; }
