@@ -236,6 +236,36 @@ int rn_set_bounds_device(rn_ctx *ctx, int granularity, size_t rows, int precisio
                          const void *umin, const void *umax);
 int rn_get_bounds_layout(rn_ctx *ctx, int *granularity, size_t *rows);
 int rn_get_bounds(rn_ctx *ctx, size_t rows, double *xmin, double *xmax, double *xsafe, double *umin, double *umax);
+/* Plan report: what the plan the context holds costs and where it violates its bounds, per stage and per scenario.  The reference's KPIs
+ * (SmpcController::updateKpi and the read-outs getEconomicKpi, getSmoothKpi, getSafeKpi, getNetworkKpi, SmpcController.cu:1819-1859) are
+ * closed-loop sums over ONE realised trajectory; these entry points give the predictive counterpart over the scenario tree, from the x and u
+ * that rn_get(RN_BUF_X / RN_BUF_U) would return at that moment, without a read-back and without the tree bookkeeping on the host.
+ * Per-node terms, all physical: du_i = u_i - u_parent(i) (the root against prevU), alpha_i the context's RN_BUF_ALPHA, the bounds the
+ *   unscaled table in force (rn_set_bounds, any granularity):
+ *     RN_PLAN_ECON      p_i alpha_i' u_i                     RN_PLAN_SMOOTH    p_i du_i' W du_i          RN_PLAN_STORED   p_i sum_j x_ij
+ *     RN_PLAN_SHORT_EXP p_i sum_j max(xs_j - x_ij, 0)        RN_PLAN_XBOX_EXP  p_i sum_j [max(xmin_j - x_ij, 0) + max(x_ij - xmax_j, 0)]
+ *     RN_PLAN_UBOX_EXP  the same for u                       RN_PLAN_*_MAX     the largest single entry of the same three violations, not weighted
+ * rn_plan_report: perStage [stages][RN_PLAN_COLS], stages = dims.N: the sum columns summed over the nodes of the stage, the maxima taken
+ *   over the same nodes.  On a sharded context the call is collective and every rank receives the whole tree's table, the same bits.
+ * rn_plan_report_scenarios: perLeaf [leaves][RN_PLAN_COLS], leaves = the context's (local) node count at the last stage: the terms NOT
+ *   weighted, summed (maxima: taken) along the path from the leaf to the root; RN_PLAN_STORED holds the leaf's own sum_j x.  leafNode (may be
+ *   NULL) receives the node index of every row (local on a shard: map it through rn_shard_global_nodes).  With probNode of the leaves the
+ *   caller has the cost distribution, hence a CVaR.  Rows stay local on a sharded context (the crown is replicated: every path is complete),
+ *   but the call is collective there as well.
+ * rn_plan_report_device: the same two tables, doubles in device memory, valid until the next report on this context; launches on the
+ *   context's stream, no host synchronisation.  *perStage is COLUMN-major, [RN_PLAN_COLS][dims.N] (the sum columns and the maxima are each
+ *   one contiguous block); *perLeaf is [*leaves][RN_PLAN_COLS]; row l is local node (nodes - *leaves + l).
+ * Arithmetic: fp64 on fp32 contexts too (every stored value converted first); every sum in an order fixed by the tree and the launch shape,
+ *   no floating-point atomics: two calls on an unchanged context return the same bits.  There are no thresholded counts ("probability of
+ *   shortfall"): APG drives active constraints to exactly x = xs, such a column would be noise.
+ * State: RN_E_STATE before rn_factor_step, before the affine terms, or before the first sweep of a solve.  stages / leaves wrong or a NULL
+ *   output: RN_E_ARG.  Memory: the first report allocates a [nodes][RN_PLAN_COLS] table and the result tables and keeps them; later reports
+ *   allocate nothing (rn_device_memory_info info[2]); a context that never asks allocates and launches nothing. */
+enum { RN_PLAN_ECON = 0, RN_PLAN_SMOOTH, RN_PLAN_STORED, RN_PLAN_SHORT_EXP, RN_PLAN_XBOX_EXP, RN_PLAN_UBOX_EXP,   /* sums   */
+       RN_PLAN_SHORT_MAX, RN_PLAN_XBOX_MAX, RN_PLAN_UBOX_MAX, RN_PLAN_COLS };                                     /* maxima */
+int rn_plan_report(rn_ctx *ctx, size_t stages, double *perStage /* [stages][RN_PLAN_COLS] */);
+int rn_plan_report_scenarios(rn_ctx *ctx, size_t leaves, double *perLeaf /* [leaves][RN_PLAN_COLS] */, int *leafNode /* may be NULL */);
+int rn_plan_report_device(rn_ctx *ctx, void **perStage, void **perLeaf, size_t *leaves);
 /* Engine::setDemandUncertaintyFlag / setPriceUncertaintyFlag / SmpcConfiguration::getWeightEconomical */
 int rn_set_uncertainty(rn_ctx *ctx, int demandUncertainty, int priceUncertainty, double weightEconomical);
 /* Engine::updateStateControl (Engine.cu:1300-1316) */

@@ -44,10 +44,10 @@ UNITS = {
     "k_dual": ["common.hpp", "k_dual.hpp"],
     "k_walks": ["common.hpp", "k_dual.hpp", "k_walks.hpp"],
     "k_slab": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp"],
-    "k_misc": ["common.hpp", "k_misc.hpp"],
+    "k_misc": ["common.hpp", "k_misc.hpp", "k_plan.hpp"],
     "k_fbe": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "fbe_kernels.hpp"],
-    "rapidnet_capi": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "k_stream.hpp", "k_misc.hpp", "kernels.hpp", "fbe_kernels.hpp", "fbe_methods.inc",
-                      "caller_data.inc", "partition.hpp", "bounds.hpp"],
+    "rapidnet_capi": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "k_stream.hpp", "k_misc.hpp", "k_plan.hpp", "kernels.hpp", "fbe_kernels.hpp", "fbe_methods.inc",
+                      "caller_data.inc", "plan_report.inc", "partition.hpp", "bounds.hpp"],
 }
 OBJ_DIR = os.path.join(HERE, "build")
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]
@@ -163,6 +163,7 @@ TEST_STOP_TOLERANCE = os.path.join(BIN_DIR, "test_stop_tolerance")
 TEST_TREE_DATA = os.path.join(BIN_DIR, "test_tree_data")
 TEST_BOUNDS = os.path.join(BIN_DIR, "test_bounds")
 TEST_RESTART = os.path.join(BIN_DIR, "test_restart")
+TEST_PLAN_REPORT = os.path.join(BIN_DIR, "test_plan_report")
 
 
 def build_host(force=False):
@@ -217,6 +218,11 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_RESTART, test_src, "-L" + HERE, "-lrapidnet_host",
                                "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
         _stamp(TEST_RESTART, [test_src] + deps + hdr)
+    test_src = os.path.join(ROOT, "tests", "cpp", "test_plan_report.cpp")
+    if force or _stale(TEST_PLAN_REPORT, [test_src] + deps + hdr):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_PLAN_REPORT, test_src, "-L" + HERE, "-lrapidnet_host",
+                               "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
+        _stamp(TEST_PLAN_REPORT, [test_src] + deps + hdr)
     return LIB_HOST
 
 

@@ -33,6 +33,9 @@ BOUNDS = {"shared": BOUNDS_SHARED, "stage": BOUNDS_PER_STAGE, "node": BOUNDS_PER
 KNOBS = {k: i for i, k in enumerate(("dual_trips", "dual_pipe", "vlv_wide", "slab_pipe", "slab_frag", "unscaled_walk", "stream_two_per_cu",
                                      "stream_split", "nama_pair", "ls_sequential", "value_mfma", "tune_bias_us", "struct_linear", "fuse_split", "stream_skip"))}
 EXCHANGE_COLLECTIVE, EXCHANGE_ONESHOT, EXCHANGE_AUTO = 0, 1, 2
+# rn_plan_report: the columns of both tables, in the order of RN_PLAN_* (the first six are sums, the last three maxima)
+PLAN_COLUMNS = ("econ", "smooth", "stored", "shortExp", "xboxExp", "uboxExp", "shortMax", "xboxMax", "uboxMax")
+PLAN_SUMS = 6
 
 # every symbol include/rapidnet.h (the boundary) and include/rapidnet_debug.h (test hooks, rn_debug_*) declare
 SYMBOLS = [
@@ -52,6 +55,7 @@ SYMBOLS = [
     "rn_guard_check", "rn_device_memory_info", "rn_reserve_iterations", "rn_profile_read_collective", "rn_debug_inject_allocation", "rn_guard_report", "rn_debug_guard_poke",
     "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_set_bounds", "rn_set_bounds_device", "rn_get_bounds_layout", "rn_get_bounds", "rn_debug_cut_moments",
     "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live",
+    "rn_plan_report", "rn_plan_report_scenarios", "rn_plan_report_device",
 ]
 
 
@@ -252,6 +256,9 @@ def load():
     lib.rn_get_bounds_layout.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_size_t)]
     lib.rn_get_bounds.argtypes = [vp, C.c_size_t, dp, dp, dp, dp, dp]
     lib.rn_debug_cut_moments.argtypes = [vp, dp, dp, C.c_size_t]
+    lib.rn_plan_report.argtypes = [vp, C.c_size_t, dp]
+    lib.rn_plan_report_scenarios.argtypes = [vp, C.c_size_t, dp, dp]
+    lib.rn_plan_report_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
     _LIB = lib
     return lib
 
@@ -720,6 +727,30 @@ class Solver:
         self._check(self.lib.rn_get_bounds(self.h, r, *[out[k].ctypes.data for k in ("xmin", "xmax", "xsafe", "umin", "umax")]))
         out["granularity"], out["rows"] = g, r
         return out
+
+    # ---- what the plan at hand costs and where it violates its bounds (rn_plan_report ...) ------------------------
+    def planLeaves(self):
+        """rows of the per-scenario table: the context's (local) node count at the last stage"""
+        st = _i32(self.tree["stages"])
+        mine = np.asarray(self.global_nodes) if self.nranks > 1 else np.arange(self.nodes)
+        return int((st[mine] == st.max()).sum())
+
+    def planReport(self):
+        """rn_plan_report + rn_plan_report_scenarios: {"stage": {column: array [N]}, "scenario": {column: array [leaves]}, "leafNode": array
+        [leaves] of (local) node indices}, columns as PLAN_COLUMNS.  On a shard every rank calls it (both calls are collective)."""
+        nc, leaves = len(PLAN_COLUMNS), self.planLeaves()
+        st, sc, ln = np.zeros((self.N, nc)), np.zeros((leaves, nc)), np.zeros(leaves, dtype=np.int32)
+        self._check(self.lib.rn_plan_report(self.h, self.N, st.ctypes.data))
+        self._check(self.lib.rn_plan_report_scenarios(self.h, leaves, sc.ctypes.data, ln.ctypes.data))
+        return {"stage": {k: st[:, i].copy() for i, k in enumerate(PLAN_COLUMNS)}, "scenario": {k: sc[:, i].copy() for i, k in enumerate(PLAN_COLUMNS)},
+                "leafNode": ln}
+
+    def planReportDevice(self):
+        """rn_plan_report_device: (address of the per-stage table, COLUMN-major [columns][N] doubles; address of the per-scenario table
+        [leaves][columns] doubles; leaves), valid until the next report; nothing is waited for"""
+        a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        self._check(self.lib.rn_plan_report_device(self.h, C.byref(a), C.byref(b), C.byref(n)))
+        return a.value, b.value, n.value
 
     def updateTree(self, tree):
         """a re-weighted scenario tree of the SAME topology (on a shard: the full tree): replaces self.tree and hands its probabilities and errors

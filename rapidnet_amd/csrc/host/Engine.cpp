@@ -115,6 +115,24 @@ int Engine::getBoundsLayout(size_t *rows) {
 void Engine::getBounds(size_t rows, real_t *xmin, real_t *xmax, real_t *xsafe, real_t *umin, real_t *umax) {
     check(rn_get_bounds(ctx, rows, xmin, xmax, xsafe, umin, umax), "rn_get_bounds");
 }
+size_t Engine::getNumLocalScenarios() {
+    const uint_t *stage = ptrMyScenarioTree->getStageNodes();
+    const uint_t nodes = ptrMyScenarioTree->getNumNodes();
+    uint_t last = 0;
+    for (uint_t i = 0; i < nodes; i++) last = stage[i] > last ? stage[i] : last;
+    size_t n = 0;
+    for (int g : getGlobalNodes()) n += stage[g] == last;
+    return n;
+}
+void Engine::evaluatePlan(PlanReport &r) {
+    r.stages = ptrMyScenarioTree->getPredHorizon();
+    r.scenarios = getNumLocalScenarios();
+    r.perStage.assign(r.stages * RN_PLAN_COLS, 0.0);
+    r.perScenario.assign(r.scenarios * RN_PLAN_COLS, 0.0);
+    r.leafNode.assign(r.scenarios, 0);
+    check(rn_plan_report(ctx, r.stages, r.perStage.data()), "rn_plan_report");
+    check(rn_plan_report_scenarios(ctx, r.scenarios, r.perScenario.data(), r.leafNode.data()), "rn_plan_report_scenarios");
+}
 
 void Engine::create(int precision, int device, int operatorMode, int rank, int nranks, const void *id128, int cutStage) {
     myRank = rank; numRanks = nranks;

@@ -94,6 +94,19 @@ public:
     // pointer skips that array)
     int getBoundsLayout(size_t *rows = nullptr);
     void getBounds(size_t rows, real_t *xmin, real_t *xmax, real_t *xsafe, real_t *umin, real_t *umax);
+    // What the plan the engine holds costs and where it violates its bounds (rapidnet.h, rn_plan_report / rn_plan_report_scenarios: the
+    // predictive counterpart over the scenario tree of the reference's closed-loop KPIs, SmpcController.cu:1819-1859).  perStage
+    // [stages][RN_PLAN_COLS], perScenario [scenarios][RN_PLAN_COLS], leafNode [scenarios]: the local node of every scenario row (map it
+    // through getGlobalNodes() on a shard).  After a solve; on a sharded engine every rank calls it (the per-stage table is the whole tree's).
+    struct PlanReport {
+        size_t stages = 0, scenarios = 0;
+        std::vector<real_t> perStage, perScenario;
+        std::vector<int> leafNode;
+        real_t stage(size_t k, int column) const { return perStage[k * RN_PLAN_COLS + column]; }
+        real_t scenario(size_t l, int column) const { return perScenario[l * RN_PLAN_COLS + column]; }
+    };
+    size_t getNumLocalScenarios();                   // local nodes at the last stage: the rows of PlanReport::perScenario
+    void evaluatePlan(PlanReport &report);
     int getRank() { return myRank; }
     int getNumRanks() { return numRanks; }
     uint_t getNumLocalNodes();                       // nodes this rank holds (= the tree's node count on one GPU)

@@ -84,6 +84,36 @@ uint_t SmpcController::getRestartsRun() {
     check(rn_get_restart_info(ptrMyEngine->getContext(), counts, last), "rn_get_restart_info");
     return (uint_t)counts[0];
 }
+const Engine::PlanReport &SmpcController::getPlanReport() {
+    ptrMyEngine->evaluatePlan(planReport);
+    return planReport;
+}
+uint_t SmpcController::writePlanReport(std::fstream &out) {
+    if (!out.is_open()) return 0;
+    static const char *const columns[RN_PLAN_COLS] = {"econ", "smooth", "stored", "shortExp", "xboxExp", "uboxExp", "shortMax", "xboxMax", "uboxMax"};
+    const Engine::PlanReport &r = getPlanReport();
+    const std::streamsize digits = out.precision(17);
+    const auto table = [&](const char *name, const std::vector<real_t> &v, size_t rows) {
+        out << "\"" << name << "\": [";
+        for (size_t i = 0; i < rows; i++) {
+            out << (i ? ", [" : "[");
+            for (int c = 0; c < RN_PLAN_COLS; c++) out << (c ? ", " : "") << v[i * RN_PLAN_COLS + c];
+            out << "]";
+        }
+        out << "]";
+    };
+    out << "\"planReport\" : {\"columns\": [";
+    for (int c = 0; c < RN_PLAN_COLS; c++) out << (c ? ", " : "") << "\"" << columns[c] << "\"";
+    out << "], ";
+    table("perStage", r.perStage, r.stages);
+    out << ", \"leafNode\": [";
+    for (size_t i = 0; i < r.scenarios; i++) out << (i ? ", " : "") << r.leafNode[i];
+    out << "], ";
+    table("perScenario", r.perScenario, r.scenarios);
+    out << "}" << std::endl;
+    out.precision(digits);
+    return 1;
+}
 uint_t SmpcController::controlAction(real_t *u) {
     if (!factorStepFlag) { ptrMyEngine->factorStep(); factorStepFlag = true; }
     size_t before[4];

@@ -54,6 +54,13 @@ public:
     // momentum restarts of the last APG solve (controlAction, algorithmApg): 0 unless Engine::setRestart / the configuration's
     // "momentumRestart": "gradient" asked for the gradient test (rapidnet.h, rn_get_restart_info)
     uint_t getRestartsRun();
+    // What the plan of the last control step costs and where it violates its bounds, per stage and per scenario (Engine::evaluatePlan,
+    // rapidnet.h rn_plan_report: the predictive counterpart of the closed-loop read-outs above, :1819-1859).  To be called AFTER
+    // controlAction, outside the window of its leak check: the first report allocates its tables on the device and keeps them.
+    const Engine::PlanReport &getPlanReport();
+    // ... written as one more entry of the control output: "planReport" : {"columns": [...], "perStage": [[...]], "leafNode": [...],
+    // "perScenario": [[...]]}, a JSON object with 17 significant digits.  controlAction(fstream&)'s own output is unchanged.
+    uint_t writePlanReport(std::fstream &controlOutputJson);
     real_t *getValueFbe() { return vecValueFbe.data(); }    // :1883
     real_t *getVecTau() { return vecTau.data(); }
     ~SmpcController();
@@ -98,6 +105,7 @@ protected:
     bool factorStepFlag, simulatorFlag, ownsObjects, simulatorDisturbance = false;
     std::vector<real_t> vecPrimalInfs, vecValueFbe, vecTau, lastControl;
     real_t economicKpi, smoothKpi, safeKpi, networkKpi;
+    Engine::PlanReport planReport;
 };
 
 #endif

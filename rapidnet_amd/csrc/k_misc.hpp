@@ -2,6 +2,7 @@
 // (part of the kernel sources of librapidnet_hip.so; kernels.hpp includes every family header, the translation units k_*.hip instantiate them)
 #pragma once
 #include "common.hpp"
+#include "k_plan.hpp"   // the plan report's kernel: instantiated in k_misc.hip with this family
 
 namespace rn {
 
@@ -446,9 +447,17 @@ __global__ void k_pack(T *y, T *part, int ny, int off, int dim, long long nodes,
         if (toY) y[node * ny + off + t] = part[i]; else part[i] = y[node * ny + off + t];
     }
 }
+// projectionBox<<<1,nu>>> SmpcController.cu:1649.  The element type arrives as a flag and not as a template parameter (one kernel instead of
+// two, as k_tree_data); the comparisons and the stored value are the typed ones, bit for bit
 template <typename T>
-__global__ void k_clamp_vec(T *u, const T *lo, const T *hi, int n) {   // projectionBox<<<1,nu>>> SmpcController.cu:1649
+__device__ __forceinline__ void clamp_vec_body(void *u_, const void *lo_, const void *hi_, int n) {
+    T *u = static_cast<T *>(u_);
+    const T *lo = static_cast<const T *>(lo_), *hi = static_cast<const T *>(hi_);
     for (int i = threadIdx.x; i < n; i += blockDim.x) { const T v = u[i]; u[i] = v < lo[i] ? lo[i] : (v > hi[i] ? hi[i] : v); }
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void k_clamp_vec(void *u, const void *lo, const void *hi, int n, int f64) {
+    if (f64) clamp_vec_body<double>(u, lo, hi, n); else clamp_vec_body<float>(u, lo, hi, n);
 }
 
 

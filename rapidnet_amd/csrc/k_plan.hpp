@@ -1,0 +1,257 @@
+// k_plan.hpp -- the plan report: costs and bound violations of the plan a context holds, per stage and per scenario
+// (part of the kernel sources of librapidnet_hip.so; k_misc.hip instantiates the one kernel, k_misc.hpp includes this header)
+#pragma once
+#include "common.hpp"
+
+namespace rn {
+
+// ------------------------------------------------------------------------------------------------------
+// rn_plan_report / rn_plan_report_scenarios / rn_plan_report_device (include/rapidnet.h).  The reference's KPIs (SmpcController::updateKpi
+// and the get*Kpi read-outs, SmpcController.cu:1819-1859) are closed-loop sums over ONE realised trajectory; this is their predictive
+// counterpart over the scenario tree, evaluated on the physical x and u the last sweep stored.  For node i with parent a(i)
+// (du_i = u_i - u_a(i), the root against prevU) the node table [nodes][PLAN_COLS] holds, NOT weighted,
+//   ECON   alpha_i' u_i                    SMOOTH  du_i' W du_i               STORED  sum_j x_ij
+//   SHORT  sum_j max(xs_j - x_ij, 0)       XBOX    sum_j max(xmin_j - x_ij, 0) + max(x_ij - xmax_j, 0)      UBOX  the same for u
+//   SHORT_MAX, XBOX_MAX, UBOX_MAX          the largest single entry of the same three violations
+// with the bounds row of the unscaled table in force (rn_set_bounds: row = stage * bStrideStage + node * bStrideNode, in elements).
+// One kernel, two launches, the phase a run-time argument that is uniform over the grid (as the precision flag: one kernel instead of
+// four, k_tree_data's and k_restart_test's idiom):
+//   phase 0  node terms.  k_value_terms' shape: a workgroup takes PLAN_TILE nodes; every wave requests the parents of its rows first, then
+//            all u / u_parent / alpha / umin / umax values of its rows in one batch, then all x / xmin / xs / xmax; du goes to LDS so that
+//            every element of W fetched from L2 serves the whole tile.  Columns beyond 64 lanes are looped, tails are masked.
+//   phase 1  folds.  Workgroup k < N folds the contiguous node rows of stage k -- sum columns weighted by p_i, maxima as they are -- into
+//            stage[c * N + k]; the further workgroups take one leaf per thread and walk leaf -> root through `parent` (N dependent steps over
+//            rows phase 0 has just left in L2): sums and maxima along the path, NOT weighted, STORED the leaf's own.
+// Arithmetic: every loaded value is converted to double before the first operation, on fp32 contexts too.  Every sum has an order fixed by
+// the tree and the launch shape -- a lane over its strided positions, the wave (wave_sum_f64), the waves in LDS in ascending order -- and
+// there are no floating-point atomics: an unchanged context gives the same bits.  Violations are one IEEE subtraction and comparisons
+// (contraction off), so the maxima are exact functions of the inputs.
+// Sharded contexts: the stages [0, crownStages) are replicated on every rank.  Their node rows are computed everywhere (every leaf's path
+// is complete on its rank); their SUM columns of the stage table are written as 0 unless countCrown (rank 0), so that the sum over the
+// ranks counts them once; their maxima are the same on every rank.  The stage table is column-major ([PLAN_COLS][N]) so that the sum
+// block (the first PLAN_SUMS * N doubles) and the maxima block behind it are each one contiguous payload of a collective.
+constexpr int PLAN_ECON = 0, PLAN_SMOOTH = 1, PLAN_STORED = 2, PLAN_SHORT = 3, PLAN_XBOX = 4, PLAN_UBOX = 5, PLAN_SHORT_MAX = 6, PLAN_XBOX_MAX = 7,
+              PLAN_UBOX_MAX = 8, PLAN_COLS = 9, PLAN_SUMS = 6;
+constexpr int PLAN_THREADS = 128, PLAN_WAVES = PLAN_THREADS / 64, PLAN_TILE = 8, PLAN_RPW = PLAN_TILE / PLAN_WAVES, PLAN_JB = 8;
+constexpr int PLAN_RED = PLAN_WAVES * PLAN_COLS > PLAN_WAVES * PLAN_TILE ? PLAN_WAVES * PLAN_COLS : PLAN_WAVES * PLAN_TILE;   // doubles of LDS behind du
+struct PlanArgs {
+    int phase, f64;
+    int nodes, nx, nu, ny, N, leaves;
+    const void *x, *u, *alpha, *prevU, *prob, *W, *blo, *bhi;   // of T (f64: doubles, else floats)
+    int bStrideStage, bStrideNode;
+    const int *parent, *stageOf, *stageCum;
+    int crownStages, countCrown;
+    double *node;      // [nodes][PLAN_COLS]
+    double *stage;     // [PLAN_COLS][N]
+    double *leaf;      // [leaves][PLAN_COLS]
+    int *leafNode;     // [leaves]
+};
+inline size_t plan_lds_bytes(int nu) { return ((size_t)nu * PLAN_TILE + PLAN_RED) * sizeof(double); }
+
+__device__ __forceinline__ double plan_wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { const double o = __shfl_xor(v, off); v = o > v ? o : v; }
+    return v;
+}
+// the part of a difference that is above zero: one IEEE subtraction, one comparison
+__device__ __forceinline__ double plan_excess(double a, double b) {
+#pragma clang fp contract(off)
+    const double d = a - b;
+    return d > 0.0 ? d : 0.0;
+}
+
+template <typename T>
+__device__ __forceinline__ void plan_nodes_body(const PlanArgs &a, double *du, double *red) {
+#pragma clang fp contract(off)
+    const T *const x = static_cast<const T *>(a.x), *const u = static_cast<const T *>(a.u), *const alpha = static_cast<const T *>(a.alpha);
+    const T *const prevU = static_cast<const T *>(a.prevU), *const W = static_cast<const T *>(a.W);
+    const T *const blo = static_cast<const T *>(a.blo), *const bhi = static_cast<const T *>(a.bhi);
+    const int nx = a.nx, nu = a.nu;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tiles = (a.nodes + PLAN_TILE - 1) / PLAN_TILE;
+    for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {      // (uniform trip count: the barriers below)
+        const int n0 = tile * PLAN_TILE;
+        const int cnt = a.nodes - n0 < PLAN_TILE ? a.nodes - n0 : PLAN_TILE;
+        {
+            int nd[PLAN_RPW], par[PLAN_RPW];
+            size_t brow[PLAN_RPW];
+#pragma unroll
+            for (int r = 0; r < PLAN_RPW; r++) {      // a row beyond the tile's end reads node n0 and is dropped
+                const int n = wave * PLAN_RPW + r;
+                nd[r] = n < cnt ? n0 + n : -1;
+                const int nc = n < cnt ? n0 + n : n0;
+                par[r] = a.parent[nc];
+                brow[r] = (size_t)a.stageOf[nc] * a.bStrideStage + (size_t)nc * a.bStrideNode;
+            }
+            double econ[PLAN_RPW], ubox[PLAN_RPW], umax[PLAN_RPW], stored[PLAN_RPW], shrt[PLAN_RPW], xbox[PLAN_RPW], smax[PLAN_RPW], xmax[PLAN_RPW];
+#pragma unroll
+            for (int r = 0; r < PLAN_RPW; r++) econ[r] = ubox[r] = umax[r] = stored[r] = shrt[r] = xbox[r] = smax[r] = xmax[r] = 0.0;
+            for (int t = lane; t < nu; t += 64) {
+                T un[PLAN_RPW], up[PLAN_RPW], al[PLAN_RPW], lo[PLAN_RPW], hi[PLAN_RPW];
+#pragma unroll
+                for (int r = 0; r < PLAN_RPW; r++) {
+                    const int nc = nd[r] >= 0 ? nd[r] : n0;
+                    un[r] = u[(size_t)nc * nu + t];
+                    up[r] = par[r] < 0 ? prevU[t] : u[(size_t)par[r] * nu + t];
+                    al[r] = alpha[(size_t)nc * nu + t];
+                    lo[r] = blo[brow[r] + 2 * nx + t];
+                    hi[r] = bhi[brow[r] + 2 * nx + t];
+                }
+#pragma unroll
+                for (int r = 0; r < PLAN_RPW; r++) {
+                    const bool live = nd[r] >= 0;
+                    const double uv = (double)un[r];
+                    du[t * PLAN_TILE + wave * PLAN_RPW + r] = live ? uv - (double)up[r] : 0.0;
+                    if (live) {
+                        econ[r] = fma_rn((double)al[r], uv, econ[r]);
+                        const double v1 = plan_excess((double)lo[r], uv), v2 = plan_excess(uv, (double)hi[r]);
+                        ubox[r] += v1 + v2;
+                        const double m = v1 > v2 ? v1 : v2;
+                        umax[r] = m > umax[r] ? m : umax[r];
+                    }
+                }
+            }
+            for (int j = lane; j < nx; j += 64) {
+                T xv[PLAN_RPW], lo[PLAN_RPW], xs[PLAN_RPW], hi[PLAN_RPW];
+#pragma unroll
+                for (int r = 0; r < PLAN_RPW; r++) {
+                    const int nc = nd[r] >= 0 ? nd[r] : n0;
+                    xv[r] = x[(size_t)nc * nx + j];
+                    lo[r] = blo[brow[r] + j];
+                    xs[r] = blo[brow[r] + nx + j];
+                    hi[r] = bhi[brow[r] + j];
+                }
+#pragma unroll
+                for (int r = 0; r < PLAN_RPW; r++) {
+                    if (nd[r] >= 0) {
+                        const double v = (double)xv[r];
+                        stored[r] += v;
+                        const double s = plan_excess((double)xs[r], v);
+                        shrt[r] += s;
+                        smax[r] = s > smax[r] ? s : smax[r];
+                        const double v1 = plan_excess((double)lo[r], v), v2 = plan_excess(v, (double)hi[r]);
+                        xbox[r] += v1 + v2;
+                        const double m = v1 > v2 ? v1 : v2;
+                        xmax[r] = m > xmax[r] ? m : xmax[r];
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < PLAN_RPW; r++) {      // (every lane takes part: the loops above hold no wave-wide operation)
+                const double e = wave_sum_f64(econ[r]), st = wave_sum_f64(stored[r]), sh = wave_sum_f64(shrt[r]), xb = wave_sum_f64(xbox[r]),
+                             ub = wave_sum_f64(ubox[r]);
+                const double sm = plan_wave_max(smax[r]), xm = plan_wave_max(xmax[r]), um = plan_wave_max(umax[r]);
+                if (lane == 0 && nd[r] >= 0) {
+                    double *row = a.node + (size_t)nd[r] * PLAN_COLS;
+                    row[PLAN_ECON] = e; row[PLAN_STORED] = st; row[PLAN_SHORT] = sh; row[PLAN_XBOX] = xb; row[PLAN_UBOX] = ub;
+                    row[PLAN_SHORT_MAX] = sm; row[PLAN_XBOX_MAX] = xm; row[PLAN_UBOX_MAX] = um;
+                }
+            }
+        }
+        __syncthreads();
+        // du' W du of every node of the tile: thread t holds row t of W du for the whole tile, PLAN_JB columns of W requested together
+        double q[PLAN_TILE];
+#pragma unroll
+        for (int n = 0; n < PLAN_TILE; n++) q[n] = 0.0;
+        for (int t = threadIdx.x; t < nu; t += PLAN_THREADS) {
+            double wd[PLAN_TILE];
+#pragma unroll
+            for (int n = 0; n < PLAN_TILE; n++) wd[n] = 0.0;
+            for (int j0 = 0; j0 < nu; j0 += PLAN_JB) {
+                T wv[PLAN_JB];
+#pragma unroll
+                for (int jj = 0; jj < PLAN_JB; jj++) wv[jj] = W[t + (size_t)(j0 + jj < nu ? j0 + jj : nu - 1) * nu];
+#pragma unroll
+                for (int jj = 0; jj < PLAN_JB; jj++) {
+                    if (j0 + jj < nu) {
+                        const double w = (double)wv[jj];
+                        const double *dj = du + (size_t)(j0 + jj) * PLAN_TILE;
+#pragma unroll
+                        for (int n = 0; n < PLAN_TILE; n++) wd[n] = fma_rn(w, dj[n], wd[n]);
+                    }
+                }
+            }
+#pragma unroll
+            for (int n = 0; n < PLAN_TILE; n++) q[n] = fma_rn(du[t * PLAN_TILE + n], wd[n], q[n]);
+        }
+#pragma unroll
+        for (int n = 0; n < PLAN_TILE; n++) {
+            const double s = wave_sum_f64(q[n]);
+            if (lane == 0) red[wave * PLAN_TILE + n] = s;
+        }
+        __syncthreads();
+        if ((int)threadIdx.x < cnt) {
+            double s = red[threadIdx.x];
+            for (int w = 1; w < PLAN_WAVES; w++) s += red[w * PLAN_TILE + threadIdx.x];
+            a.node[(size_t)(n0 + threadIdx.x) * PLAN_COLS + PLAN_SMOOTH] = s;
+        }
+        __syncthreads();      // du and red belong to the next tile from here on
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void plan_folds_body(const PlanArgs &a, double *red) {
+#pragma clang fp contract(off)
+    const T *const prob = static_cast<const T *>(a.prob);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if ((int)blockIdx.x < a.N) {      // one stage: its node rows are contiguous
+        const int k = blockIdx.x, s0 = a.stageCum[k], s1 = a.stageCum[k + 1];
+        double acc[PLAN_COLS];
+#pragma unroll
+        for (int c = 0; c < PLAN_COLS; c++) acc[c] = 0.0;
+        for (int i = s0 + threadIdx.x; i < s1; i += PLAN_THREADS) {
+            const double p = (double)prob[i];
+            const double *row = a.node + (size_t)i * PLAN_COLS;
+#pragma unroll
+            for (int c = 0; c < PLAN_SUMS; c++) acc[c] = fma_rn(p, row[c], acc[c]);
+#pragma unroll
+            for (int c = PLAN_SUMS; c < PLAN_COLS; c++) acc[c] = row[c] > acc[c] ? row[c] : acc[c];
+        }
+#pragma unroll
+        for (int c = 0; c < PLAN_COLS; c++) {
+            const double v = c < PLAN_SUMS ? wave_sum_f64(acc[c]) : plan_wave_max(acc[c]);
+            if (lane == 0) red[wave * PLAN_COLS + c] = v;
+        }
+        __syncthreads();
+        if (threadIdx.x < PLAN_COLS) {
+            const int c = threadIdx.x;
+            double v = red[c];
+            for (int w = 1; w < PLAN_WAVES; w++) { const double o = red[w * PLAN_COLS + c]; v = c < PLAN_SUMS ? v + o : (o > v ? o : v); }
+            const bool counted = a.countCrown || k >= a.crownStages;
+            a.stage[(size_t)c * a.N + k] = (c < PLAN_SUMS && !counted) ? 0.0 : v;
+        }
+        return;
+    }
+    const int l = ((int)blockIdx.x - a.N) * PLAN_THREADS + threadIdx.x;      // one leaf per thread, leaf -> root
+    if (l >= a.leaves) return;
+    const int leafNode = a.stageCum[a.N - 1] + l;
+    double acc[PLAN_COLS];
+#pragma unroll
+    for (int c = 0; c < PLAN_COLS; c++) acc[c] = 0.0;
+    const double own = a.node[(size_t)leafNode * PLAN_COLS + PLAN_STORED];
+    int i = leafNode;
+    for (int step = 0; step < a.N && i >= 0; step++) {      // (a path has at most N nodes: a bad parent table cannot keep the loop alive)
+        const double *row = a.node + (size_t)i * PLAN_COLS;
+#pragma unroll
+        for (int c = 0; c < PLAN_SUMS; c++) acc[c] += row[c];
+#pragma unroll
+        for (int c = PLAN_SUMS; c < PLAN_COLS; c++) acc[c] = row[c] > acc[c] ? row[c] : acc[c];
+        i = a.parent[i];
+    }
+    acc[PLAN_STORED] = own;
+    double *out = a.leaf + (size_t)l * PLAN_COLS;
+#pragma unroll
+    for (int c = 0; c < PLAN_COLS; c++) out[c] = acc[c];
+    a.leafNode[l] = leafNode;
+}
+
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void __launch_bounds__(PLAN_THREADS) k_plan_report(PlanArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char plan_smem[];
+    double *du = reinterpret_cast<double *>(plan_smem);      // [nu][PLAN_TILE]: the tile's values of one column are contiguous
+    double *red = du + (size_t)a.nu * PLAN_TILE;             // PLAN_RED doubles
+    if (a.phase == 0) { if (a.f64) plan_nodes_body<double>(a, du, red); else plan_nodes_body<float>(a, du, red); }
+    else { if (a.f64) plan_folds_body<double>(a, red); else plan_folds_body<float>(a, red); }
+}
+
+}  // namespace rn

@@ -248,6 +248,9 @@ struct CtxBase {
     virtual int get_bounds(size_t, double *const *) = 0;
     virtual int set_cut_children(const int *, const int *, int, bool, int, int, const double *, const double *) = 0;
     virtual int cut_moments(double *, double *, size_t) = 0;
+    virtual int plan_report(size_t, double *) = 0;
+    virtual int plan_report_scenarios(size_t, double *, int *) = 0;
+    virtual int plan_report_device(void **, void **, size_t *) = 0;
 };
 
 // ---- in-process stand-in for the communicator (rn_debug_local_group_*): `n` contexts of one process, one host thread each ----
@@ -1556,6 +1559,7 @@ struct Ctx : CtxBase {
         Batch &bt = batch ? *batch : none;
         SweepArgs<T> a = sweep_args(bt);
         a.writePrimal = primalOut ? 1 : 0;
+        if (primalOut && !hessianInput) primalSwept = true;      // (rn_plan_report: d_x and d_u hold a plan from here on)
         if (vPending) { if (hessianInput) { if (int rc = v_flush()) return rc; } else vPending = false; }      // (see v_flush)
         if (hessianInput) {
             a.w = hessianInput;
@@ -2539,7 +2543,7 @@ struct Ctx : CtxBase {
         T *src = d_u;
         if (project) {  // SmpcController.cu:1647-1650: clamp with the (scaled) bounds of the root node
             RN_HIP(hipMemcpyAsync(d_tmp, d_u, d.nu * sizeof(T), hipMemcpyDeviceToDevice, stream));
-            hipLaunchKernelGGL(k_clamp_vec<T>, dim3(1), dim3(128), 0, stream, d_tmp, d_lo + 2 * d.nx, d_hi + 2 * d.nx, d.nu);
+            hipLaunchKernelGGL(k_clamp_vec<>, dim3(1), dim3(128), 0, stream, (void *)d_tmp, (const void *)(d_lo + 2 * d.nx), (const void *)(d_hi + 2 * d.nx), d.nu, sizeof(T) == 8 ? 1 : 0);
             src = d_tmp;
         }
         return download(u0, src, d.nu);
@@ -2623,6 +2627,9 @@ struct Ctx : CtxBase {
 
     // ---- caller data into and out of the context: raw access, operator blocks, tree data, bounds -----------
 #include "caller_data.inc"
+
+    // ---- what the plan at hand costs and where it violates its bounds, per stage and per scenario ------------
+#include "plan_report.inc"
 
     // ---- multi-GPU ---------------------------------------------------------------------------------------
     // The communicator of this context.  ncclCommInitRank blocks until every rank of the id has arrived -- for ever if one never does.
@@ -2938,6 +2945,9 @@ int rn_get_bounds(rn_ctx *ctx, size_t rows, double *xmin, double *xmax, double *
     return ctx->impl->get_bounds(rows, b);
 }
 int rn_debug_cut_moments(rn_ctx *ctx, double *E, double *P, size_t n) { RN_GUARD(ctx); return ctx->impl->cut_moments(E, P, n); }
+int rn_plan_report(rn_ctx *ctx, size_t stages, double *perStage) { RN_GUARD(ctx); return ctx->impl->plan_report(stages, perStage); }
+int rn_plan_report_scenarios(rn_ctx *ctx, size_t leaves, double *perLeaf, int *leafNode) { RN_GUARD(ctx); return ctx->impl->plan_report_scenarios(leaves, perLeaf, leafNode); }
+int rn_plan_report_device(rn_ctx *ctx, void **perStage, void **perLeaf, size_t *leaves) { RN_GUARD(ctx); return ctx->impl->plan_report_device(perStage, perLeaf, leaves); }
 int rn_set_uncertainty(rn_ctx *ctx, int dflag, int pflag, double w) { RN_GUARD(ctx); return ctx->impl->set_uncertainty(dflag, pflag, w); }
 int rn_update_state_control(rn_ctx *ctx, const double *x, const double *u, const double *dm) { RN_GUARD(ctx); return ctx->impl->update_state_control(x, u, dm); }
 int rn_eliminate_input_disturbance_coupling(rn_ctx *ctx, const double *dh, const double *ah) { RN_GUARD(ctx); return ctx->impl->eliminate(dh, ah); }
