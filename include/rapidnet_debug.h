@@ -66,8 +66,9 @@ enum {
     RN_KNOB_TUNE_BIAS_US = 11,     /* rn_exchange_autotune, test of the selection: microseconds per iteration added to THIS rank's measured one-shot time */
     RN_KNOB_STRUCT_LINEAR = 12,    /* structured mode: 0 = the first product k_gemm_prep_m2 in front of the chain walks instead of the linear form (k_up_chain_lin); 2 = the linear form without the chain walk riding in the fused walk + dual update; 3 = the linear form with the subtree sums of beta walked and multiplied in every iteration instead of once per control step; 4 = that constant, but v_i and [L v_i; B L v_i] as two products instead of one with the composite operator; 5 = the composite operator without the forward walk's affine terms in its constant operand */
     RN_KNOB_FUSE_SPLIT = 13,       /* fused forward walk + dual update: workgroups per chain (1 .. chain length); 0 = one per chain and only where the chains fill 3/4 of the CUs (round 6's first rule) */
-    RN_KNOB_STREAM_SKIP = 14,      /* k_stream_gemv: 0 = every span of every operator block is walked; 1 (default) = only the spans that meet a nonzero entry of the dual vector (bitwise the same results) */
-    RN_KNOB_COUNT = 15
+    RN_KNOB_STREAM_SKIP = 14,      /* k_stream_gemv: 0 = every span of every operator block is walked; 1 = only the spans that meet a nonzero entry of the dual vector, whole spans; -1 (default) = the library's choice: that skip, by half-spans where RN_KNOB_STREAM_HALF admits them (bitwise the same results in every form) */
+    RN_KNOB_STREAM_HALF = 15,      /* k_stream_gemv with two slots per thread and an even span, RN_KNOB_STREAM_SKIP at the library's choice: 0 = a span's two halves are walked or skipped together; 1 (default) = each half by itself where half a span is a whole number of 64-byte half lines (bitwise the same results) */
+    RN_KNOB_COUNT = 16
 };
 int rn_debug_set_knob(rn_ctx *ctx, int knob, int value);
 
@@ -82,8 +83,17 @@ int rn_debug_stream_info(rn_ctx *ctx, int info[4]);
  * context.  A span (G consecutive operator columns, rn_get_kernel_info) is live when one of its entries of the dual vector the sweep is evaluated at
  * has any bit but the sign set (-0.0 is zero, a denormal is live; a pair of sweeps in one pass: in either vector); a live column likewise.  With
  * RN_KNOB_STREAM_SKIP = 0 every span is walked and counted.  Synchronises the context's stream, copies one record per workgroup and sums on the host.
- * RN_E_STATE before the first sweep and in the structured mode (no blocks). */
+ * RN_E_STATE before the first sweep and in the structured mode (no blocks).
+ * Where the launch skips half-spans by themselves (rn_debug_stream_units) the live spans are an UPPER BOUND on what it requested: a live span
+ * with one dead half is counted whole here.  rn_algorithmic_bytes counts what was requested: the live units of rn_debug_stream_units. */
 int rn_debug_stream_live(rn_ctx *ctx, long long out[4]);
+
+/* The same launch in the units its skip walks: out = {live units, units, columns per unit}, summed over the blocks.  A unit is half a span
+ * (G / 2 columns; a ragged last span has one or two, ceil(ny / (G / 2)) per block in all) where the launch skips halves by themselves: the skip
+ * at the library's choice (RN_KNOB_STREAM_SKIP = -1), RN_KNOB_STREAM_HALF != 0, two slots per thread, G even and half a span a whole number of
+ * 64-byte half lines.  Everywhere else a unit is a
+ * span and the figures are rn_debug_stream_live's first two with G.  Same synchronisation, same errors. */
+int rn_debug_stream_units(rn_ctx *ctx, long long out[3]);
 
 /* The gradient restart test (rn_set_restart, rapidnet.h) alone: runs k_restart_test on the context's current w (the last sweep's input, what
  * RN_BUF_ACC_* shows), y+ and y and returns out = {g, na2, nb2} -- the kernel can be checked without running a solve.  Allocates the kernel's

@@ -40,13 +40,13 @@ def _stamp(out, srcs, extra=()):
 # family per unit, so that an edit of one kernel header recompiles that unit and the host driver (which only parses the headers: its
 # kernels are declared `extern template`, csrc/instantiations/*.inc, tools/gen_instantiations.py).
 UNITS = {
-    "k_stream": ["common.hpp", "k_stream.hpp"],
+    "k_stream": ["common.hpp", "k_stream.hpp", "stream_bits.hpp"],
     "k_dual": ["common.hpp", "k_dual.hpp"],
     "k_walks": ["common.hpp", "k_dual.hpp", "k_walks.hpp"],
     "k_slab": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp"],
     "k_misc": ["common.hpp", "k_misc.hpp", "k_plan.hpp"],
     "k_fbe": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "fbe_kernels.hpp"],
-    "rapidnet_capi": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "k_stream.hpp", "k_misc.hpp", "k_plan.hpp", "kernels.hpp", "fbe_kernels.hpp", "fbe_methods.inc",
+    "rapidnet_capi": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "k_stream.hpp", "stream_bits.hpp", "k_misc.hpp", "k_plan.hpp", "kernels.hpp", "fbe_kernels.hpp", "fbe_methods.inc",
                       "caller_data.inc", "plan_report.inc", "partition.hpp", "bounds.hpp"],
 }
 OBJ_DIR = os.path.join(HERE, "build")
@@ -164,6 +164,7 @@ TEST_TREE_DATA = os.path.join(BIN_DIR, "test_tree_data")
 TEST_BOUNDS = os.path.join(BIN_DIR, "test_bounds")
 TEST_RESTART = os.path.join(BIN_DIR, "test_restart")
 TEST_PLAN_REPORT = os.path.join(BIN_DIR, "test_plan_report")
+TEST_STREAM_BITS = os.path.join(BIN_DIR, "test_stream_bits")
 
 
 def build_host(force=False):
@@ -223,6 +224,12 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_PLAN_REPORT, test_src, "-L" + HERE, "-lrapidnet_host",
                                "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
         _stamp(TEST_PLAN_REPORT, [test_src] + deps + hdr)
+    # (host only: the column-mask arithmetic of the streaming kernel's walk, csrc/stream_bits.hpp, against a bit-by-bit loop)
+    test_src = os.path.join(ROOT, "tests", "cpp", "test_stream_bits.cpp")
+    bits_hdr = os.path.join(CSRC, "stream_bits.hpp")
+    if force or _stale(TEST_STREAM_BITS, [test_src, bits_hdr]):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-I" + CSRC, "-o", TEST_STREAM_BITS, test_src])
+        _stamp(TEST_STREAM_BITS, [test_src, bits_hdr])
     return LIB_HOST
 
 

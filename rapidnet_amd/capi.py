@@ -31,7 +31,7 @@ BOUNDS_SHARED, BOUNDS_PER_STAGE, BOUNDS_PER_NODE = 0, 1, 2      # rn_set_bounds
 BOUNDS = {"shared": BOUNDS_SHARED, "stage": BOUNDS_PER_STAGE, "node": BOUNDS_PER_NODE}
 # include/rapidnet_debug.h, RN_KNOB_*
 KNOBS = {k: i for i, k in enumerate(("dual_trips", "dual_pipe", "vlv_wide", "slab_pipe", "slab_frag", "unscaled_walk", "stream_two_per_cu",
-                                     "stream_split", "nama_pair", "ls_sequential", "value_mfma", "tune_bias_us", "struct_linear", "fuse_split", "stream_skip"))}
+                                     "stream_split", "nama_pair", "ls_sequential", "value_mfma", "tune_bias_us", "struct_linear", "fuse_split", "stream_skip", "stream_half"))}
 EXCHANGE_COLLECTIVE, EXCHANGE_ONESHOT, EXCHANGE_AUTO = 0, 1, 2
 # rn_plan_report: the columns of both tables, in the order of RN_PLAN_* (the first six are sums, the last three maxima)
 PLAN_COLUMNS = ("econ", "smooth", "stored", "shortExp", "xboxExp", "uboxExp", "shortMax", "xboxMax", "uboxMax")
@@ -54,7 +54,7 @@ SYMBOLS = [
     "rn_debug_set_allreduce", "rn_debug_local_group_create", "rn_debug_local_group_join", "rn_debug_local_group_destroy",
     "rn_guard_check", "rn_device_memory_info", "rn_reserve_iterations", "rn_profile_read_collective", "rn_debug_inject_allocation", "rn_guard_report", "rn_debug_guard_poke",
     "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_set_bounds", "rn_set_bounds_device", "rn_get_bounds_layout", "rn_get_bounds", "rn_debug_cut_moments",
-    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live",
+    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live", "rn_debug_stream_units",
     "rn_plan_report", "rn_plan_report_scenarios", "rn_plan_report_device",
 ]
 
@@ -247,6 +247,7 @@ def load():
     lib.rn_debug_set_knob.argtypes = [vp, ip, ip]
     lib.rn_debug_stream_info.argtypes = [vp, dp]
     lib.rn_debug_stream_live.argtypes = [vp, dp]
+    lib.rn_debug_stream_units.argtypes = [vp, dp]
     lib.rn_profile_read_collective.argtypes = [vp, dp, dp]
     lib.rn_set_tree_data.argtypes = [vp, C.c_size_t, dp, dp, dp]
     lib.rn_set_tree_data_device.argtypes = [vp, C.c_size_t, ip, vp, vp, vp]
@@ -849,6 +850,13 @@ class Solver:
         out = np.zeros(4, dtype=np.int64)
         self._check(self.lib.rn_debug_stream_live(self.h, out.ctypes.data))
         return dict(zip(("liveSpans", "spans", "liveColumns", "columns"), (int(v) for v in out)))
+
+    def streamUnits(self):
+        """rn_debug_stream_units (include/rapidnet_debug.h): the most recent launch of k_stream_gemv in the units its skip walks -- half-spans
+        where it skips them by themselves, whole spans elsewhere."""
+        out = np.zeros(3, dtype=np.int64)
+        self._check(self.lib.rn_debug_stream_units(self.h, out.ctypes.data))
+        return dict(zip(("liveUnits", "units", "columnsPerUnit"), (int(v) for v in out)))
 
     def debugGuardPoke(self, nbytes):
         self._check(self.lib.rn_debug_guard_poke(self.h, int(nbytes)))

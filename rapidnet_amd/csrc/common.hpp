@@ -421,6 +421,9 @@ struct StreamSplit {
     // the skip of spans that meet no nonzero entry of w (k_stream.hpp, stream_walk): 0 = every span is walked
     int skip;
     int2 *live;       // [workgroups] what each workgroup walked: {spans, columns | ragged last span among them << 30} (nullptr: not recorded)
+    // the walk over half-spans (NL = 2, G even: stream_walk_half): 1 = a half is skipped by itself, 0 = both halves take their span's liveness
+    int half;
+    int *units;       // [workgroups] the units each workgroup walked (half-spans there, spans elsewhere); recorded with `live`
 };
 
 // Bookkeeping of the PREVIOUS iteration's fused dual update (optimistic modes: no decision launch of its own): folds the

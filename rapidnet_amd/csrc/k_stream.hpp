@@ -2,6 +2,7 @@
 // (part of the kernel sources of librapidnet_hip.so; kernels.hpp includes every family header, the translation units k_*.hip instantiate them)
 #pragma once
 #include "common.hpp"
+#include "stream_bits.hpp"
 
 namespace rn {
 
@@ -45,6 +46,8 @@ namespace rn {
 // and meets the live spans in increasing order.  The first group cannot be requested before
 // w has arrived any more.  sp.skip == 0: every span is walked (the mask is "span exists").
 // Returns what was walked: spans, columns, and whether the ragged last span was among them.
+// NL = 2 (the 493-scenario tree in every precision): the unit of the skip is HALF a span and the walk is stream_walk_half, below; stream_walk is the
+// walk of NL = 1, 3, 4.
 __device__ __forceinline__ bool stream_nz(double v) { return ((unsigned long long)__double_as_longlong(v) << 1) != 0ull; }
 __device__ __forceinline__ bool stream_nz(float v) { return (__float_as_uint(v) << 1) != 0u; }
 template <typename T, typename VT, int VPL, int NL, int D, int NR>
@@ -105,11 +108,7 @@ __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *
         if (s < span1) {
             const int c0 = s * G;
             if (skip) {      // the span's G bits of the column mask (they may straddle two words)
-                const int sh = c0 & 63;
-                const unsigned long long lo = sh_nz[c0 >> 6], hi = sh_nz[(c0 >> 6) + 1];
-                unsigned long long bits = (lo >> sh) | (sh ? hi << (64 - sh) : 0ull);
-                if (G < 64) bits &= (1ull << G) - 1ull;
-                cols = __popcll(bits);
+                cols = __popcll(stream_mask_bits(sh_nz, c0, G));
             } else {
                 cols = ny - c0 < G ? ny - c0 : G;
             }
@@ -177,6 +176,148 @@ __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *
 #undef RN_LOADH
 #undef RN_USEH
 }
+// THE WALK OVER HALF-SPANS: what every NL = 2 instantiation runs (the kernels choose it with if constexpr; stream_walk above is NL = 1, 3, 4).
+// A thread's two slots of a span are two UNITS of the walk, unit u = 2 * span + h, ONE load per thread each.
+//   G even (stream_slots): h is the half of the span -- unit u holds the columns [u * G/2, (u + 1) * G/2), S/2 = G/2 * SPC slots, and on the
+// shapes the host admits (Ctx::stream_half_on) a whole number of 128-byte lines (fp64, 2nv = 194: 4 columns x 196 doubles = 6 272 B = 49
+// lines).  Thread t' < S/2 owns slot t' of the first half and slot S/2 + t' of the second: S/2 is a multiple of SPC, so both are the thread's
+// same rows.  Threads >= S/2 are idle as the padded lanes always were (a clamped address, nothing stored in sh_red), and a wave without any
+// slot does not enter the walk.  With halfOn the SKIP works on units: one lane per unit reads its G/2 bits of sh_nz (stream_mask_bits).  On the
+// 493-scenario tree 0.33 of the half-spans are live against 0.48 of the spans (61 % of the live spans have one live half).
+//   G odd, or halfOn == 0 (RN_KNOB_STREAM_HALF = 0, halves that are not whole lines): the slots are those of the span walk where G is odd (t and
+// t + 512), and both units of a span take the SPAN's liveness (each lane reads the span's G bits): the same code, the traffic of the span walk.
+//   Chunks of 64 units = 32 spans; groups of 2 D live units (the requests in flight and the buffer registers of D spans x 2 loads); the partial
+// group goes in front; the steady state has no branch.  h is a scalar (the popped index's low bit) and selects, by scalar-conditioned moves,
+// the slot's offset and column and which accumulator meets the dual entry -- the other one meets +0: a * (+0) added to a partial that began at
+// +0 changes no bit, for the reason the skip changes none (and like the skip it presumes finite block entries).  Every slot's partial still
+// meets its spans in increasing order: the outputs are the bits of the span walk and of the walk over everything.
+//   The ragged last span: each of its live units a guarded load of its own behind the groups.  span0 / span1, liveSpans, liveCols and liveRagged
+// are in SPANS as in stream_walk; liveUnits counts the units walked (bits 0-15; with halfOn the live units of the ragged span among them in bits
+// 16-19 and their columns from bit 20 on: rn_algorithmic_bytes counts those units at the columns they have).
+template <typename T, typename VT, int VPL, int DU, int NR>
+__device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, const T *sh_y, const T *sh_y2, const unsigned long long *sh_nz, int skip, int halfOn, int span0, int span1,
+                                                 int G, int ny, int spanSlots, const int (&off)[2], const int (&cj)[2], const T (&msk)[2], T (&part)[2][VPL],
+                                                 T (&part2)[NR == 2 ? 2 : 1][VPL], int &liveSpans, int &liveCols, int &liveRagged, int &liveUnits) {
+    const int lane = threadIdx.x & 63, Gh = G >> 1;
+    const int u0 = 2 * span0, u1 = 2 * span1;
+    const int rag = (ny % G != 0 && span1 * G > ny) ? ny / G : -1;      // the ragged last span, where this range holds it
+    VT bufA[DU], bufB[DU];
+    int sA[DU], sB[DU];
+    liveSpans = 0; liveCols = 0; liveRagged = 0; liveUnits = 0;
+    const char *const Abb = reinterpret_cast<const char *>(Ab);
+    const unsigned spanBytes = (unsigned)spanSlots * 16u;
+    const unsigned offB[2] = {(unsigned)off[0] * 16u, (unsigned)off[1] * 16u};
+#define RN_POP(sv, d) { sv[d] = __builtin_amdgcn_readfirstlane(ub + __builtin_ctzll(mf)); mf &= mf - 1ull; }
+#define RN_LOAD1(buf, sv, d) buf[d] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (size_t)(sv[d] >> 1) * spanBytes + ((sv[d] & 1) ? offB[1] : offB[0])));
+#define RN_USE1(buf, sv, d) {                                                                                          \
+        const bool h1 = (sv[d] & 1) != 0;                                                                              \
+        const int cy = (sv[d] >> 1) * G + (h1 ? cj[1] : cj[0]);                                                        \
+        const T yv = sh_y[cy];                                                                                         \
+        const T ya = h1 ? (T)0 : yv, yb = h1 ? yv : (T)0;                                                              \
+        _Pragma("unroll") for (int e = 0; e < VPL; e++) { part[0][e] += (T)buf[d][e] * ya; part[1][e] += (T)buf[d][e] * yb; } \
+        if (NR == 2) {                                                                                                 \
+            const T yv2 = sh_y2[cy];                                                                                   \
+            const T ya2 = h1 ? (T)0 : yv2, yb2 = h1 ? yv2 : (T)0;                                                      \
+            _Pragma("unroll") for (int e = 0; e < VPL; e++) { part2[0][e] += (T)buf[d][e] * ya2; part2[NR == 2 ? 1 : 0][e] += (T)buf[d][e] * yb2; } \
+        }                                                                                                              \
+    }
+#define RN_LOADG(buf, sv) _Pragma("unroll") for (int d = 0; d < DU; d++) { RN_POP(sv, d) RN_LOAD1(buf, sv, d) }
+#define RN_USEG(buf, sv) _Pragma("unroll") for (int d = 0; d < DU; d++) RN_USE1(buf, sv, d)
+#define RN_LOADH(buf, sv) _Pragma("unroll") for (int d = 0; d < DU - 1; d++) if (d < nHead) { RN_POP(sv, d) RN_LOAD1(buf, sv, d) }
+#define RN_USEH(buf, sv) _Pragma("unroll") for (int d = 0; d < DU - 1; d++) if (d < nHead) RN_USE1(buf, sv, d)
+    for (int ub = u0; ub < u1; ub += 64) {      // chunks of 64 units (ub is even: a span's two units share a chunk); a group never crosses a chunk
+        const int u = ub + lane;
+        // the run of columns whose liveness is the unit's: its own half, or its span
+        const int c0 = halfOn ? u * Gh : (u >> 1) * G, n = halfOn ? Gh : G;
+        int cols = 0;
+        if (u < u1 && c0 < ny) cols = skip ? __popcll(stream_mask_bits(sh_nz, c0, n)) : (ny - c0 < n ? ny - c0 : n);
+        const unsigned long long m = __ballot(cols > 0);
+        liveSpans += __popcll((m | (m >> 1)) & 0x5555555555555555ull);
+        liveUnits += __popcll(m);
+        if (threadIdx.x < 64) {      // (the record: the first wave's lane 0 keeps it; a span's columns are counted once)
+            int t = (halfOn || !(lane & 1)) ? cols : 0;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+            liveCols += t;
+        }
+        const int ragSh = 2 * rag - ub;
+        const unsigned long long ragBits = (ragSh >= 0 && ragSh < 64) ? (m & (3ull << ragSh)) : 0ull;
+        unsigned long long mf = m & ~ragBits;
+        const int nLive = __popcll(mf), nGroups = nLive / DU, nHead = nLive - nGroups * DU;
+        RN_LOADH(bufB, sB)
+        if (nGroups > 0) RN_LOADG(bufA, sA)
+        RN_USEH(bufB, sB)
+        if (nGroups > 0) {
+            int g = 0;
+            for (; g + 2 < nGroups; g += 2) {      // steady state: no branch inside
+                RN_LOADG(bufB, sB)
+                RN_USEG(bufA, sA)
+                RN_LOADG(bufA, sA)
+                RN_USEG(bufB, sB)
+            }
+            if (g + 1 < nGroups) {
+                RN_LOADG(bufB, sB)
+                RN_USEG(bufA, sA)
+                RN_USEG(bufB, sB)
+            } else {
+                RN_USEG(bufA, sA)
+            }
+        }
+        if (ragBits) {      // the ragged last span: its live units, each a guarded load, last (an idle slot or one behind the block reads the block's first slot against zero)
+            liveRagged = 1;
+#pragma unroll
+            for (int h = 0; h < 2; h++)
+                if ((ragBits >> (ragSh + h)) & 1ull) {
+                    if (halfOn) { const int left = ny - (2 * rag + h) * Gh; liveUnits += (1 << 16) + ((left < Gh ? left : Gh) << 20); }      // (the record: see below)
+                    const int c = rag * G + cj[h];
+                    const bool ok = msk[h] != (T)0 && c < ny;      // (a column of the block: the slot lies inside it)
+                    const VT bufR = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (ok ? (size_t)rag * spanBytes + offB[h] : (size_t)0)));
+                    const T yc = ok ? sh_y[c] : (T)0;
+#pragma unroll
+                    for (int e = 0; e < VPL; e++) part[h][e] += (T)bufR[e] * yc;
+                    if (NR == 2) {
+                        const T yc2 = ok ? sh_y2[c] : (T)0;
+#pragma unroll
+                        for (int e = 0; e < VPL; e++) part2[NR == 2 ? h : 0][e] += (T)bufR[e] * yc2;
+                    }
+                }
+        }
+    }
+#undef RN_POP
+#undef RN_LOAD1
+#undef RN_USE1
+#undef RN_LOADG
+#undef RN_USEG
+#undef RN_LOADH
+#undef RN_USEH
+}
+// Which slots of a span thread `tid` owns: off[j] (clamped to a slot of the span for idle threads), their columns cj[j] inside the span, msk[j] = 1
+// for an owned slot.  Slots tid, tid + 512, ...; NL = 2 with an even G: slot tid of each HALF of the span (stream_walk_half).
+template <typename T, int NL>
+__device__ __forceinline__ void stream_slots(int tid, int G, int SPC, int spanSlots, int (&off)[NL], int (&cj)[NL], T (&msk)[NL]) {
+    const bool halves = NL == 2 && !(G & 1);
+    const int stride = halves ? spanSlots >> 1 : STREAM_THREADS;
+#pragma unroll
+    for (int j = 0; j < NL; j++) {
+        const int q = tid + stride * j;
+        const bool ok = halves ? tid < stride : q < spanSlots;
+        off[j] = ok ? q : (halves ? stride * (j + 1) - 1 : spanSlots - 1);          // idle slots re-read a last slot and are not stored
+        cj[j] = off[j] / SPC;
+        msk[j] = ok ? (T)1 : (T)0;
+    }
+}
+// the NL = 2 kernels' call of the walk over units: every wave that owns a slot (the kernels call stream_walk themselves for NL = 1, 3, 4 -- through
+// a common wrapper those instantiations came out of the compiler with up to 10 more VGPRs and a wave less per SIMD)
+template <typename T, typename VT, int VPL, int DU, int NR>
+__device__ __forceinline__ void stream_walk_two(const VT *__restrict__ Ab, const T *sh_y, const T *sh_y2, const unsigned long long *sh_nz, int skip, int halfOn, int span0, int span1,
+                                                int G, int ny, int spanSlots, const int (&off)[2], const int (&cj)[2], const T (&msk)[2],
+                                                T (&part)[2][VPL], T (&part2)[NR == 2 ? 2 : 1][VPL], int &liveSpans, int &liveCols, int &liveRagged, int &liveUnits) {
+    liveSpans = 0; liveCols = 0; liveRagged = 0; liveUnits = 0;
+    const int firstIdle = (G & 1) ? STREAM_THREADS : spanSlots >> 1;      // the first thread without a slot
+    if (__builtin_amdgcn_readfirstlane((int)threadIdx.x & ~63) < firstIdle)
+        stream_walk_half<T, VT, VPL, DU, NR>(Ab, sh_y, sh_y2, sh_nz, skip, (G & 1) ? 0 : halfOn, span0, span1, G, ny, spanSlots, off, cj, msk, part, part2,
+                                            liveSpans, liveCols, liveRagged, liveUnits);
+}
 // the workgroup's copy of w (and of the second right-hand side) into LDS, and the column mask sh_nz of the skip beside it: every wave ballots its
 // 64 columns (trip count the same for every thread: (ny + 63) / 64 + 1 words, the last one zero).  w0 / w20: the first STREAM_THREADS entries,
 // requested by the caller in front of everything else.
@@ -195,9 +336,14 @@ __device__ __forceinline__ void stream_stage_w(const T *__restrict__ w, const T 
         if ((tid & 63) == 0 && (c >> 6) < nzWords) sh_nz[c >> 6] = b;
     }
 }
-// what a workgroup walked, for rn_debug_stream_live / rn_algorithmic_bytes: one 8-byte store per workgroup, overwritten by every launch
-__device__ __forceinline__ void stream_record(int2 *live, int liveSpans, int liveCols, int liveRagged) {
-    if (threadIdx.x == 0 && live) live[blockIdx.x] = make_int2(liveSpans, liveCols | (liveRagged << 30));
+// what a workgroup walked, for rn_debug_stream_live / rn_algorithmic_bytes (spans) and rn_debug_stream_units (the units of the walk: half-spans where
+// stream_walk_half ran, i.e. NL = 2): one 8-byte and there one 4-byte store per workgroup, overwritten by every launch
+template <bool UNITS>      // (the instantiations that walk spans store what they always stored: their units are the spans)
+__device__ __forceinline__ void stream_record(int2 *live, int *units, int liveSpans, int liveCols, int liveRagged, int liveUnits) {
+    if (threadIdx.x == 0 && live) {
+        live[blockIdx.x] = make_int2(liveSpans, liveCols | (liveRagged << 30));
+        if (UNITS) units[blockIdx.x] = liveUnits;
+    }
 }
 template <typename T>
 struct StreamRhs2 { const T *w; T *my; T *qa; };
@@ -209,6 +355,9 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
     //  keeps the kernel inside its registers: 150-172 instead of 256 + 20-28 bytes of scratch per lane with the full depth.  The
     //  order in which a thread meets its columns does not depend on the depth: same sums, bit for bit)
     constexpr int VPL = Slot<T>::N, D0 = NL <= 2 ? (SPLIT ? RN_STREAM_D - 1 : RN_STREAM_D) : RN_STREAM_D_WIDE, D = (NR == 2 && sizeof(T) == 4) ? (NL == 4 ? 1 : D0 - 1) : D0;
+    // (NL = 2: units per group of the walk over half-spans -- the loads in flight of D spans; the fp32 pair one unit fewer: 169 VGPRs with 8, one
+    //  over what leaves three waves per SIMD as the span walk's 142 did)
+    constexpr int DU = 2 * D - ((NR == 2 && sizeof(T) == 4) ? 1 : 0);
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *sh_y = reinterpret_cast<T *>(smem_raw);          // ny (+ G of zero padding is not needed: guarded reads)
     T *sh_red = sh_y + ((a.ny + 3) & ~3);               // G * LD
@@ -228,14 +377,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
     const int span0 = SPLIT ? (second ? sp.spanHalf : 0) : 0, span1 = (split && !second) ? sp.spanHalf : spansAll;
     int off[NL], cj[NL];
     T msk[NL];
-#pragma unroll
-    for (int j = 0; j < NL; j++) {
-        const int q = tid + STREAM_THREADS * j;
-        const bool ok = q < spanSlots;
-        off[j] = ok ? q : spanSlots - 1;          // idle slots re-read the last slot of the span and multiply by zero
-        cj[j] = off[j] / SPC;
-        msk[j] = ok ? (T)1 : (T)0;
-    }
+    stream_slots<T, NL>(tid, G, SPC, spanSlots, off, cj, msk);
     T part[NL][VPL], part2[NR == 2 ? NL : 1][VPL];
 #pragma unroll
     for (int j = 0; j < NL; j++)
@@ -270,8 +412,9 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
         for (int t = tid + STREAM_THREADS; t < nx; t += STREAM_THREADS)
             r2.qa[(size_t)node * nx + t] = stream_qa_elem(spn, dyRow[t], sh_y2[t], dyRow[nx + t], sh_y2[nx + t]);
     }
-    int liveSpans, liveCols, liveRagged;
-    stream_walk<T, VT, VPL, NL, D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, span0, span1, G, ny, spanSlots, blockSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged);
+    int liveSpans, liveCols, liveRagged, liveUnits;
+    if constexpr (NL == 2) stream_walk_two<T, VT, VPL, DU, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, sp.half, span0, span1, G, ny, spanSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged, liveUnits);
+    else { stream_walk<T, VT, VPL, NL, D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, span0, span1, G, ny, spanSlots, blockSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged); liveUnits = 0; }
 #pragma unroll
     for (int j = 0; j < NL; j++)
         if (msk[j] != (T)0) {
@@ -280,7 +423,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
         }
     if (tid < nx && !second) stream_out(qa0, a.qa + (size_t)node * nx + tid);
     if (NR == 2 && tid < nx) stream_out(qa02, r2.qa + (size_t)node * nx + tid);
-    stream_record(sp.live, liveSpans, liveCols, liveRagged);
+    stream_record<NL == 2>(sp.live, sp.units, liveSpans, liveCols, liveRagged, liveUnits);
     __syncthreads();
     T *const myOut = second ? sp.my2 + (size_t)(node - sp.first) * 2 * nv : a.my + (size_t)node * 2 * nv;
     if (NR == 2) {      // both right-hand sides' partials folded in one walk (each in the order of the one-vector kernel): the LDS round trips overlap
@@ -318,10 +461,10 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
 // same fold over k): bitwise the results of two unsplit launches.  NL >= 3 runs groups one span shorter (D = 2) to stay inside the registers;
 // the depth does not change the order in which a thread meets its columns.
 // LDS: NR * (ny + G * LD) doubles (NR = 2: up to the CU's 160 KB, Ctx::launch_stream).  HBM bytes per node: LD*ny*4 + NR*(ny + 2nv + nx)*8.
-// Registers (hipcc's resource report, SPLIT = false | true; with the walk over live spans): NL = 1: 120 | 72 VGPRs, NL = 2: 184 | 156, NL = 3: 193 | 188,
-// NL = 4: 255 | 248; no scratch (k_stream_gemv<float, 2, *>: 160 | 122, <double, 2, *>: 147 | 123 -- the SPLIT instantiations with NL <= 2 walk groups of
-// RN_STREAM_D - 1 spans, which is what fits two workgroups per CU in the native types).  NR = 2 (SPLIT = false): NL = 1: 138, NL = 2: 215, NL = 3: 210,
-// NL = 4: 229 (groups of one span); no scratch, two waves per SIMD from NL = 2 on (one workgroup per CU).
+// Registers (hipcc's resource report, SPLIT = false | true; NL = 2 with the walk over half-spans, the others with the walk over live spans): NL = 1: 120 | 64 VGPRs,
+// NL = 2: 211 | 125 (span walk: 184 | 156), NL = 3: 193 | 188, NL = 4: 255 | 248; no scratch (k_stream_gemv<float, 2, *>: 137 | 125, <double, 2, *>: 123 | 125 -- span walk
+// 160 | 122 and 147 | 123; the SPLIT instantiations with NL <= 2 walk groups of RN_STREAM_D - 1 spans = 8 units, which is what fits two workgroups per CU).  NR = 2
+// (SPLIT = false): NL = 1: 138, NL = 2: 247 (span walk: 215), NL = 3: 210, NL = 4: 229 (groups of one span); no scratch, two waves per SIMD from NL = 2 on.
 template <int NL, bool SPLIT, int NR = 1>
 __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_mixed(SweepArgs<double> a, int G, int node0, StreamSplit<double> sp, StreamRhs2<double> r2) {
     static_assert(NR == 1 || !SPLIT, "two right-hand sides: unsplit launches only");
@@ -345,14 +488,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
     const int span0 = SPLIT ? (second ? sp.spanHalf : 0) : 0, span1 = (split && !second) ? sp.spanHalf : spansAll;
     int off[NL], cj[NL];
     T msk[NL];
-#pragma unroll
-    for (int j = 0; j < NL; j++) {
-        const int q = tid + STREAM_THREADS * j;
-        const bool ok = q < spanSlots;
-        off[j] = ok ? q : spanSlots - 1;          // idle slots re-read the last slot of the span and multiply by zero
-        cj[j] = off[j] / SPC;
-        msk[j] = ok ? (T)1 : (T)0;
-    }
+    stream_slots<T, NL>(tid, G, SPC, spanSlots, off, cj, msk);
     T part[NL][VPL], part2[NR == 2 ? NL : 1][VPL];
 #pragma unroll
     for (int j = 0; j < NL; j++)
@@ -383,8 +519,9 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
         for (int t = tid + STREAM_THREADS; t < nx; t += STREAM_THREADS)
             r2.qa[(size_t)node * nx + t] = stream_qa_elem(spn, dyRow[t], sh_y2[t], dyRow[nx + t], sh_y2[nx + t]);
     }
-    int liveSpans, liveCols, liveRagged;
-    stream_walk<T, VT, VPL, NL, D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, span0, span1, G, ny, spanSlots, blockSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged);
+    int liveSpans, liveCols, liveRagged, liveUnits;
+    if constexpr (NL == 2) stream_walk_two<T, VT, VPL, 2 * D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, sp.half, span0, span1, G, ny, spanSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged, liveUnits);
+    else { stream_walk<T, VT, VPL, NL, D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, span0, span1, G, ny, spanSlots, blockSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged); liveUnits = 0; }
 #pragma unroll
     for (int j = 0; j < NL; j++)
         if (msk[j] != (T)0) {
@@ -393,7 +530,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_
         }
     if (tid < nx && !second) stream_out(qa0, a.qa + (size_t)node * nx + tid);
     if (NR == 2 && tid < nx) stream_out(qa02, r2.qa + (size_t)node * nx + tid);
-    stream_record(sp.live, liveSpans, liveCols, liveRagged);
+    stream_record<NL == 2>(sp.live, sp.units, liveSpans, liveCols, liveRagged, liveUnits);
     __syncthreads();
     T *const myOut = second ? sp.my2 + (size_t)(node - sp.first) * 2 * nv : a.my + (size_t)node * 2 * nv;
     if (NR == 2) {      // both right-hand sides' partials folded in one walk, each in the order of the one-vector kernel

@@ -178,6 +178,7 @@ struct CtxBase {
     virtual int profile_read(double *, long *) = 0;
     virtual int algorithmic_bytes(double *, double *) const = 0;
     virtual int stream_live(long long *) = 0;
+    virtual int stream_units(long long *) = 0;
     virtual int synchronize() = 0;
     virtual void *stream_handle() = 0;
     virtual int comm_init(int, int, const void *, double timeoutSeconds = -1.0) = 0;
@@ -1149,17 +1150,24 @@ struct Ctx : CtxBase {
     int algorithmic_bytes(double *bwd, double *dual) const override {
         // k_stream_gemv, one launch = the whole tree: A_i (2nv x ny, unpadded) read once + y_i read + m1,m2,a_i written
         // (fp32 storage under fp64 iterates: the block at 4 bytes per entry, the vectors at 8)
-        // With the skip of spans that meet no nonzero dual entry (stream_walk) the block bytes are those of the spans the MOST RECENT launch walked:
-        // whole spans at G * LD entries, the ragged last span at its ny % G columns; before any launch and with RN_KNOB_STREAM_SKIP = 0 the dense figure
+        // With the skip (stream_walk, stream_walk_half) the block bytes are those of the units the MOST RECENT launch walked: whole spans at G * LD entries, the
+        // ragged last span at its ny % G columns -- or, where the launch skips half-spans by themselves (stream_half_on), live halves at G / 2 columns and
+        // those of a ragged span at the columns they have; before any launch and with RN_KNOB_STREAM_SKIP = 0 the dense figure
         const double s = sizeof(T), n = d.nodes, sa = block_elem();
         if (bwd) {
             *bwd = structured ? 0.0 : n * ((double)2 * d.nv * ny * sa + (ny + 2.0 * d.nv + d.nx) * s);
             if (!structured && stream_skip() && lastStreamGrid > 0) {
-                long long live[4], ragged = 0;
-                if (int rc = const_cast<Ctx *>(this)->stream_live_sum(live, &ragged)) return rc;      // (a copy from the device: changes nothing the context computes)
                 int G, NL;
                 stream_shape(&G, &NL);
-                *bwd = ((double)(live[0] - ragged) * G + (double)ragged * (ny % G)) * LD * sa + n * (ny + 2.0 * d.nv + d.nx) * s;
+                if (stream_half_on(G, NL)) {
+                    long long units = 0, ragUnits = 0, ragCols = 0;
+                    if (int rc = const_cast<Ctx *>(this)->stream_units_sum(&units, &ragUnits, &ragCols)) return rc;
+                    *bwd = ((double)(units - ragUnits) * (G / 2) + (double)ragCols) * LD * sa + n * (ny + 2.0 * d.nv + d.nx) * s;
+                } else {
+                    long long live[4], ragged = 0;
+                    if (int rc = const_cast<Ctx *>(this)->stream_live_sum(live, &ragged)) return rc;      // (a copy from the device: changes nothing the context computes)
+                    *bwd = ((double)(live[0] - ragged) * G + (double)ragged * (ny % G)) * LD * sa + n * (ny + 2.0 * d.nv + d.nx) * s;
+                }
             }
         }
         // fused dual update: Hx, w, y+prev read, y+, w_next written (+ the two scaled-bound streams unless they are regenerated)
@@ -1206,11 +1214,30 @@ struct Ctx : CtxBase {
     // the skip of operator spans that meet no nonzero entry of w (k_stream.hpp, stream_walk; RN_KNOB_STREAM_SKIP = 0: every span): what every workgroup of
     // the most recent launch walked is in d_streamLive (rn_debug_stream_live, rn_algorithmic_bytes); lastStreamGrid = 0: no launch yet
     int2 *d_streamLive = nullptr;
+    int *d_streamUnits = nullptr;      // the units each workgroup walked (rn_debug_stream_units)
     int lastStreamGrid = 0, lastStreamSplitFirst = 0;
     bool stream_skip() const { return knob[RN_KNOB_STREAM_SKIP] != 0; }
+    // The skip at HALF-span granularity (k_stream.hpp, stream_walk_half; RN_KNOB_STREAM_HALF, default on): where the kernel's units are half-spans
+    // (NL = 2, G even) and half a span is a whole number of 64-byte HALF lines.  fp32 blocks of 2nv = 194 rows: 8 columns x 196 floats = 6 272 B =
+    // 49 whole lines.  fp64: LD = 194, 4 columns x 194 doubles = 6 208 B = 48.5 lines -- a span's two halves share its middle line, so a lone
+    // live half fetches 49 lines for 48.5 and two live halves request the middle line in two wave-loads (as every wave-load boundary inside a
+    // span always did: 1 KB wave-loads over columns of 1 552 B); measured on the 493-scenario tree, profiles/ab_stream_half.txt.  A half that
+    // is not even a whole number of half lines is not skipped by itself (no such shape was measured).
+    // Off: both halves take their span's liveness.  RN_KNOB_STREAM_SKIP = 1 FORCES the skip by whole spans, the form that value has always selected
+    // (tests/test_gpu_stream_skip.py holds rn_algorithmic_bytes of such contexts to the bytes of the live spans); the half-spans belong to the
+    // library's own choice, knob -1.
+    bool stream_half_on() const {
+        int G, NL;
+        stream_shape(&G, &NL);
+        return stream_half_on(G, NL);
+    }
+    bool stream_half_on(int G, int NL) const {
+        return knob[RN_KNOB_STREAM_SKIP] < 0 && knob[RN_KNOB_STREAM_HALF] != 0 && NL == 2 && G % 2 == 0 && ((long long)(G / 2) * LD * block_elem()) % 64 == 0;
+    }
     size_t stream_nz_bytes() const { return (size_t)((ny + 63) / 64 + 1) * 8; }      // the column mask behind the kernel's LDS sets
     int stream_split_setup() {
         if (!d_streamLive && !structured) { if (int rc = dalloc(&d_streamLive, (size_t)2 * d.nodes)) return rc; }
+        if (!d_streamUnits && !structured) { if (int rc = dalloc(&d_streamUnits, (size_t)2 * d.nodes)) return rc; }
         if (splitFirst >= 0) return RN_OK;
         splitFirst = d.nodes;
         const int mode = knob[RN_KNOB_STREAM_SPLIT] != 0;
@@ -1264,7 +1291,7 @@ struct Ctx : CtxBase {
         const size_t lds = stream_lds(G), nzb = stream_nz_bytes();
         RN_CHECK(lds + nzb <= 64 * 1024 || (lds + nzb <= 160 * 1024 && ensure_stream_lds()), RN_E_ARG, "k_stream_gemv: a span of operator columns does not fit the CU's LDS");
         const int node0 = h_stageCum[a.chainStage];   // first node of the chain region as this sweep sees it
-        const StreamSplit<T> sp{a.splitFirst, splitSpanHalf, d_my2, stream_skip() ? 1 : 0, d_streamLive};
+        const StreamSplit<T> sp{a.splitFirst, splitSpanHalf, d_my2, stream_skip() ? 1 : 0, d_streamLive, stream_half_on(G, NL) ? 1 : 0, d_streamUnits};
         const int grid = d.nodes + (d.nodes - a.splitFirst);      // two workgroups for every block of the split round
         lastStreamGrid = grid; lastStreamSplitFirst = a.splitFirst;
         const StreamRhs2<T> none{nullptr, nullptr, nullptr};
@@ -2511,6 +2538,37 @@ struct Ctx : CtxBase {
         if (ragged) *ragged = rg;
         return RN_OK;
     }
+    // the units records of the most recent launch summed (stream_walk_half: live units, those of ragged last spans among them, and the columns of those)
+    int stream_units_sum(long long *units, long long *ragUnits, long long *ragCols) {
+        RN_HIP(hipSetDevice(device));
+        RN_HIP(hipStreamSynchronize(stream));
+        std::vector<int> h((size_t)lastStreamGrid);
+        RN_HIP(hipMemcpy(h.data(), d_streamUnits, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+        long long u = 0, ru = 0, rc = 0;
+        for (int e : h) { u += e & 0xffff; ru += (e >> 16) & 0xf; rc += e >> 20; }
+        *units = u;
+        if (ragUnits) *ragUnits = ru;
+        if (ragCols) *ragCols = rc;
+        return RN_OK;
+    }
+    // {live units, units, columns per unit} of the most recent streaming launch: half-spans where the launch skipped them by themselves
+    // (stream_half_on), whole spans otherwise
+    int stream_units(long long *out) override {
+        RN_CHECK(out, RN_E_ARG, "rn_debug_stream_units: null output");
+        RN_CHECK(!structured && lastStreamGrid > 0 && d_streamLive && d_streamUnits, RN_E_STATE, "rn_debug_stream_units: no streaming launch yet");
+        int G, NL;
+        stream_shape(&G, &NL);
+        if (!stream_half_on()) {
+            long long live[4];
+            if (int rc = stream_live_sum(live, nullptr)) return rc;
+            out[0] = live[0]; out[1] = live[1]; out[2] = G;
+            return RN_OK;
+        }
+        long long lu = 0;
+        if (int rc = stream_units_sum(&lu, nullptr, nullptr)) return rc;
+        out[0] = lu; out[1] = (long long)d.nodes * ((ny + G / 2 - 1) / (G / 2)); out[2] = G / 2;
+        return RN_OK;
+    }
     int stream_live(long long *out) override {
         RN_CHECK(out, RN_E_ARG, "rn_debug_stream_live: null output");
         RN_CHECK(!structured && lastStreamGrid > 0 && d_streamLive, RN_E_STATE, "rn_debug_stream_live: no streaming launch yet");
@@ -3112,6 +3170,7 @@ int rn_debug_guard_poke(rn_ctx *ctx, int nbytes) { RN_GUARD(ctx); return ctx->im
 int rn_debug_set_knob(rn_ctx *ctx, int knob, int value) { RN_GUARD(ctx); return ctx->impl->set_knob(knob, value); }
 int rn_debug_stream_info(rn_ctx *ctx, int info[4]) { RN_GUARD(ctx); return ctx->impl->stream_info(info); }
 int rn_debug_stream_live(rn_ctx *ctx, long long out[4]) { RN_GUARD(ctx); return ctx->impl->stream_live(out); }
+int rn_debug_stream_units(rn_ctx *ctx, long long out[3]) { RN_GUARD(ctx); return ctx->impl->stream_units(out); }
 int rn_debug_restart_test(rn_ctx *ctx, double out[3]) { RN_GUARD(ctx); return ctx->impl->debug_restart_test(out); }
 int rn_debug_peer_seq(rn_ctx *ctx, unsigned int seq) { RN_GUARD(ctx); return ctx->impl->debug_peer_seq(seq); }
 int rn_guard_report(long out[2]) { if (!out) return RN_E_ARG; out[0] = rn::g_guardContexts.load(); out[1] = rn::g_guardBadBytes.load(); return RN_OK; }

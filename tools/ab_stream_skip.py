@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Same-process A/B of k_stream_gemv's skip of operator spans that meet no nonzero dual entry (RN_KNOB_STREAM_SKIP, csrc/k_stream.hpp):
 
-    knob 0: every span of every block is walked  |  knob 1 (default): only the live spans
+    knob 0: every span of every block is walked  |  knob 1: only the live spans, whole ones (the library's default also skips single
+    half-spans: tools/ab_stream_half.py)
 
 Contexts of one workload live side by side and are timed in ALTERNATING regions (rn_apg_reset, 20 iterations, then `--steps` timed ones; a region
 of one context, then of the next, ...; several rounds), so that whatever the box does in the meantime hits all alike: ms per iteration min /
