@@ -50,9 +50,38 @@ namespace rn {
 // walk of NL = 1, 3, 4.
 __device__ __forceinline__ bool stream_nz(double v) { return ((unsigned long long)__double_as_longlong(v) << 1) != 0ull; }
 __device__ __forceinline__ bool stream_nz(float v) { return (__float_as_uint(v) << 1) != 0u; }
+// The group schedule of both walks.  Each walk defines RN_GROUP (its group size: D spans, or DU units), RN_POP (the next live index of the chunk's mask into sv[d]),
+// RN_LOAD1 / RN_USE1 (request / consume what a thread owns of span or unit sv[d]) and the buffers bufA / bufB with their index sets sA / sB.  A chunk's nLive =
+// nGroups * RN_GROUP + nHead live ones: the live count mod the group size goes FIRST (they are met in increasing order either way), as a partial group (RN_LOADH /
+// RN_USEH: the first nHead, whole ones) in the second buffer, with the first full group requested right behind it: the chunk's last loads are then those of a full
+// group.  The steady state has no branch inside, so the compiler's vmcnt waits are exact: while group g is consumed, group g+1 (and then g+2) is in flight.
+#define RN_LOADG(buf, sv) _Pragma("unroll") for (int d = 0; d < RN_GROUP; d++) { RN_POP(sv, d) RN_LOAD1(buf, sv, d) }
+#define RN_USEG(buf, sv) _Pragma("unroll") for (int d = 0; d < RN_GROUP; d++) RN_USE1(buf, sv, d)
+#define RN_LOADH(buf, sv) _Pragma("unroll") for (int d = 0; d < RN_GROUP - 1; d++) if (d < nHead) { RN_POP(sv, d) RN_LOAD1(buf, sv, d) }
+#define RN_USEH(buf, sv) _Pragma("unroll") for (int d = 0; d < RN_GROUP - 1; d++) if (d < nHead) RN_USE1(buf, sv, d)
+#define RN_STREAM_GROUPS                                                                                               \
+    RN_LOADH(bufB, sB)                                                                                                 \
+    if (nGroups > 0) RN_LOADG(bufA, sA)                                                                                \
+    RN_USEH(bufB, sB)                                                                                                  \
+    if (nGroups > 0) {                                                                                                 \
+        int g = 0;                                                                                                     \
+        for (; g + 2 < nGroups; g += 2) {                                                                              \
+            RN_LOADG(bufB, sB)                                                                                         \
+            RN_USEG(bufA, sA)                                                                                          \
+            RN_LOADG(bufA, sA)                                                                                         \
+            RN_USEG(bufB, sB)                                                                                          \
+        }                                                                                                              \
+        if (g + 1 < nGroups) {                                                                                         \
+            RN_LOADG(bufB, sB)                                                                                         \
+            RN_USEG(bufA, sA)                                                                                          \
+            RN_USEG(bufB, sB)                                                                                          \
+        } else {                                                                                                       \
+            RN_USEG(bufA, sA)                                                                                          \
+        }                                                                                                              \
+    }
 template <typename T, typename VT, int VPL, int NL, int D, int NR>
 __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *sh_y, const T *sh_y2, const unsigned long long *sh_nz, int skip, int span0, int span1, int G, int ny,
-                                            int spanSlots, long long blockSlots, const int (&off)[NL], const int (&cj)[NL], const T (&msk)[NL], T (&part)[NL][VPL],
+                                            int spanSlots, const int (&off)[NL], const int (&cj)[NL], const T (&msk)[NL], T (&part)[NL][VPL],
                                             T (&part2)[NR == 2 ? NL : 1][VPL], int &liveSpans, int &liveCols, int &liveRagged) {
     const int lane = threadIdx.x & 63;
     const int rag = (ny % G != 0 && span1 * G > ny) ? ny / G : -1;      // the ragged last span, where this range holds it
@@ -66,42 +95,19 @@ __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *
 #pragma unroll
     for (int j = 0; j < NL; j++) offB[j] = (unsigned)off[j] * 16u;
 #define RN_POP(sv, d) { sv[d] = __builtin_amdgcn_readfirstlane(cb + __builtin_ctzll(mf)); mf &= mf - 1ull; }
-#define RN_LOADG(buf, sv)                                                                                              \
-    _Pragma("unroll") for (int d = 0; d < D; d++) {                                                                    \
-        RN_POP(sv, d)                                                                                                  \
-        _Pragma("unroll") for (int j = 0; j < NL; j++)                                                                 \
-            buf[d][j] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (size_t)sv[d] * spanBytes + offB[j])); \
+#define RN_GROUP D
+#define RN_LOAD1(buf, sv, d)                                                                                           \
+    _Pragma("unroll") for (int j = 0; j < NL; j++)                                                                     \
+        buf[d][j] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (size_t)sv[d] * spanBytes + offB[j]));
+#define RN_USE1(buf, sv, d)                                                                                            \
+    _Pragma("unroll") for (int j = 0; j < NL; j++) {                                                                   \
+        const T yc = sh_y[sv[d] * G + cj[j]] * msk[j];                                                                 \
+        _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] += (T)buf[d][j][e] * yc;                            \
+        if (NR == 2) {      /* (fp32 blocks under fp64 sums: the lane's values are converted once and meet both columns) */ \
+            const T yc2 = sh_y2[sv[d] * G + cj[j]] * msk[j];                                                           \
+            _Pragma("unroll") for (int e = 0; e < VPL; e++) part2[j][e] += (T)buf[d][j][e] * yc2;                      \
+        }                                                                                                              \
     }
-#define RN_USEG(buf, sv)                                                                                               \
-    _Pragma("unroll") for (int d = 0; d < D; d++)                                                                      \
-        _Pragma("unroll") for (int j = 0; j < NL; j++) {                                                               \
-            const T yc = sh_y[sv[d] * G + cj[j]] * msk[j];                                                             \
-            _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] += (T)buf[d][j][e] * yc;                        \
-            if (NR == 2) {      /* (fp32 blocks under fp64 sums: the lane's values are converted once and meet both columns) */ \
-                const T yc2 = sh_y2[sv[d] * G + cj[j]] * msk[j];                                                       \
-                _Pragma("unroll") for (int e = 0; e < VPL; e++) part2[j][e] += (T)buf[d][j][e] * yc2;                  \
-            }                                                                                                          \
-        }
-    // the partial group a chunk STARTS with: its first nHead (< D) live spans, whole ones
-#define RN_LOADH(buf, sv)                                                                                              \
-    _Pragma("unroll") for (int d = 0; d < D - 1; d++)                                                                  \
-        if (d < nHead) {                                                                                               \
-            RN_POP(sv, d)                                                                                              \
-            _Pragma("unroll") for (int j = 0; j < NL; j++)                                                             \
-                buf[d][j] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (size_t)sv[d] * spanBytes + offB[j])); \
-        }
-#define RN_USEH(buf, sv)                                                                                               \
-    _Pragma("unroll") for (int d = 0; d < D - 1; d++)                                                                  \
-        if (d < nHead) {                                                                                               \
-            _Pragma("unroll") for (int j = 0; j < NL; j++) {                                                           \
-                const T yc = sh_y[sv[d] * G + cj[j]] * msk[j];                                                         \
-                _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] += (T)buf[d][j][e] * yc;                    \
-                if (NR == 2) {                                                                                         \
-                    const T yc2 = sh_y2[sv[d] * G + cj[j]] * msk[j];                                                   \
-                    _Pragma("unroll") for (int e = 0; e < VPL; e++) part2[j][e] += (T)buf[d][j][e] * yc2;              \
-                }                                                                                                      \
-            }                                                                                                          \
-        }
     for (int cb = span0; cb < span1; cb += 64) {      // chunks of 64 spans: a group never crosses a chunk
         const int s = cb + lane;
         int cols = 0;
@@ -124,29 +130,7 @@ __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *
         const unsigned long long ragBit = (rag >= cb && rag < cb + 64) ? (m & (1ull << (rag - cb))) : 0ull;
         unsigned long long mf = m & ~ragBit;
         const int nLive = __popcll(mf), nGroups = nLive / D, nHead = nLive - nGroups * D;
-        // the live count mod D goes FIRST (the spans are met in increasing order either way), as a partial group in the second buffer, with the
-        // first full group requested right behind it: the chunk's last loads are then those of a full group
-        RN_LOADH(bufB, sB)
-        if (nGroups > 0) RN_LOADG(bufA, sA)
-        RN_USEH(bufB, sB)
-        if (nGroups > 0) {
-            int g = 0;
-            // steady state has no branch inside, so the compiler's vmcnt waits are exact: while group g is consumed, group
-            // g+1 (and then g+2) is in flight
-            for (; g + 2 < nGroups; g += 2) {
-                RN_LOADG(bufB, sB)
-                RN_USEG(bufA, sA)
-                RN_LOADG(bufA, sA)
-                RN_USEG(bufB, sB)
-            }
-            if (g + 1 < nGroups) {
-                RN_LOADG(bufB, sB)
-                RN_USEG(bufA, sA)
-                RN_USEG(bufB, sB)
-            } else {
-                RN_USEG(bufA, sA)
-            }
-        }
+        RN_STREAM_GROUPS
         if (ragBit) {      // the ragged last span (ny % G columns), where it is live: guarded, by itself, last
             liveRagged = 1;
             VT bufR[NL];
@@ -170,11 +154,10 @@ __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *
             }
         }
     }
+#undef RN_GROUP
 #undef RN_POP
-#undef RN_LOADG
-#undef RN_USEG
-#undef RN_LOADH
-#undef RN_USEH
+#undef RN_LOAD1
+#undef RN_USE1
 }
 // THE WALK OVER HALF-SPANS: what every NL = 2 instantiation runs (the kernels choose it with if constexpr; stream_walk above is NL = 1, 3, 4).
 // A thread's two slots of a span are two UNITS of the walk, unit u = 2 * span + h, ONE load per thread each.
@@ -207,6 +190,7 @@ __device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, cons
     const char *const Abb = reinterpret_cast<const char *>(Ab);
     const unsigned spanBytes = (unsigned)spanSlots * 16u;
     const unsigned offB[2] = {(unsigned)off[0] * 16u, (unsigned)off[1] * 16u};
+#define RN_GROUP DU
 #define RN_POP(sv, d) { sv[d] = __builtin_amdgcn_readfirstlane(ub + __builtin_ctzll(mf)); mf &= mf - 1ull; }
 #define RN_LOAD1(buf, sv, d) buf[d] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (size_t)(sv[d] >> 1) * spanBytes + ((sv[d] & 1) ? offB[1] : offB[0])));
 #define RN_USE1(buf, sv, d) {                                                                                          \
@@ -221,10 +205,6 @@ __device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, cons
             _Pragma("unroll") for (int e = 0; e < VPL; e++) { part2[0][e] += (T)buf[d][e] * ya2; part2[NR == 2 ? 1 : 0][e] += (T)buf[d][e] * yb2; } \
         }                                                                                                              \
     }
-#define RN_LOADG(buf, sv) _Pragma("unroll") for (int d = 0; d < DU; d++) { RN_POP(sv, d) RN_LOAD1(buf, sv, d) }
-#define RN_USEG(buf, sv) _Pragma("unroll") for (int d = 0; d < DU; d++) RN_USE1(buf, sv, d)
-#define RN_LOADH(buf, sv) _Pragma("unroll") for (int d = 0; d < DU - 1; d++) if (d < nHead) { RN_POP(sv, d) RN_LOAD1(buf, sv, d) }
-#define RN_USEH(buf, sv) _Pragma("unroll") for (int d = 0; d < DU - 1; d++) if (d < nHead) RN_USE1(buf, sv, d)
     for (int ub = u0; ub < u1; ub += 64) {      // chunks of 64 units (ub is even: a span's two units share a chunk); a group never crosses a chunk
         const int u = ub + lane;
         // the run of columns whose liveness is the unit's: its own half, or its span
@@ -244,25 +224,7 @@ __device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, cons
         const unsigned long long ragBits = (ragSh >= 0 && ragSh < 64) ? (m & (3ull << ragSh)) : 0ull;
         unsigned long long mf = m & ~ragBits;
         const int nLive = __popcll(mf), nGroups = nLive / DU, nHead = nLive - nGroups * DU;
-        RN_LOADH(bufB, sB)
-        if (nGroups > 0) RN_LOADG(bufA, sA)
-        RN_USEH(bufB, sB)
-        if (nGroups > 0) {
-            int g = 0;
-            for (; g + 2 < nGroups; g += 2) {      // steady state: no branch inside
-                RN_LOADG(bufB, sB)
-                RN_USEG(bufA, sA)
-                RN_LOADG(bufA, sA)
-                RN_USEG(bufB, sB)
-            }
-            if (g + 1 < nGroups) {
-                RN_LOADG(bufB, sB)
-                RN_USEG(bufA, sA)
-                RN_USEG(bufB, sB)
-            } else {
-                RN_USEG(bufA, sA)
-            }
-        }
+        RN_STREAM_GROUPS
         if (ragBits) {      // the ragged last span: its live units, each a guarded load, last (an idle slot or one behind the block reads the block's first slot against zero)
             liveRagged = 1;
 #pragma unroll
@@ -283,6 +245,7 @@ __device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, cons
                 }
         }
     }
+#undef RN_GROUP
 #undef RN_POP
 #undef RN_LOAD1
 #undef RN_USE1
@@ -290,6 +253,7 @@ __device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, cons
 #undef RN_USEG
 #undef RN_LOADH
 #undef RN_USEH
+#undef RN_STREAM_GROUPS
 }
 // Which slots of a span thread `tid` owns: off[j] (clamped to a slot of the span for idle threads), their columns cj[j] inside the span, msk[j] = 1
 // for an owned slot.  Slots tid, tid + 512, ...; NL = 2 with an even G: slot tid of each HALF of the span (stream_walk_half).
@@ -347,17 +311,39 @@ __device__ __forceinline__ void stream_record(int2 *live, int *units, int liveSp
 }
 template <typename T>
 struct StreamRhs2 { const T *w; T *my; T *qa; };
-template <typename T, int NL, bool SPLIT, int NR = 1>
+// Spans per group (D, stream_walk) and units per group (DU, stream_walk_half: NL = 2) of k_stream_gemv<T, NL, SPLIT, NR, ST>.  D0 is the measured depth; the
+// SPLIT instantiations with NL <= 2 walk groups one span shorter, which is what fits two workgroups per CU.  Two right-hand sides double the accumulators,
+// and a group is shortened where they would not fit the registers -- by a DIFFERENT rule for each storage (the order in which a thread meets its columns
+// does not depend on the depth: same sums, bit for bit).  Blocks in the context's own type, fp32 (4 values per slot x 2 accumulator sets): a group one span
+// shorter (NL = 4: one span per group), 150-172 VGPRs instead of 256 + 20-28 bytes of scratch per lane with the full depth; NL = 2 one UNIT fewer (169 VGPRs
+// with 8, one over what leaves three waves per SIMD as the span walk's 142 did); fp64 pairs keep the full depth.  fp32 blocks under fp64 sums: NL >= 3 runs
+// groups one span shorter (NL = 4: one span per group) to stay inside the registers; NL <= 2 keeps the full depth, two units per span.
+template <typename T, typename ST, int NL, bool SPLIT, int NR>
+struct StreamDepth {
+    static constexpr bool native = sizeof(ST) == sizeof(T);
+    static constexpr bool shortPair = NR == 2 && (native ? sizeof(T) == 4 : NL >= 3);
+    static constexpr int D0 = NL <= 2 ? (SPLIT ? RN_STREAM_D - 1 : RN_STREAM_D) : RN_STREAM_D_WIDE;
+    static constexpr int D = shortPair ? (NL == 4 ? 1 : D0 - 1) : D0;
+    static constexpr int DU = 2 * D - ((native && shortPair) ? 1 : 0);
+};
+// ST: the type the blocks are STORED in -- T, or float under T = double (rn_set_operator_storage(RN_STORE_F32)): half the bytes of the
+// only large thing in HBM, every sum still formed in fp64.  a.A points at floats then: a.LD is 2nv rounded up to four floats, a.strideA counts floats (whole
+// lines of 32), G and NL are the host's choice for 4-byte elements (Ctx::stream_shape) -- the block is walked exactly as the fp32 context walks its own
+// (slots of FOUR floats, same G, same column order).  Behind the load the lane converts its floats (exact, once for both right-hand sides) and accumulates in
+// double against the double sh_y; LDS sets, fold and outputs are T and go where ST = T puts them, so no consumer knows about the storage.  NR = 2 over fp32
+// storage is behind rn_set_sweep_pairing(RN_PAIR_ON) (Ctx::stream_pair_ok); not measured on an MI355X yet.
+// LDS: NR * (ny + G * LD) values of T (fp32 storage, NR = 2: up to the CU's 160 KB, Ctx::launch_stream).  HBM bytes per node, fp32 storage: LD*ny*4 + NR*(ny + 2nv + nx)*8.
+// Registers with fp32 storage (hipcc's resource report, SPLIT = false | true; NL = 2 with the walk over half-spans, the others with the walk over live spans): NL = 1:
+// 120 | 64 VGPRs, NL = 2: 211 | 125 (span walk: 184 | 156), NL = 3: 193 | 188, NL = 4: 255 | 248; no scratch (ST = T = float, NL = 2: 137 | 125, double: 123 | 125 -- span
+// walk 160 | 122 and 147 | 123).  NR = 2 (SPLIT = false): NL = 1: 138, NL = 2: 247 (span walk: 215), NL = 3: 210, NL = 4: 229 (groups of one span); no scratch, two waves
+// per SIMD from NL = 2 on.
+template <typename T, int NL, bool SPLIT, int NR = 1, typename ST = T>
 __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(SweepArgs<T> a, int G, int node0, StreamSplit<T> sp, StreamRhs2<T> r2) {
     static_assert(NR == 1 || !SPLIT, "two right-hand sides: unsplit launches only");
-    typedef typename Slot<T>::type VT;
-    // (two right-hand sides in fp32: 4 values per slot x 2 accumulator sets -- a group one span shorter (NL = 4: one span per group)
-    //  keeps the kernel inside its registers: 150-172 instead of 256 + 20-28 bytes of scratch per lane with the full depth.  The
-    //  order in which a thread meets its columns does not depend on the depth: same sums, bit for bit)
-    constexpr int VPL = Slot<T>::N, D0 = NL <= 2 ? (SPLIT ? RN_STREAM_D - 1 : RN_STREAM_D) : RN_STREAM_D_WIDE, D = (NR == 2 && sizeof(T) == 4) ? (NL == 4 ? 1 : D0 - 1) : D0;
-    // (NL = 2: units per group of the walk over half-spans -- the loads in flight of D spans; the fp32 pair one unit fewer: 169 VGPRs with 8, one
-    //  over what leaves three waves per SIMD as the span walk's 142 did)
-    constexpr int DU = 2 * D - ((NR == 2 && sizeof(T) == 4) ? 1 : 0);
+    static_assert(sizeof(ST) == sizeof(T) || (sizeof(T) == 8 && sizeof(ST) == 4), "blocks are stored in the context's type, or in fp32 under fp64");
+    typedef typename Slot<ST>::type VT;
+    typedef StreamDepth<T, ST, NL, SPLIT, NR> Depth;
+    constexpr int VPL = Slot<ST>::N, D = Depth::D, DU = Depth::DU;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T *sh_y = reinterpret_cast<T *>(smem_raw);          // ny (+ G of zero padding is not needed: guarded reads)
     T *sh_red = sh_y + ((a.ny + 3) & ~3);               // G * LD
@@ -370,8 +356,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
     const bool second = split && ((((int)blockIdx.x - sp.first) & 1) != 0);
     const int nx = a.nx, nv = a.nv, ny = a.ny, LD = a.LD;
     const int SPC = LD / VPL, spanSlots = G * SPC;
-    const long long blockSlots = (long long)ny * SPC;
-    const VT *__restrict__ Ab = reinterpret_cast<const VT *>(a.A + (size_t)node * a.strideA);
+    const VT *__restrict__ Ab = reinterpret_cast<const VT *>(reinterpret_cast<const ST *>(a.A) + (size_t)node * a.strideA);
     // this workgroup's spans: [span0, span1) of the block's ceil(ny / G)
     const int spansAll = (ny + G - 1) / G;
     const int span0 = SPLIT ? (second ? sp.spanHalf : 0) : 0, span1 = (split && !second) ? sp.spanHalf : spansAll;
@@ -414,7 +399,7 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
     }
     int liveSpans, liveCols, liveRagged, liveUnits;
     if constexpr (NL == 2) stream_walk_two<T, VT, VPL, DU, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, sp.half, span0, span1, G, ny, spanSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged, liveUnits);
-    else { stream_walk<T, VT, VPL, NL, D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, span0, span1, G, ny, spanSlots, blockSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged); liveUnits = 0; }
+    else { stream_walk<T, VT, VPL, NL, D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, span0, span1, G, ny, spanSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged); liveUnits = 0; }
 #pragma unroll
     for (int j = 0; j < NL; j++)
         if (msk[j] != (T)0) {
@@ -444,112 +429,6 @@ __global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv(
 }
 
 // ------------------------------------------------------------------------------------------------------
-// The same launch for an fp64 context whose blocks are STORED in fp32 (rn_set_operator_storage(RN_STORE_F32)):
-// half the bytes of the only large thing in HBM, every sum still formed in fp64.  a.A points at floats here: a.LD is 2nv rounded up
-// to four floats, a.strideA counts floats (whole lines of 32), G and NL are the host's choice for 4-byte elements (Ctx::stream_shape)
-// -- the block is walked exactly as the fp32 context walks its own: 16-byte slots of FOUR floats, every wave-load one contiguous
-// kilobyte, spans of whole 128-byte lines, non-temporal, double-buffered in groups of D spans.  What differs from k_stream_gemv<float>
-// is everything behind the load: the lane converts its four floats (exact) and accumulates part[NL][4] in double against the double
-// sh_y; the fold over the span's columns and the outputs my / my2 / qa are double and go where k_stream_gemv<double> puts them, so no
-// consumer knows about the storage.  The order in which a row meets its columns is that of the fp32 context's kernel (same G).
-// Prologue order, the skip of spans that meet no nonzero dual entry (stream_walk) and the branch-free steady state: as above, for the reasons given there.
-// NR = 2 (unsplit only): the quasi-Newton loops' two Hessian sweeps in one pass over the fp32 blocks, as k_stream_gemv NR = 2 does for native
-// blocks -- behind rn_set_sweep_pairing(RN_PAIR_ON) (Ctx::stream_pair_ok); not measured on an MI355X yet.  The second accelerated dual r2.w is
-// requested with the small loads in front of the first group and kept in a second LDS set (sh_y2 / sh_red2, doubles); the lane converts its
-// four floats once and accumulates part and part2 in double; r2.qa is stored at the end like a.qa; the epilogue folds both partial sets in one
-// walk into a.my and r2.my.  Each right-hand side's sums are formed exactly as the NR = 1, SPLIT = false kernel forms them (same column order,
-// same fold over k): bitwise the results of two unsplit launches.  NL >= 3 runs groups one span shorter (D = 2) to stay inside the registers;
-// the depth does not change the order in which a thread meets its columns.
-// LDS: NR * (ny + G * LD) doubles (NR = 2: up to the CU's 160 KB, Ctx::launch_stream).  HBM bytes per node: LD*ny*4 + NR*(ny + 2nv + nx)*8.
-// Registers (hipcc's resource report, SPLIT = false | true; NL = 2 with the walk over half-spans, the others with the walk over live spans): NL = 1: 120 | 64 VGPRs,
-// NL = 2: 211 | 125 (span walk: 184 | 156), NL = 3: 193 | 188, NL = 4: 255 | 248; no scratch (k_stream_gemv<float, 2, *>: 137 | 125, <double, 2, *>: 123 | 125 -- span walk
-// 160 | 122 and 147 | 123; the SPLIT instantiations with NL <= 2 walk groups of RN_STREAM_D - 1 spans = 8 units, which is what fits two workgroups per CU).  NR = 2
-// (SPLIT = false): NL = 1: 138, NL = 2: 247 (span walk: 215), NL = 3: 210, NL = 4: 229 (groups of one span); no scratch, two waves per SIMD from NL = 2 on.
-template <int NL, bool SPLIT, int NR = 1>
-__global__ void __launch_bounds__(STREAM_THREADS, RN_STREAM_MINW) k_stream_gemv_mixed(SweepArgs<double> a, int G, int node0, StreamSplit<double> sp, StreamRhs2<double> r2) {
-    static_assert(NR == 1 || !SPLIT, "two right-hand sides: unsplit launches only");
-    typedef double T;
-    typedef nat_f4 VT;
-    constexpr int VPL = 4, D0 = NL <= 2 ? (SPLIT ? RN_STREAM_D - 1 : RN_STREAM_D) : RN_STREAM_D_WIDE, D = (NR == 2 && NL >= 3) ? (NL == 4 ? 1 : D0 - 1) : D0;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    T *sh_y = reinterpret_cast<T *>(smem_raw);          // ny
-    T *sh_red = sh_y + ((a.ny + 3) & ~3);               // G * LD
-    T *sh_y2 = sh_red + (size_t)G * a.LD;               // NR = 2: the same pair again for the second right-hand side
-    T *sh_red2 = sh_y2 + ((a.ny + 3) & ~3);
-    const int tid = threadIdx.x;
-    const bool split = SPLIT && (int)blockIdx.x >= sp.first;
-    const int node = split ? sp.first + (((int)blockIdx.x - sp.first) >> 1) : (int)blockIdx.x;
-    const bool second = split && ((((int)blockIdx.x - sp.first) & 1) != 0);
-    const int nx = a.nx, nv = a.nv, ny = a.ny, LD = a.LD;
-    const int SPC = LD / VPL, spanSlots = G * SPC;
-    const long long blockSlots = (long long)ny * SPC;
-    const VT *__restrict__ Ab = reinterpret_cast<const VT *>(reinterpret_cast<const float *>(a.A) + (size_t)node * a.strideA);
-    const int spansAll = (ny + G - 1) / G;
-    const int span0 = SPLIT ? (second ? sp.spanHalf : 0) : 0, span1 = (split && !second) ? sp.spanHalf : spansAll;
-    int off[NL], cj[NL];
-    T msk[NL];
-    stream_slots<T, NL>(tid, G, SPC, spanSlots, off, cj, msk);
-    T part[NL][VPL], part2[NR == 2 ? NL : 1][VPL];
-#pragma unroll
-    for (int j = 0; j < NL; j++)
-#pragma unroll
-        for (int e = 0; e < VPL; e++) { part[j][e] = 0; if (NR == 2) part2[j][e] = 0; }
-    const bool has0 = tid < ny;
-    const size_t i0 = (size_t)node * ny + (has0 ? tid : 0);
-    const int stage = node >= node0 ? a.chainStage + (node - node0) / a.K : a.tr.stageOf[node];
-    const T *dyRow = a.tr.dy + (size_t)stage * ny;
-    const T spn = a.tr.sqrtp[node];
-    const int tq = tid < nx ? tid : 0;
-    const T dq0 = dyRow[tq], dq1 = dyRow[nx + tq];    // for a_i below
-    const T w0a = a.w[i0];      // the y column: the accelerated dual the sweep is evaluated at
-    T w20 = 0;
-    if (NR == 2) w20 = r2.w[i0];      // the second right-hand side: with the small loads, in front of the first group
-    // a_i is STORED AT THE END of the kernel: stores count in the same in-order counter as the loads, so a store issued
-    // here has to be acknowledged before the wave may consume any group of A_i requested after it
-    T qa0 = 0, qa02 = 0;
-    unsigned long long *sh_nz = reinterpret_cast<unsigned long long *>(sh_y + (size_t)NR * (((ny + 3) & ~3) + (size_t)G * LD));   // (ny + 63) / 64 + 1 words
-    stream_stage_w<T, NR>(a.w + (size_t)node * ny, NR == 2 ? r2.w + (size_t)node * ny : nullptr, w0a, w20, sh_y, sh_y2, sh_nz, ny);
-    __syncthreads();
-    // a_i = F_i' xi_i = sqrt(p_i) (d_x o xi_box + d_xs o xi_safe)      (a split block: written by its first half)
-    if (tid < nx) qa0 = stream_qa_elem(spn, dq0, sh_y[tid], dq1, sh_y[nx + tid]);
-    if (!second) for (int t = tid + STREAM_THREADS; t < nx; t += STREAM_THREADS)
-        a.qa[(size_t)node * nx + t] = stream_qa_elem(spn, dyRow[t], sh_y[t], dyRow[nx + t], sh_y[nx + t]);
-    if (NR == 2) {
-        if (tid < nx) qa02 = stream_qa_elem(spn, dq0, sh_y2[tid], dq1, sh_y2[nx + tid]);
-        for (int t = tid + STREAM_THREADS; t < nx; t += STREAM_THREADS)
-            r2.qa[(size_t)node * nx + t] = stream_qa_elem(spn, dyRow[t], sh_y2[t], dyRow[nx + t], sh_y2[nx + t]);
-    }
-    int liveSpans, liveCols, liveRagged, liveUnits;
-    if constexpr (NL == 2) stream_walk_two<T, VT, VPL, 2 * D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, sp.half, span0, span1, G, ny, spanSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged, liveUnits);
-    else { stream_walk<T, VT, VPL, NL, D, NR>(Ab, sh_y, sh_y2, sh_nz, sp.skip, span0, span1, G, ny, spanSlots, blockSlots, off, cj, msk, part, part2, liveSpans, liveCols, liveRagged); liveUnits = 0; }
-#pragma unroll
-    for (int j = 0; j < NL; j++)
-        if (msk[j] != (T)0) {
-#pragma unroll
-            for (int e = 0; e < VPL; e++) { sh_red[(size_t)off[j] * VPL + e] = part[j][e]; if (NR == 2) sh_red2[(size_t)off[j] * VPL + e] = part2[j][e]; }
-        }
-    if (tid < nx && !second) stream_out(qa0, a.qa + (size_t)node * nx + tid);
-    if (NR == 2 && tid < nx) stream_out(qa02, r2.qa + (size_t)node * nx + tid);
-    stream_record<NL == 2>(sp.live, sp.units, liveSpans, liveCols, liveRagged, liveUnits);
-    __syncthreads();
-    T *const myOut = second ? sp.my2 + (size_t)(node - sp.first) * 2 * nv : a.my + (size_t)node * 2 * nv;
-    if (NR == 2) {      // both right-hand sides' partials folded in one walk, each in the order of the one-vector kernel
-        T *const myOut2 = r2.my + (size_t)node * 2 * nv;
-        for (int r = tid; r < 2 * nv; r += STREAM_THREADS) {
-            T s = sh_red[r], s2 = sh_red2[r];
-            for (int k = 1; k < G; k++) { s += sh_red[(size_t)k * LD + r]; s2 += sh_red2[(size_t)k * LD + r]; }
-            stream_out(s, myOut + r);
-            stream_out(s2, myOut2 + r);
-        }
-        return;
-    }
-    for (int r = tid; r < 2 * nv; r += STREAM_THREADS) {    // slot q of a span = column q / SPC, rows (q % SPC) * VPL ...
-        T s = sh_red[r];
-        for (int k = 1; k < G; k++) s += sh_red[(size_t)k * LD + r];
-        stream_out(s, myOut + r);
-    }
-}
-
 // Structured operator mode ("shared-operator model"): every per-node block of the factor step
 // is (shared matrix) x (stage diagonal) x (power of p_i)  --  D_i = Bbt F_i', Ftil_i = L' G_i', Phi_i = -Omega_i D_i / 2,
 // Psi_i = -Omega_i Ftil_i / 2 (Engine.cu:721-745) with F_i, G_i diagonal (Utilities.cu:33-58).  Hence

@@ -379,7 +379,7 @@ struct Ctx : CtxBase {
     // of p_i, Engine.cu:721-745 -- and becomes dense the moment a caller hands in a block of its own (rn_set_operator: materialise_dense)
     int opsMode = RN_OPS_AUTO, structured = 1, warmStart = 0;
     // Element type of the dense blocks (rn_set_operator_storage).  RN_STORE_F32 on an fp64 context: the blocks live in d_A32 as floats -- LD,
-    // strideA and the streaming kernel's span follow the 4-byte element -- and k_stream_gemv_mixed accumulates them in fp64; every other buffer
+    // strideA and the streaming kernel's span follow the 4-byte element -- and k_stream_gemv<double, ..., float> accumulates them in fp64; every other buffer
     // and every other kernel is the fp64 context's.  On an fp32 context the request changes nothing (its blocks are floats already).
     int storeReq = RN_STORE_NATIVE;
     float *d_A32 = nullptr;
@@ -1268,22 +1268,38 @@ struct Ctx : CtxBase {
         splitSpanHalf = (groups + 1) / 2 * D;       // whole groups; the first half gets the odd one (the second also walks the ragged last span)
         return RN_OK;
     }
-    bool ensure_stream_lds() {   // > 64 KB of dynamic LDS needs the function attribute (once)
+    // The instantiations of k_stream_gemv: the blocks' storage type, SPLIT, NR and NL are each chosen HERE and nowhere else (all kernels of one T
+    // share a signature).  Two right-hand sides run the unsplit kernel; one runs the SPLIT one where two workgroups share a CU.
+    typedef void (*StreamKernel)(SweepArgs<T>, int, int, StreamSplit<T>, StreamRhs2<T>);
+    template <typename ST, bool SPLIT, int NR>
+    static StreamKernel stream_kernel_nl(int NL) {
+        switch (NL) {
+            case 1: return k_stream_gemv<T, 1, SPLIT, NR, ST>;
+            case 2: return k_stream_gemv<T, 2, SPLIT, NR, ST>;
+            case 3: return k_stream_gemv<T, 3, SPLIT, NR, ST>;
+            default: return k_stream_gemv<T, 4, SPLIT, NR, ST>;
+        }
+    }
+    template <typename ST>
+    static StreamKernel stream_kernel_of(bool twoPerCU, bool pair, int NL) {
+        return pair ? stream_kernel_nl<ST, false, 2>(NL) : twoPerCU ? stream_kernel_nl<ST, true, 1>(NL) : stream_kernel_nl<ST, false, 1>(NL);
+    }
+    static StreamKernel stream_kernel(bool stored32, bool twoPerCU, bool pair, int NL) {
+        if constexpr (sizeof(T) == 8) { if (stored32) return stream_kernel_of<float>(twoPerCU, pair, NL); }
+        return stream_kernel_of<T>(twoPerCU, pair, NL);
+    }
+    bool ensure_stream_lds() {   // > 64 KB of dynamic LDS needs the function attribute (once): every kernel the selector can return
         static const bool ok = [] {
             bool all = true;
-            for (const void *fn : {(const void *)k_stream_gemv<T, 1, false>, (const void *)k_stream_gemv<T, 2, false>, (const void *)k_stream_gemv<T, 3, false>, (const void *)k_stream_gemv<T, 4, false>,
-                                   (const void *)k_stream_gemv<T, 1, true>, (const void *)k_stream_gemv<T, 2, true>, (const void *)k_stream_gemv<T, 3, true>, (const void *)k_stream_gemv<T, 4, true>})
-                all = all && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-            if constexpr (sizeof(T) == 8)
-                for (const void *fn : {(const void *)k_stream_gemv_mixed<1, false>, (const void *)k_stream_gemv_mixed<2, false>, (const void *)k_stream_gemv_mixed<3, false>, (const void *)k_stream_gemv_mixed<4, false>,
-                                       (const void *)k_stream_gemv_mixed<1, true>, (const void *)k_stream_gemv_mixed<2, true>, (const void *)k_stream_gemv_mixed<3, true>, (const void *)k_stream_gemv_mixed<4, true>,
-                                       (const void *)k_stream_gemv_mixed<1, false, 2>, (const void *)k_stream_gemv_mixed<2, false, 2>, (const void *)k_stream_gemv_mixed<3, false, 2>, (const void *)k_stream_gemv_mixed<4, false, 2>})
-                    all = all && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
+            for (int stored32 = 0; stored32 < (sizeof(T) == 8 ? 2 : 1); stored32++)
+                for (int form = 0; form < 3; form++)
+                    for (int NL = 1; NL <= STREAM_NLMAX; NL++)
+                        all = all && hipFuncSetAttribute((const void *)stream_kernel(stored32 != 0, form == 1, form == 2, NL), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
             return all;
         }();
         return ok;
     }
-    // second != nullptr: two right-hand sides in one pass (k_stream_gemv / k_stream_gemv_mixed NR = 2; see stream_pair_ok)
+    // second != nullptr: two right-hand sides in one pass (k_stream_gemv NR = 2; see stream_pair_ok)
     int launch_stream(const SweepArgs<T> &a, const StreamRhs2<T> *second = nullptr) {
         int G, NL;
         stream_shape(&G, &NL);
@@ -1294,68 +1310,23 @@ struct Ctx : CtxBase {
         const StreamSplit<T> sp{a.splitFirst, splitSpanHalf, d_my2, stream_skip() ? 1 : 0, d_streamLive, stream_half_on(G, NL) ? 1 : 0, d_streamUnits};
         const int grid = d.nodes + (d.nodes - a.splitFirst);      // two workgroups for every block of the split round
         lastStreamGrid = grid; lastStreamSplitFirst = a.splitFirst;
-        const StreamRhs2<T> none{nullptr, nullptr, nullptr};
-        if constexpr (sizeof(T) == 8) {
-            if (store32()) {   // fp32 blocks under fp64 iterates (k_stream_gemv_mixed): one right-hand side, split or not, or two, unsplit
-                if (second) {
-                    // (both sets are doubles over a span chosen for 4-byte entries: twice the native pair's LDS for the same operator width, so
-                    //  past 64 KB the launch takes the function attribute like the one-vector launch does)
-                    RN_CHECK(a.splitFirst >= d.nodes, RN_E_STATE, "k_stream_gemv_mixed with two right-hand sides: unsplit launches only");
-                    RN_CHECK(2 * lds + nzb <= 64 * 1024 || (2 * lds + nzb <= 160 * 1024 && ensure_stream_lds()), RN_E_ARG, "k_stream_gemv_mixed with two right-hand sides: the two LDS sets do not fit the CU's LDS");
-                    switch (NL) {
-                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
-                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
-                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
-                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
-                    }
-                } else if (streamTwoPerCU) {
-                    switch (NL) {
-                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                    }
-                } else {
-                    switch (NL) {
-                        case 1: hipLaunchKernelGGL((k_stream_gemv_mixed<1, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                        case 2: hipLaunchKernelGGL((k_stream_gemv_mixed<2, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                        case 3: hipLaunchKernelGGL((k_stream_gemv_mixed<3, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                        default: hipLaunchKernelGGL((k_stream_gemv_mixed<4, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                    }
-                }
-                return RN_OK;
-            }
-        }
-        if (second) {
+        if (second && store32()) {
+            // (both sets are doubles over a span chosen for 4-byte entries: twice the native pair's LDS for the same operator width, so
+            //  past 64 KB the launch takes the function attribute like the one-vector launch does)
+            RN_CHECK(a.splitFirst >= d.nodes, RN_E_STATE, "k_stream_gemv over fp32 storage with two right-hand sides: unsplit launches only");
+            RN_CHECK(2 * lds + nzb <= 64 * 1024 || (2 * lds + nzb <= 160 * 1024 && ensure_stream_lds()), RN_E_ARG, "k_stream_gemv over fp32 storage with two right-hand sides: the two LDS sets do not fit the CU's LDS");
+        } else if (second) {
             RN_CHECK(a.splitFirst >= d.nodes && 2 * lds + nzb <= 64 * 1024, RN_E_STATE, "k_stream_gemv with two right-hand sides: unsplit launches only");
-            switch (NL) {
-                case 1: hipLaunchKernelGGL((k_stream_gemv<T, 1, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
-                case 2: hipLaunchKernelGGL((k_stream_gemv<T, 2, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
-                case 3: hipLaunchKernelGGL((k_stream_gemv<T, 3, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
-                default: hipLaunchKernelGGL((k_stream_gemv<T, 4, false, 2>), dim3(grid), dim3(STREAM_THREADS), 2 * lds + nzb, stream, a, G, node0, sp, *second); break;
-            }
-        } else if (streamTwoPerCU) {
-            switch (NL) {
-                case 1: hipLaunchKernelGGL((k_stream_gemv<T, 1, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                case 2: hipLaunchKernelGGL((k_stream_gemv<T, 2, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                case 3: hipLaunchKernelGGL((k_stream_gemv<T, 3, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                default: hipLaunchKernelGGL((k_stream_gemv<T, 4, true>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-            }
-        } else {
-            switch (NL) {
-                case 1: hipLaunchKernelGGL((k_stream_gemv<T, 1, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                case 2: hipLaunchKernelGGL((k_stream_gemv<T, 2, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                case 3: hipLaunchKernelGGL((k_stream_gemv<T, 3, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-                default: hipLaunchKernelGGL((k_stream_gemv<T, 4, false>), dim3(grid), dim3(STREAM_THREADS), lds + nzb, stream, a, G, node0, sp, none); break;
-            }
         }
+        hipLaunchKernelGGL(stream_kernel(store32(), streamTwoPerCU, second != nullptr, NL), dim3(grid), dim3(STREAM_THREADS), (second ? 2 : 1) * lds + nzb, stream,
+                           a, G, node0, sp, second ? *second : StreamRhs2<T>{nullptr, nullptr, nullptr});
         return RN_OK;
     }
     // rn_set_sweep_pairing: RN_PAIR_AUTO (default), RN_PAIR_ON (AUTO plus fp32-stored blocks), RN_PAIR_OFF (never)
     int pairReq = RN_PAIR_AUTO;
     // two right-hand sides in one streaming pass are possible for dense per-node blocks, and
     //   blocks in the context's own type (k_stream_gemv NR = 2): both LDS sets in 64 KB, no split last round;
-    //   fp32-stored blocks (k_stream_gemv_mixed NR = 2; bitwise the two sweeps, its gain not measured yet): behind RN_PAIR_ON only, a split
+    //   fp32-stored blocks (k_stream_gemv with ST = float, NR = 2; bitwise the two sweeps, its gain not measured yet): behind RN_PAIR_ON only, a split
     //   last round included -- the pair sweep then runs unsplit (launch_sweep), the context's other sweeps keep their split.  Its LDS sets
     //   are doubles over a span chosen for 4-byte entries (twice the columns): twice the native pair's bytes at the same operator width, so
     //   they may take the CU's whole 160 KB (ensure_stream_lds, at the launch) -- at 64 KB nv = 32 with ny = 80 would already not pair

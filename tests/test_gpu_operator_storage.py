@@ -1,4 +1,4 @@
-"""Dense operator blocks stored in fp32 under fp64 iterates (rn_set_operator_storage(RN_STORE_F32), k_stream_gemv_mixed).
+"""Dense operator blocks stored in fp32 under fp64 iterates (rn_set_operator_storage(RN_STORE_F32), k_stream_gemv<double, ..., float>).
 
 The contract: an fp64 context with fp32 block storage computes the fp64 solution of the problem WITH THE ROUNDED BLOCKS.  So the
 reference of the parity tests is the fp64 oracle holding the context's own blocks: every per-node block (Phi, Psi, D, Ftil) is read

@@ -1,4 +1,4 @@
-"""NAMA's two Hessian sweeps in ONE pass over fp32-stored operator blocks (rn_set_sweep_pairing(RN_PAIR_ON), k_stream_gemv_mixed with two
+"""NAMA's two Hessian sweeps in ONE pass over fp32-stored operator blocks (rn_set_sweep_pairing(RN_PAIR_ON), k_stream_gemv over fp32 storage with two
 right-hand sides; the oracles are SmpcController.cu:1331 and :1341-1345).
 
 The contract: the pair is bitwise the two sweeps run one after the other (each right-hand side's sums are formed as the unsplit one-vector

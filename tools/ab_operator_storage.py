@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Same-process A/B of the dense operator storage on the headline tree (barcelona493) and on rank 0's 1/8 shard of it:
 
-    fp64 native  |  fp64 iterates on fp32 blocks (rn_set_operator_storage, k_stream_gemv_mixed)  |  fp32 context
+    fp64 native  |  fp64 iterates on fp32 blocks (rn_set_operator_storage, k_stream_gemv<double, ..., float>)  |  fp32 context
 
 The three contexts live side by side and are timed in ALTERNATING regions of rn_apg_iterate (a region of one, then of the next, ...;
 several rounds), so that whatever the box does in the meantime hits all three alike; medians per context.  Then, with rn_profile_enable,
@@ -12,7 +12,7 @@ forced to 0 and to 1 (which instantiation its launches take).
     python3 tools/ab_operator_storage.py [--steps 200] [--rounds 5] [--workload barcelona493] [--no-shard] > profiles/ab_operator_storage.txt
 
 The NAMA leg (--nama, or --nama-only without the APG part): ms per NAMA iteration on the whole tree with fp32-stored blocks, the two Hessian
-sweeps one after the other (rn_set_sweep_pairing(RN_PAIR_OFF)) and in one pass (RN_PAIR_ON, k_stream_gemv_mixed with two right-hand sides),
+sweeps one after the other (rn_set_sweep_pairing(RN_PAIR_OFF)) and in one pass (RN_PAIR_ON, k_stream_gemv over fp32 storage with two right-hand sides),
 the native fp64 context's paired figure beside them, rn_fbe_counters of each; alternating regions of rn_algorithm_fbe_nama, medians and the
 run-to-run spread (min, max over the regions).  --append FILE adds the leg's lines to FILE.  On a checkout from before rn_set_sweep_pairing
 the leg runs what exists there: the sequential fp32-storage figure and the native paired one (the comparison that counts is that checkout's

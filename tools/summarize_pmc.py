@@ -26,9 +26,9 @@ for k in sorted(set(fetch) | set(write)):
               "launches": len(fetch.get(k, write.get(k, [])))}
 
 
-def total(prefix):
+def total(prefix, without=None):
     for k, v in raw.items():
-        if k.startswith(prefix) and v["FETCH_SIZE_KiB_median"] is not None and v["launches"] >= 4:
+        if k.startswith(prefix) and not (without and without in k) and v["FETCH_SIZE_KiB_median"] is not None and v["launches"] >= 4:
             return 1024.0 * (2.0 * v["FETCH_SIZE_KiB_median"] + (v["WRITE_SIZE_KiB_median"] or 0.0))
     return None
 
@@ -45,6 +45,6 @@ print(json.dumps({
     "source": "rocprofv3 --kernel-trace --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/collect_traffic.sh), bench.py --steps 20 --dense-only, "
               "barcelona493 fp64, medians per launch",
     "correction": "FETCH_SIZE doubled (gfx950 counts 64 B per 128-B request on wide streaming reads: MI355X_MICROARCH.md, HBM); WRITE_SIZE as is; KiB*1024",
-    "k_stream_gemv_bytes_per_launch": total("void rn::k_stream_gemv<double"),
+    "k_stream_gemv_bytes_per_launch": total("void rn::k_stream_gemv<double", without=", float>("),      # (blocks in the context's own type, as always)
     "k_dual_stage_bytes_per_launch": total("void rn::k_dual_stage<double, false"),
     "raw": raw}, indent=1))
