@@ -47,7 +47,7 @@ UNITS = {
     "k_misc": ["common.hpp", "k_misc.hpp", "k_plan.hpp"],
     "k_fbe": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "fbe_kernels.hpp"],
     "rapidnet_capi": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "k_stream.hpp", "stream_bits.hpp", "k_misc.hpp", "k_plan.hpp", "kernels.hpp", "fbe_kernels.hpp", "fbe_methods.inc",
-                      "caller_data.inc", "plan_report.inc", "partition.hpp", "bounds.hpp"],
+                      "sweep.inc", "caller_data.inc", "plan_report.inc", "partition.hpp", "bounds.hpp"],
 }
 OBJ_DIR = os.path.join(HERE, "build")
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]

@@ -348,12 +348,11 @@
             hipLaunchKernelGGL(k_value_mfma<T>, dim3(vmBlocks()), dim3(64 * VM_WAVES), (size_t)16 * SBw * sizeof(T), stream, (const T *)d_u, (const T *)d_udir, (const T *)d_prevU,
                                (const int *)d_parent, (const T *)d_prob, (const T *)d_Wp, pad16(d.nu), pad4(d.nu), (const T *)d_alpha, d.nu, d.nodes, LsTaus<T>{}, 1, d_valPartials,
                                DOT_MAX, 0, value_first_node(), SBw);
-            hipLaunchKernelGGL(k_dots_finish<>, dim3(1), dim3(ELT_THREADS), 0, stream, d_valPartials, vmBlocks(), 2, d_scal + 8);
         } else {
             hipLaunchKernelGGL(k_value_terms<T>, dim3(valueBlocks), dim3(VALUE_THREADS), (size_t)VALUE_TILE * d.nu * sizeof(T), stream, d_u, d_prevU, d_parent,
                                d_prob, d_W, d_alpha, d.nu, d.nodes, d_valPartials, value_first_node());
-            hipLaunchKernelGGL(k_dots_finish<>, dim3(1), dim3(ELT_THREADS), 0, stream, d_valPartials, valueBlocks, 2, d_scal + 8);
         }
+        hipLaunchKernelGGL(k_dots_finish<>, dim3(1), dim3(ELT_THREADS), 0, stream, d_valPartials, valueMfma ? vmBlocks() : valueBlocks, 2, d_scal + 8);
         RN_HIP(hipGetLastError());
         return RN_OK;
     }
@@ -533,28 +532,31 @@
         return RN_OK;
     }
     // SmpcController::computeLineSearchAmeLbfgsUpdate (:1311-1414)
+    // the two element-wise launches of the AME line search's opening (SmpcController.cu:1332-1340), in the order its sweeps allow (line_search_ame):
+    // w += lambda res, x += lambda xdir, u += lambda udir, Hx += lambda HxDir with the directions of the sweep on the residual ...
+    void launch_ame_trial_step(const T *xdir, const T *udir, const T *hxDir) {
+        TrialArgs<T> g{d_x, d_u, p_acc_view, d_hx, xdir, udir, d_res, hxDir, (long long)d.nodes * d.nx, (long long)d.nodes * d.nu, ntot(), (T)stepSize};
+        hipLaunchKernelGGL(k_trial_step<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, g);
+    }
+    // ... and the direction's correction dir -= lambda res
+    void launch_ame_correction() { hipLaunchKernelGGL(k_axpby<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, d_dir, d_dir, d_res, (T)1, (T)-stepSize, ntot()); }
     int line_search_ame(double valueY, double *tauOut) override {
         RN_CHECK(tauOut, RN_E_ARG, "rn_line_search_ame_lbfgs_update: null output");
         RN_FBE_READY("rn_line_search_ame_lbfgs_update")
         T tau = 1;
-        const long long n = ntot();
         if (int rc = launch_dots({{d_res, d_dir}})) return rc;                                 // valueDirection = -<res, dir>, read with the search's first batch
         if (pair_active()) {
             // the reference's two Hessian oracles (:1331 on the residual, :1341-1345 on the corrected direction) do not feed each other:
             // the direction's correction (:1338-1340) only needs the residual.  So the correction comes first and both sweeps share one
             // pass over the operator blocks -- a third of the iteration's HBM traffic; same values as the sequence below.
-            hipLaunchKernelGGL(k_axpby<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, d_dir, d_dir, d_res, (T)1, (T)-stepSize, n);   // :1338-1340
-            if (int rc = launch_sweep(nullptr, 0, d_res, true, d_dir)) return rc;                       // :1331 and :1341-1345
-            TrialArgs<T> g{d_x, d_u, p_acc_view, d_hx, d_xdirB, d_udirB, d_res, d_hxDirB, (long long)d.nodes * d.nx, (long long)d.nodes * d.nu, n, (T)stepSize};
-            hipLaunchKernelGGL(k_trial_step<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, g);                                      // :1332-1337
+            launch_ame_correction();                                                               // :1338-1340
+            if (int rc = launch_sweep(nullptr, 0, d_res, true, d_dir)) return rc;                  // :1331 and :1341-1345
+            launch_ame_trial_step(d_xdirB, d_udirB, d_hxDirB);                                     // :1332-1337
             sweepPairs++;
         } else {
             if (int rc = hessian_sweep(d_res)) return rc;                                          // :1331
-            {   // w += lambda res, x += lambda xdir, u += lambda udir, Hx += lambda HxDir             (:1332-1337)
-                TrialArgs<T> g{d_x, d_u, p_acc_view, d_hx, d_xdir, d_udir, d_res, d_hxDir, (long long)d.nodes * d.nx, (long long)d.nodes * d.nu, n, (T)stepSize};
-                hipLaunchKernelGGL(k_trial_step<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, g);
-            }
-            hipLaunchKernelGGL(k_axpby<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, d_dir, d_dir, d_res, (T)1, (T)-stepSize, n);   // :1338-1340
+            launch_ame_trial_step(d_xdir, d_udir, d_hxDir);                                        // :1332-1337
+            launch_ame_correction();                                                               // :1338-1340
             if (int rc = hessian_sweep(d_dir)) return rc;                                          // :1341-1345
         }
         if (int rc = line_search_loop(valueY, &tau, -1)) return rc;

@@ -34,6 +34,10 @@ CONFIGS = {
     "horizon1": (16, 3, 6, 4, 2, 1, []),
     "horizon2": (17, 3, 6, 4, 2, 2, [3]),
     "fan": (18, 4, 8, 6, 3, 4, [70]),
+    # crowns DEEPER than the forward walk folds (CROWN_MAX_DEPTH = 8 stages: the chains start at stage 9): 9 crown nodes (one crown launch per
+    # direction) and 255 of them (a crown launch per stage)
+    "deepchain": (27, 3, 6, 4, 2, 12, [1, 1, 1, 1, 1, 1, 1, 1, 2]),
+    "deepcrown": (28, 3, 6, 4, 2, 11, [2, 2, 2, 2, 2, 2, 1, 1, 2]),
     # many inputs, few tanks: 2 nv = 580 rows per operator column (several 16-byte slots per thread in k_stream_gemv) and
     # shared-operator products too large for the LDS slab kernels (tile-kernel fallback)
     "tall": (19, 8, 300, 40, 10, 3, [2]),

@@ -5,6 +5,8 @@
       run in a process of its own because the ranks' streams must sit on different hardware queues (a crown kernel that
       waits for a peer's packets must not block that peer's kernels behind it in the same queue): GPU_MAX_HW_QUEUES is set
       by the parent.  Compared with the stand-in transport (bitwise) and with the CPU oracle.
+  split
+      the same on the two-rank tree of tests/test_gpu_stream_split.py whose shards have a split last round and the merged chain + cut launch
   ipc <problem> <cut>
       one rank of a 2-process run under torch.distributed.run on one GPU: the inboxes travel as hipIpcMemHandle_t over
       gloo (the path `bench.py --gpus N` takes on a multi-GPU node); the per-batch collectives go through an all-reduce
@@ -32,10 +34,12 @@ def relmax(a, b):
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
 
 
-def inprocess(name, world, cut, structured, precision, kw):
-    p = synth.make_problem(name, **kw)
+def inprocess(name, world, cut, structured, precision, kw, problem=None, alias=True, check=None):
+    """problem: a problem of the caller's own instead of the named one (alias: whether its oracle may alias the operators); check(shards): the
+    caller's assertions on the shard contexts behind each transport's run"""
+    p = problem or synth.make_problem(name, **kw)
     dh, ah = synth.forecast_at(p["forecast"], 0)
-    o = Oracle(p["network"], p["tree"], p["config"], precision=precision)
+    o = Oracle(p["network"], p["tree"], p["config"], precision=precision, alias_operators=alias)
     o.initialise(dh, ah)
     ohist = o.apg(44)
     tol = 1e-9 if precision == "f64" else 2e-4
@@ -73,6 +77,8 @@ def inprocess(name, world, cut, structured, precision, kw):
         for t in ts:
             t.join()
         assert not errs, errs
+        if check:
+            check(shards)
         d = {"nx": shards[0].nx, "nu": shards[0].nu, "nv": shards[0].nv, "2nx": 2 * shards[0].nx}
         nodes = shards[0].full_nodes
         got = {nm: partition.scatter_to_global([s.get(bid) for s in shards], [s.global_nodes for s in shards], nodes, d[dm]) for bid, nm, dm in VECS}
@@ -90,6 +96,15 @@ def inprocess(name, world, cut, structured, precision, kw):
     assert all(np.array_equal(a, b) for a, b in zip(results[0][1], results[1][1]))
     assert results[0][2] == results[1][2], (results[0][2], results[1][2])
     print("oneshot inprocess ok: %s world %d cut %d structured %d %s, batches %s" % (name, world, cut, structured, precision, results[1][2][0]), flush=True)
+
+
+def split_case():
+    """the two-rank tree of tests/test_gpu_stream_split.py::test_sharded_up_walk_adds_the_second_partial: every shard's streaming launch has a split
+    last round and its chain walks are merged with the cut parents' sums -- with the one-shot transport that launch is k_up_chain_cut<T, SPLIT, GATHER>"""
+    import test_gpu_stream_split as spl
+
+    p, fc, cut, expect = spl.sharded_split_problem()
+    inprocess("b240 on the split two-rank tree", 2, cut, False, "f64", {}, problem=p, alias=spl.aliasing(p), check=expect)
 
 
 def auto_case(name, world, cut):
@@ -343,6 +358,8 @@ if __name__ == "__main__":
     if mode == "inprocess":
         kw = {"penalty_x": 20.0, "penalty_xs": 5.0} if "trip" in sys.argv[5:] else {}
         inprocess(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]), "structured" in sys.argv[5:], "f32" if "f32" in sys.argv[5:] else "f64", kw)
+    elif mode == "split":
+        split_case()
     elif mode == "auto":
         auto_case(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]))
     elif mode == "timeout":

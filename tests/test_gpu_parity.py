@@ -259,8 +259,10 @@ def test_counters_on_a_clean_run():
 # probability, so for those shapes the oracle is run with the aliasing off (same formulas, per-node blocks).
 # "ragged" / "ragged2": NON-UNIFORM branching, per-node child counts (solveSumChildren / solveChildNodesUpdate walk nChildrenCumul,
 # Utilities.cu:142-201); ragged2 also branches again after a single-child stage, so its oracle runs with the aliasing off.
+# "deepchain" / "deepcrown": the chains start below stage CROWN_MAX_DEPTH, so the forward walk does not fold the crown (Ctx::fold_crown_mode = 0):
+# k_down_crown_all for the 9 crown nodes of the one, a k_down_crown launch per stage for the 255 of the other; both branch late.
 EDGE_SHAPES = [("deep", True), ("fan", True), ("tall", True), ("widecrown", True), ("late", False), ("horizon1", False), ("horizon2", False),
-               ("ragged", True), ("ragged2", False)]
+               ("ragged", True), ("ragged2", False), ("deepchain", False), ("deepcrown", False)]
 
 
 @pytest.mark.parametrize("structured", [False, True])

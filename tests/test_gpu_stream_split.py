@@ -377,25 +377,16 @@ def sharded_tree(cus, lanes_per, world=2):
     raise AssertionError("no two-rank tree for %d CUs" % cus)
 
 
-@pytest.mark.parametrize("exchange", ["optimistic", "exact"])
-def test_sharded_up_walk_adds_the_second_partial(exchange):
-    """k_up_chain_cut<SPLIT>: two ranks whose cut lies right above the chains, so that the chain
-    walks and the cut parents' sums are ONE launch, each shard's OWN node count putting its last round in the split range, three
-    stages deep.  The conditions of the merged launch (Ctx::up_cut_lanes) are asserted from the shards."""
+def sharded_split_problem():
+    """(problem, forecast, cut stage, expect) of the b240 network on sharded_tree; expect(shards) asserts, from the two shard contexts behind a
+    run, the split last round of each and the conditions of the merged launch (Ctx::up_cut_lanes)"""
     idx, nx, nu, nd, ne = NETS["b240"]
     lanes_per = (nu - ne + nx + 63) // 64 * 64
     branching, N, cut, rs = sharded_tree(num_cus(), lanes_per)
     p, fc = problem("b240", "sharded", branching, N)
-    ref, ohist = reference(("b240", "sharded"), p, fc)
-    rk = Ranks(p, 2, cut, optimistic=exchange != "exact")
-    try:
-        def solve(s):
-            s.initialiseSmpcController(*fc)
-            s.apgReset()
-            return s.apgIterate(ITERS)
 
-        hists = rk.run(solve)
-        for rank, (s, r) in enumerate(zip(rk.shards, rs)):
+    def expect(shards):
+        for rank, (s, r) in enumerate(zip(shards, rs)):
             info, k = s.streamInfo(), s.kernelInfo()
             print("\nrank %d nodes %d r %d %s %s" % (rank, s.nodes, r, info, k))
             assert info["splitFirst"] == s.nodes - r and s.nodes == info["numCUs"] + r and info["twoPerCU"] == 1, (info, s.nodes, r)
@@ -407,11 +398,42 @@ def test_sharded_up_walk_adds_the_second_partial(exchange):
             assert 2 <= kids[cum[cut - 1]:cum[cut]].max() <= UPCUT_THREADS // lanes_per and lanes_per <= UPCUT_THREADS
             k_local = cum[N] - cum[N - 1]
             assert 2 * k_local < r <= 3 * k_local                       # the split round reaches the third stage from the end
+
+    return p, fc, cut, expect
+
+
+@pytest.mark.parametrize("exchange", ["optimistic", "exact"])
+def test_sharded_up_walk_adds_the_second_partial(exchange):
+    """k_up_chain_cut<SPLIT>: two ranks whose cut lies right above the chains, so that the chain
+    walks and the cut parents' sums are ONE launch, each shard's OWN node count putting its last round in the split range, three
+    stages deep.  The conditions of the merged launch (Ctx::up_cut_lanes) are asserted from the shards."""
+    p, fc, cut, expect = sharded_split_problem()
+    ref, ohist = reference(("b240", "sharded"), p, fc)
+    rk = Ranks(p, 2, cut, optimistic=exchange != "exact")
+    try:
+        def solve(s):
+            s.initialiseSmpcController(*fc)
+            s.apgReset()
+            return s.apgIterate(ITERS)
+
+        hists = rk.run(solve)
+        expect(rk.shards)
         for h in hists:
             assert np.abs(h - ohist).max() <= REL_TOL * np.abs(ohist).max()
         compare("sharded, %s" % exchange, rk.gathered, rk.shards[0], p["tree"], ref, REL_TOL)
     finally:
         rk.close()
+
+
+def test_sharded_up_walk_with_the_one_shot_exchange():
+    """k_up_chain_cut<SPLIT, GATHER>: the same two shards with the one-shot transport, whose merged launch also pushes the cut parents' sums to
+    the peer and gathers the peer's.  In a process of its own, as every in-process one-shot run (tests/oneshot_worker.py, `split`): the split
+    and the merged launch are asserted from the shards behind each transport's run, the one-shot iterates, histories and batch counters are
+    bitwise the stand-in transport's, and both are the oracle's at REL_TOL."""
+    from test_gpu_oneshot import run
+
+    out = run(("split",))
+    assert "oneshot inprocess ok" in out, out
 
 
 @pytest.mark.parametrize("knobs", [{"fuse_split": 1}, {"fuse_split": 3}, {"unscaled_walk": 0}])

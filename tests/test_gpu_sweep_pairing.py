@@ -96,6 +96,31 @@ def test_pair_against_the_oracle_on_the_same_blocks():
     s.close()
 
 
+@pytest.mark.parametrize("storage,pairing", [("f32", "on"), ("native", "auto")])
+def test_pair_under_the_profiler_runs_its_halves_in_turn(storage, pairing):
+    """While rn_profile_enable is set every interval is bracketed on the context's one stream: the second right-hand side's steps run BEHIND
+    the first's, on the first's scratch set, instead of beside them on a stream of their own.  Same kernels, same inputs: bitwise the
+    pair of a context that is not profiled, and the oracle's iterates on the same blocks at REL_TOL."""
+    p, fc = problem("small")
+    iters, runs = 6, {}
+    for prof in (0, 1):
+        s = solver(p, fc, storage=storage, sweep_pairing=pairing)
+        s.setAlgorithm(NAMA, 5)
+        s.profileEnable(prof)
+        h, v, t = s.algorithmNama(iters)
+        s.profileEnable(0)
+        runs[prof] = {"hist": h, "values": v, "tau": t, "bufs": {b: s.get(b) for b in FBE_BUFS}, "pairs": pairs_of(s)}
+        if prof:
+            o = oracle_with_blocks(p, fc, blocks_of(s), alg=NAMA)
+            ho, vo, to = o.fbe_nama(iters)
+            assert np.array_equal(t, to), (t, to)
+            assert relmax(v, vo) < REL_TOL and relmax(h, ho) < REL_TOL
+            fbe.compare_fbe(s, o, NAMA, REL_TOL, "paired NAMA under the profiler, %s blocks" % storage)
+        s.close()
+    assert runs[0]["pairs"] > 0 and runs[1]["pairs"] == runs[0]["pairs"], (runs[0]["pairs"], runs[1]["pairs"])
+    assert_bitwise(runs[1], runs[0], "profiled pair, %s blocks" % storage)
+
+
 def test_pair_on_a_context_with_a_split_last_round():
     """the context's APG launch is split; the pair sweep runs unsplit and leaves the split state alone"""
     p, fc = spl.problem("b236", "three")
