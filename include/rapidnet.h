@@ -266,6 +266,38 @@ enum { RN_PLAN_ECON = 0, RN_PLAN_SMOOTH, RN_PLAN_STORED, RN_PLAN_SHORT_EXP, RN_P
 int rn_plan_report(rn_ctx *ctx, size_t stages, double *perStage /* [stages][RN_PLAN_COLS] */);
 int rn_plan_report_scenarios(rn_ctx *ctx, size_t leaves, double *perLeaf /* [leaves][RN_PLAN_COLS] */, int *leafNode /* may be NULL */);
 int rn_plan_report_device(rn_ctx *ctx, void **perStage, void **perLeaf, size_t *leaves);
+/* Plan bands: what the plan the context holds looks like across the scenario tree -- per stage the band of every tank level (RN_BAND_X) or
+ * pump flow (RN_BAND_U) over the scenarios, and the trajectories themselves: a fan chart's 5 % / median / 95 % with scenario paths drawn over
+ * it, the companion of the plan report's cost distribution.  The reference has no counterpart (its read-outs, SmpcController.cu:1819-1859,
+ * follow ONE realised trajectory).  Values are the physical x and u that rn_get(RN_BUF_X / RN_BUF_U) would return at that moment; results
+ * are doubles whatever the context's precision (an fp32 value is widened exactly).
+ * Quantile of stage k, component c, level q in [0, 1], under the probabilities in force (rn_set_tree_data): the nodes i of the stage with
+ *   p_i > 0, ordered by (value ascending, node index ascending); their p added in that order in fp64, one after the other,
+ *   c_1 = p_(1), c_j = c_(j-1) + p_(j); the result is the value of the first j with c_j >= q * c_m (c_m the last sum, q * c_m one product).
+ *   It is always one of the inputs (no interpolation); q = 0 is the minimum and q = 1 the maximum over the nodes that can occur; a stage of
+ *   one node returns that node's value for every q.  The summation order is part of the definition: two calls, and every rank of a sharded
+ *   context, return the same bits.
+ * rn_plan_quantiles: out [stages][dim][nq], stages = dims.N, dim = nx or nu, level l at the caller's position l (q in any order, nq <=
+ *   RN_BAND_MAX_LEVELS).
+ * rn_plan_quantiles_device: the same table, doubles in device memory, valid until the next rn_plan_quantiles* call on this context; launches
+ *   on the context's stream, no host synchronisation (the levels travel in the kernel's arguments).  A (stage, component) that holds a
+ *   value that is not finite reads NaN at every level there; the host form returns RN_E_STATE instead.
+ * rn_plan_paths: out [leaves][dims.N][dim]: row (l, k) is the row of the ancestor at stage k of leaf l, the l-th node of the last stage;
+ *   leafNode (may be NULL) receives that node's index.
+ * Sharded contexts (rn_create_sharded): every rank calls; each packs its rows and probabilities into a table of the whole tree, the table
+ *   is summed on the context's communicator (exact: one rank at most holds a nonzero value at each entry; a zero's sign may change), and
+ *   every rank then holds the WHOLE tree's results, the same bits: stages and node indices are the full tree's, `leaves` its last stage's.
+ * Errors: RN_E_ARG for a wrong `which`, nq = 0 or nq > RN_BAND_MAX_LEVELS, a level outside [0, 1] or NaN, stages / leaves not the tree's, a
+ *   NULL levels or output pointer; RN_E_STATE before the first sweep of a solve, after a batch that failed half-way (until rn_apg_reset), when
+ *   the plan holds a value that is not finite, when a stage holds more than 4096 nodes (the sort's keys of one stage stay in LDS), or on a
+ *   context sharded by hand.  Memory: the first call allocates the result tables (sized for the larger of nx and nu; on a shard the whole
+ *   tree's table as well) and keeps them; later calls allocate nothing (rn_device_memory_info info[2]); a context that never asks
+ *   allocates and launches nothing. */
+enum { RN_BAND_X = 0, RN_BAND_U = 1 };
+enum { RN_BAND_MAX_LEVELS = 16 };
+int rn_plan_quantiles(rn_ctx *ctx, int which, size_t nq, const double *q, size_t stages, double *out /* [stages][dim][nq] */);
+int rn_plan_quantiles_device(rn_ctx *ctx, int which, size_t nq, const double *q, void **out /* device, fp64, same layout */);
+int rn_plan_paths(rn_ctx *ctx, int which, size_t leaves, double *out /* [leaves][N][dim] */, int *leafNode /* may be NULL */);
 /* Engine::setDemandUncertaintyFlag / setPriceUncertaintyFlag / SmpcConfiguration::getWeightEconomical */
 int rn_set_uncertainty(rn_ctx *ctx, int demandUncertainty, int priceUncertainty, double weightEconomical);
 /* Engine::updateStateControl (Engine.cu:1300-1316) */

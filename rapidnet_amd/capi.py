@@ -36,6 +36,9 @@ EXCHANGE_COLLECTIVE, EXCHANGE_ONESHOT, EXCHANGE_AUTO = 0, 1, 2
 # rn_plan_report: the columns of both tables, in the order of RN_PLAN_* (the first six are sums, the last three maxima)
 PLAN_COLUMNS = ("econ", "smooth", "stored", "shortExp", "xboxExp", "uboxExp", "shortMax", "xboxMax", "uboxMax")
 PLAN_SUMS = 6
+# rn_plan_quantiles / rn_plan_paths: which array (RN_BAND_*), and the most levels one call takes
+BAND_X, BAND_U, BAND_MAX_LEVELS = 0, 1, 16
+BANDS = {"x": BAND_X, "u": BAND_U}
 
 # every symbol include/rapidnet.h (the boundary) and include/rapidnet_debug.h (test hooks, rn_debug_*) declare
 SYMBOLS = [
@@ -56,6 +59,7 @@ SYMBOLS = [
     "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_set_bounds", "rn_set_bounds_device", "rn_get_bounds_layout", "rn_get_bounds", "rn_debug_cut_moments",
     "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live", "rn_debug_stream_units",
     "rn_plan_report", "rn_plan_report_scenarios", "rn_plan_report_device",
+    "rn_plan_quantiles", "rn_plan_quantiles_device", "rn_plan_paths",
 ]
 
 
@@ -260,6 +264,9 @@ def load():
     lib.rn_plan_report.argtypes = [vp, C.c_size_t, dp]
     lib.rn_plan_report_scenarios.argtypes = [vp, C.c_size_t, dp, dp]
     lib.rn_plan_report_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_size_t)]
+    lib.rn_plan_quantiles.argtypes = [vp, ip, C.c_size_t, dp, C.c_size_t, dp]
+    lib.rn_plan_quantiles_device.argtypes = [vp, ip, C.c_size_t, dp, C.POINTER(vp)]
+    lib.rn_plan_paths.argtypes = [vp, ip, C.c_size_t, dp, dp]
     _LIB = lib
     return lib
 
@@ -752,6 +759,43 @@ class Solver:
         a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
         self._check(self.lib.rn_plan_report_device(self.h, C.byref(a), C.byref(b), C.byref(n)))
         return a.value, b.value, n.value
+
+    # ---- what the plan at hand looks like across the tree (rn_plan_quantiles, rn_plan_paths) -----------------------
+    def _band(self, which):
+        w = BANDS.get(which, which)
+        return int(w), {BAND_X: self.nx, BAND_U: self.nu}.get(w, 1)
+
+    def bandLeaves(self):
+        """rows of planPaths: the node count of the WHOLE tree's last stage (on a shard too)"""
+        st = _i32(self.tree["stages"])
+        return int((st == st.max()).sum())
+
+    def planQuantiles(self, which, q):
+        """rn_plan_quantiles: weighted quantiles of every component of x or u ("x" | "u" or a BAND_* value) per stage at the levels q (any
+        order, at most BAND_MAX_LEVELS), an array [stages][dim][len(q)].  On a shard every rank calls it and receives the whole tree's."""
+        w, dim = self._band(which)
+        q = _f64(q)
+        out = np.zeros((self.N, dim, max(q.size, 1)))
+        self._check(self.lib.rn_plan_quantiles(self.h, w, q.size, q.ctypes.data, self.N, out.ctypes.data))
+        return out
+
+    def planQuantilesDevice(self, which, q):
+        """rn_plan_quantiles_device: the address of the same table, [stages][dim][len(q)] doubles in device memory, valid until the next
+        quantile call; nothing is waited for"""
+        w, _ = self._band(which)
+        q = _f64(q)
+        a = C.c_void_p()
+        self._check(self.lib.rn_plan_quantiles_device(self.h, w, q.size, q.ctypes.data, C.byref(a)))
+        return a.value
+
+    def planPaths(self, which):
+        """rn_plan_paths: (array [leaves][N][dim]: the rows of x or u along the path of every leaf of the whole tree, root first; array [leaves]
+        of the leaves' node indices in the whole tree).  On a shard every rank calls it."""
+        w, dim = self._band(which)
+        leaves = self.bandLeaves()
+        out, ln = np.zeros((leaves, self.N, dim)), np.zeros(leaves, dtype=np.int32)
+        self._check(self.lib.rn_plan_paths(self.h, w, leaves, out.ctypes.data, ln.ctypes.data))
+        return out, ln
 
     def updateTree(self, tree):
         """a re-weighted scenario tree of the SAME topology (on a shard: the full tree): replaces self.tree and hands its probabilities and errors

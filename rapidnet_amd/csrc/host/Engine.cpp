@@ -133,6 +133,18 @@ void Engine::evaluatePlan(PlanReport &r) {
     check(rn_plan_report(ctx, r.stages, r.perStage.data()), "rn_plan_report");
     check(rn_plan_report_scenarios(ctx, r.scenarios, r.perScenario.data(), r.leafNode.data()), "rn_plan_report_scenarios");
 }
+void Engine::planQuantiles(int which, const std::vector<real_t> &levels, std::vector<real_t> &out) {
+    const size_t stages = ptrMyScenarioTree->getPredHorizon(), dim = which == RN_BAND_U ? ptrMySmpcConfig->getNU() : ptrMySmpcConfig->getNX();
+    out.assign(stages * dim * levels.size(), 0.0);
+    check(rn_plan_quantiles(ctx, which, levels.size(), levels.data(), stages, out.data()), "rn_plan_quantiles");
+}
+void Engine::planPaths(int which, std::vector<real_t> &out, std::vector<int> &leafNode) {
+    const size_t stages = ptrMyScenarioTree->getPredHorizon(), dim = which == RN_BAND_U ? ptrMySmpcConfig->getNU() : ptrMySmpcConfig->getNX();
+    const size_t scenarios = ptrMyScenarioTree->getNumScenarios();
+    out.assign(scenarios * stages * dim, 0.0);
+    leafNode.assign(scenarios, 0);
+    check(rn_plan_paths(ctx, which, scenarios, out.data(), leafNode.data()), "rn_plan_paths");
+}
 
 void Engine::create(int precision, int device, int operatorMode, int rank, int nranks, const void *id128, int cutStage) {
     myRank = rank; numRanks = nranks;

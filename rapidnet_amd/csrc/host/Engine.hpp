@@ -107,6 +107,12 @@ public:
     };
     size_t getNumLocalScenarios();                   // local nodes at the last stage: the rows of PlanReport::perScenario
     void evaluatePlan(PlanReport &report);
+    // What the plan looks like across the tree (rapidnet.h, rn_plan_quantiles / rn_plan_paths; the reference has no counterpart): weighted
+    // quantiles of every component of x (RN_BAND_X) or u (RN_BAND_U) per stage at `levels`, out [stages][dim][levels]; and the rows along
+    // every scenario's path, out [scenarios][stages][dim] with leafNode [scenarios], the node of the whole tree each path ends in.  After
+    // a solve; on a sharded engine every rank calls them and receives the whole tree's tables.
+    void planQuantiles(int which, const std::vector<real_t> &levels, std::vector<real_t> &out);
+    void planPaths(int which, std::vector<real_t> &out, std::vector<int> &leafNode);
     int getRank() { return myRank; }
     int getNumRanks() { return numRanks; }
     uint_t getNumLocalNodes();                       // nodes this rank holds (= the tree's node count on one GPU)

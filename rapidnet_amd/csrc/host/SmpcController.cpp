@@ -114,6 +114,37 @@ uint_t SmpcController::writePlanReport(std::fstream &out) {
     out.precision(digits);
     return 1;
 }
+const SmpcController::PlanBands &SmpcController::getPlanBands(const std::vector<real_t> &levels) {
+    PlanBands &b = planBands;
+    b.stages = ptrMyEngine->getScenarioTree()->getPredHorizon();
+    b.scenarios = ptrMyEngine->getScenarioTree()->getNumScenarios();
+    b.nx = ptrMySmpcConfig->getNX(); b.nu = ptrMySmpcConfig->getNU();
+    b.levels = levels;
+    ptrMyEngine->planQuantiles(RN_BAND_X, levels, b.xQuantiles);
+    ptrMyEngine->planQuantiles(RN_BAND_U, levels, b.uQuantiles);
+    ptrMyEngine->planPaths(RN_BAND_X, b.xPaths, b.leafNode);
+    ptrMyEngine->planPaths(RN_BAND_U, b.uPaths, b.leafNode);
+    return planBands;
+}
+uint_t SmpcController::writePlanBands(std::fstream &out) {
+    if (!out.is_open()) return 0;
+    const PlanBands &b = getPlanBands(std::vector<real_t>{0.05, 0.5, 0.95});
+    const std::streamsize digits = out.precision(17);
+    const auto flat = [&](const char *name, const std::vector<real_t> &v) {
+        out << ", \"" << name << "\": [";
+        for (size_t i = 0; i < v.size(); i++) out << (i ? ", " : "") << v[i];
+        out << "]";
+    };
+    out << "\"planBands\" : {\"shape\": [" << b.stages << ", " << b.scenarios << ", " << b.nx << ", " << b.nu << ", " << b.levels.size() << "]";
+    flat("levels", b.levels);
+    out << ", \"leafNode\": [";
+    for (size_t i = 0; i < b.leafNode.size(); i++) out << (i ? ", " : "") << b.leafNode[i];
+    out << "]";
+    flat("xQuantiles", b.xQuantiles); flat("uQuantiles", b.uQuantiles); flat("xPaths", b.xPaths); flat("uPaths", b.uPaths);
+    out << "}" << std::endl;
+    out.precision(digits);
+    return 1;
+}
 uint_t SmpcController::controlAction(real_t *u) {
     if (!factorStepFlag) { ptrMyEngine->factorStep(); factorStepFlag = true; }
     size_t before[4];

@@ -61,6 +61,21 @@ public:
     // ... written as one more entry of the control output: "planReport" : {"columns": [...], "perStage": [[...]], "leafNode": [...],
     // "perScenario": [[...]]}, a JSON object with 17 significant digits.  controlAction(fstream&)'s own output is unchanged.
     uint_t writePlanReport(std::fstream &controlOutputJson);
+    // What the plan of the last control step looks like across the tree (Engine::planQuantiles / planPaths, rapidnet.h rn_plan_quantiles):
+    // the fan chart of every tank level and pump flow -- quantiles per stage at `levels` -- and every scenario's trajectory.  To be called
+    // AFTER controlAction, like getPlanReport: the first call allocates its tables on the device and keeps them.
+    struct PlanBands {
+        size_t stages = 0, scenarios = 0, nx = 0, nu = 0;
+        std::vector<real_t> levels;
+        std::vector<real_t> xQuantiles, uQuantiles;      // [stages][nx | nu][levels]
+        std::vector<real_t> xPaths, uPaths;              // [scenarios][stages][nx | nu]
+        std::vector<int> leafNode;                       // [scenarios]
+    };
+    const PlanBands &getPlanBands(const std::vector<real_t> &levels);
+    // ... written as one more entry of the control output: "planBands" : {"shape": [stages, scenarios, nx, nu, levels], "levels": [...],
+    // "leafNode": [...], "xQuantiles": [...], "uQuantiles": [...], "xPaths": [...], "uPaths": [...]}, flat arrays in the layouts above, with
+    // 17 significant digits, at the levels 0.05, 0.5, 0.95.  controlAction(fstream&)'s own output is unchanged.
+    uint_t writePlanBands(std::fstream &controlOutputJson);
     real_t *getValueFbe() { return vecValueFbe.data(); }    // :1883
     real_t *getVecTau() { return vecTau.data(); }
     ~SmpcController();
@@ -106,6 +121,7 @@ protected:
     std::vector<real_t> vecPrimalInfs, vecValueFbe, vecTau, lastControl;
     real_t economicKpi, smoothKpi, safeKpi, networkKpi;
     Engine::PlanReport planReport;
+    PlanBands planBands;
 };
 
 #endif

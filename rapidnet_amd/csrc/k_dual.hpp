@@ -628,13 +628,21 @@ __global__ void __launch_bounds__(ELT_THREADS) k_finalize(const Partial *partial
 
 // ------------------------------------------------------------------------------------------------------
 // step-wise elementwise kernels (known-answer test API; same arithmetic as the fused kernel)
+// The element type arrives as a flag and not as a template parameter (one kernel instead of two, as k_clamp_vec: the launch is outside the
+// batches); lambda travels as a double that holds the caller's T exactly, the arithmetic is the typed one, bit for bit
 template <typename T>
-__global__ void k_extrapolate(T *acc, T *xi, const T *upd, T lambda, long long n) {   // SmpcController.cu:535-557
+__device__ __forceinline__ void extrapolate_body(void *acc_, void *xi_, const void *upd_, T lambda, long long n) {   // SmpcController.cu:535-557
+    T *acc = static_cast<T *>(acc_), *xi = static_cast<T *>(xi_);
+    const T *upd = static_cast<const T *>(upd_);
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const T y1 = upd[i];
         acc[i] = extrap_elem(y1, xi[i], lambda);   // the roundings of the fused dual update's w_next
         xi[i] = y1;
     }
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void k_extrapolate(void *acc, void *xi, const void *upd, double lambda, long long n, int f64) {
+    if (f64) extrapolate_body<double>(acc, xi, upd, lambda, n); else extrapolate_body<float>(acc, xi, upd, (float)lambda, n);
 }
 // prox phase 1: z = clamp(hx + w/lambda); per-block dist^2 partials          (SmpcController.cu:778-792, :810)
 template <typename T>

@@ -254,4 +254,170 @@ __global__ void __launch_bounds__(PLAN_THREADS) k_plan_report(PlanArgs a) {
     else { if (a.f64) plan_folds_body<double>(a, red); else plan_folds_body<float>(a, red); }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// rn_plan_quantiles / rn_plan_quantiles_device / rn_plan_paths (include/rapidnet.h): what the plan looks like across the tree -- weighted
+// quantiles of every component of x or u per stage, and the rows along every leaf's path.  The reference has no counterpart.  One kernel,
+// the phase a run-time argument uniform over the grid, the element type of `src` and `prob` a flag (k_plan_report's idiom):
+//   phase 0  quantiles.  Workgroup (stage k, component c) loads the stage's contiguous rows of that component as (double value, node index)
+//            into LDS, padded to the next power of two with (+inf, INT_MAX); a node with p <= 0 is keyed +inf, so it sorts behind every node
+//            that can occur.  A bitonic network orders by (value, index).  Wave 0 then walks the `live` leading entries in chunks of 64:
+//            every lane fetches the p of its entry, and the sum runs through the lanes ONE AFTER THE OTHER (c_j = c_{j-1} + p_(j), fp64):
+//            once for c_m, once more to pick, for every level, the first j with c_j >= q * c_m (one product, nothing to contract).  The
+//            order of the additions is part of the definition: any call on any rank gives the same bits.  Levels arrive ascending (q) with
+//            the caller's position of each (slot).  Values that are not finite are counted into *flag, and their (stage, component) reads
+//            NaN at every level.
+//   phase 1  paths.  Workgroup l walks leaf l's ancestors into LDS once, then copies the N rows, two elements per thread where dim and the
+//            row stride are even (16-byte stores): paths[l][k][c]; leafNode[l] = the leaf.
+//   phase 2  pack (sharded contexts).  Local rows, widened, and the local p go to row gmap[i] of a zeroed [full nodes][dim + 1] table; the
+//            replicated crown rows [0, crownNodes) only where writeCrown (rank 0), so that a sum over the ranks holds every entry once.
+//            Phases 0 and 1 then read the summed table (f64 = 1, rowStride = probStride = dim + 1, prob = table + dim).
+constexpr int BANDS_THREADS = 256, BANDS_WIDTH = 4096, BANDS_LEVELS = 16;
+struct BandsArgs {
+    int phase, f64;
+    int nodes, dim, N, leaves, nq;
+    int rowStride, probStride;        // in elements
+    const void *src, *prob;           // of T (f64: doubles, else floats)
+    const int *parent, *stageCum;
+    double q[BANDS_LEVELS];           // ascending
+    int slot[BANDS_LEVELS];           // the caller's position of q[l]
+    double *quant;                    // [N][dim][nq]
+    double *paths;                    // [leaves][N][dim]
+    int *leafNode;                    // [leaves]
+    int *flag;                        // values that are not finite
+    const int *gmap;                  // phase 2: full-tree row of every local node
+    int crownNodes, writeCrown;
+    double *table;                    // phase 2: [full nodes][dim + 1]
+};
+static_assert(BANDS_WIDTH * (sizeof(double) + sizeof(int)) == 48 * 1024, "the sort's keys fill 48 KB of LDS");
+
+__device__ __forceinline__ bool bands_less(double va, int ia, double vb, int ib) { return va < vb || (va == vb && ia < ib); }
+
+template <typename T>
+__device__ __forceinline__ void bands_quantiles_body(const BandsArgs &a, double *val, int *idx, int *cnt) {
+#pragma clang fp contract(off)
+    const T *const src = static_cast<const T *>(a.src), *const prob = static_cast<const T *>(a.prob);
+    const int k = (int)blockIdx.x / a.dim, c = (int)blockIdx.x - k * a.dim;
+    const int s0 = a.stageCum[k], m = a.stageCum[k + 1] - s0;
+    if (m < 1 || m > BANDS_WIDTH) return;      // (refused on the host; uniform over the workgroup)
+    int P = 1;
+    while (P < m) P <<= 1;
+    const double inf = __builtin_huge_val();
+    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    int live = 0, bad = 0;
+    for (int i = threadIdx.x; i < P; i += BANDS_THREADS) {
+        double v = inf;
+        int id = 0x7fffffff;
+        if (i < m) {
+            id = s0 + i;
+            const double x = (double)src[(size_t)id * a.rowStride + c];
+            const double p = (double)prob[(size_t)id * a.probStride];
+            if (!(fabs(x) < inf)) bad++;
+            if (p > 0.0) { v = x; live++; }
+        }
+        val[i] = v; idx[i] = id;
+    }
+    if (live) atomicAdd(&cnt[0], live);
+    if (bad) atomicAdd(&cnt[1], bad);
+    __syncthreads();
+    for (int kk = 2; kk <= P; kk <<= 1) {      // (uniform trip counts: the barriers)
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < (P >> 1); t += BANDS_THREADS) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                const double vl = val[lo], vh = val[hi];
+                const int il = idx[lo], ih = idx[hi];
+                const bool swap = (lo & kk) == 0 ? bands_less(vh, ih, vl, il) : bands_less(vl, il, vh, ih);
+                if (swap) { val[lo] = vh; idx[lo] = ih; val[hi] = vl; idx[hi] = il; }
+            }
+            __syncthreads();
+        }
+    }
+    if (threadIdx.x >= 64) return;
+    const int lane = threadIdx.x;
+    live = cnt[0];
+    double *out = a.quant + ((size_t)k * a.dim + c) * a.nq;
+    if (cnt[1] > 0 || live == 0) {
+        if (lane < a.nq) out[lane] = __builtin_nan("");
+        if (lane == 0 && cnt[1] > 0) atomicAdd(a.flag, cnt[1]);
+        return;
+    }
+    // c_m: the p of a chunk's entries fetched together, added lane by lane (a lane beyond `live` adds +0.0, which changes no bit)
+    double tot = 0.0;
+    for (int base = 0; base < live; base += 64) {
+        const int j = base + lane;
+        const double pj = j < live ? (double)prob[(size_t)idx[j] * a.probStride] : 0.0;
+#pragma unroll
+        for (int t = 0; t < 64; t++) tot += __shfl(pj, t);
+    }
+    int l = 0;
+    double cum = 0.0;
+    for (int base = 0; base < live && l < a.nq; base += 64) {
+        const int j = base + lane;
+        const double pj = j < live ? (double)prob[(size_t)idx[j] * a.probStride] : 0.0;
+        double mine = 0.0;
+#pragma unroll
+        for (int t = 0; t < 64; t++) { cum += __shfl(pj, t); if (lane == t) mine = cum; }
+        while (l < a.nq) {      // (l is uniform over the wave)
+            const double thr = a.q[l] * tot;
+            const unsigned long long hit = __ballot(j < live && mine >= thr);
+            if (!hit) break;
+            if (lane == 0) out[a.slot[l]] = val[base + __ffsll(hit) - 1];
+            l++;
+        }
+    }
+}
+
+template <typename T, typename T2>
+__device__ __forceinline__ void bands_paths_body(const BandsArgs &a, int *anc) {
+    const T *const src = static_cast<const T *>(a.src);
+    const int l = blockIdx.x, N = a.N < BANDS_WIDTH ? a.N : BANDS_WIDTH, dim = a.dim;
+    const int leafNode = a.stageCum[a.N - 1] + l;
+    if (threadIdx.x == 0) {
+        int i = leafNode;
+        for (int k = N - 1; k >= 0; k--) {      // (N steps at most, and an index that stays in range whatever `parent` holds)
+            anc[k] = i;
+            i = a.parent[i];
+            if (i < 0 || i >= a.nodes) i = 0;
+        }
+        a.leafNode[l] = leafNode;
+    }
+    __syncthreads();
+    double *out = a.paths + (size_t)l * N * dim;
+    const int total = N * dim;
+    if (((dim | a.rowStride) & 1) == 0) {
+        for (int e = threadIdx.x * 2; e < total; e += BANDS_THREADS * 2) {
+            const int k = e / dim, c = e - k * dim;
+            const T2 v = *reinterpret_cast<const T2 *>(src + (size_t)anc[k] * a.rowStride + c);
+            *reinterpret_cast<double2 *>(out + e) = make_double2((double)v.x, (double)v.y);
+        }
+    } else {
+        for (int e = threadIdx.x; e < total; e += BANDS_THREADS) {
+            const int k = e / dim, c = e - k * dim;
+            out[e] = (double)src[(size_t)anc[k] * a.rowStride + c];
+        }
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void bands_pack_body(const BandsArgs &a) {
+    const T *const src = static_cast<const T *>(a.src), *const prob = static_cast<const T *>(a.prob);
+    const int w = a.dim + 1;
+    const long long n = (long long)a.nodes * w;
+    for (long long i = (long long)blockIdx.x * BANDS_THREADS + threadIdx.x; i < n; i += (long long)gridDim.x * BANDS_THREADS) {
+        const int node = (int)(i / w), c = (int)(i - (long long)node * w);
+        if (node < a.crownNodes && !a.writeCrown) continue;
+        a.table[(size_t)a.gmap[node] * w + c] = c < a.dim ? (double)src[(size_t)node * a.rowStride + c] : (double)prob[(size_t)node * a.probStride];
+    }
+}
+
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void __launch_bounds__(BANDS_THREADS) k_plan_bands(BandsArgs a) {
+    __shared__ double val[BANDS_WIDTH];
+    __shared__ int idx[BANDS_WIDTH];
+    __shared__ int cnt[2];
+    if (a.phase == 0) { if (a.f64) bands_quantiles_body<double>(a, val, idx, cnt); else bands_quantiles_body<float>(a, val, idx, cnt); }
+    else if (a.phase == 1) { if (a.f64) bands_paths_body<double, double2>(a, idx); else bands_paths_body<float, float2>(a, idx); }
+    else { if (a.f64) bands_pack_body<double>(a); else bands_pack_body<float>(a); }
+}
+
 }  // namespace rn

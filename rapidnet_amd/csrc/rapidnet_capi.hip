@@ -28,6 +28,7 @@
 #include "fbe_kernels.hpp"
 #include "partition.hpp"
 #include "bounds.hpp"
+#include "bands_host.hpp"
 
 // Every kernel this file launches is compiled in ONE of the units k_stream.hip ... k_fbe.hip; here the instantiations are only declared.
 // (RN_NO_EXTERN_TEMPLATES: the one-unit build tools/gen_instantiations.py uses to find out what is launched.)
@@ -252,6 +253,10 @@ struct CtxBase {
     virtual int plan_report(size_t, double *) = 0;
     virtual int plan_report_scenarios(size_t, double *, int *) = 0;
     virtual int plan_report_device(void **, void **, size_t *) = 0;
+    virtual int plan_quantiles(int, size_t, const double *, size_t, double *) = 0;
+    virtual int plan_quantiles_device(int, size_t, const double *, void **) = 0;
+    virtual int plan_paths(int, size_t, double *, int *) = 0;
+    virtual void set_full_tree(const int *, const int *, int, int) = 0;
 };
 
 // ---- in-process stand-in for the communicator (rn_debug_local_group_*): `n` contexts of one process, one host thread each ----
@@ -1349,7 +1354,7 @@ struct Ctx : CtxBase {
         for (int k = 0; k < n; k++) {
             const bool last = k == n - 1;
             if (!acc_ready) {   // re-derive w_t after manual buffer edits (SmpcController.cu:1514)
-                hipLaunchKernelGGL(k_extrapolate<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, p_acc, p_xi, p_upd, (T)h_lam[h_it - lamBase], ntot());
+                launch_extrapolate(h_lam[h_it - lamBase]);
                 acc_ready = true;
             }
             b.fuseReq = b.optimistic && fuse_want();
@@ -1950,9 +1955,14 @@ struct Ctx : CtxBase {
     }
 
     // ---- step-wise API -----------------------------------------------------------------------------------
+    // w = y+ + lambda (y+ - y), y = y+ (k_extrapolate<0>, k_dual.hpp): lambda rounded to T here, as the typed kernels took it
+    void launch_extrapolate(double lambda) {
+        hipLaunchKernelGGL(k_extrapolate<>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, (void *)p_acc, (void *)p_xi, (const void *)p_upd, (double)(T)lambda,
+                           (long long)ntot(), sizeof(T) == 8 ? 1 : 0);
+    }
     int extrapolate(double lambda) override {
         RN_HIP(hipSetDevice(device));
-        hipLaunchKernelGGL(k_extrapolate<T>, dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, p_acc, p_xi, p_upd, (T)lambda, ntot());
+        launch_extrapolate(lambda);
         RN_HIP(hipGetLastError());
         p_acc_view = p_acc; acc_ready = true;
         return RN_OK;
@@ -2030,6 +2040,9 @@ struct Ctx : CtxBase {
 
     // ---- what the plan at hand costs and where it violates its bounds, per stage and per scenario ------------
 #include "plan_report.inc"
+
+    // ---- what the plan at hand looks like across the tree: quantiles per stage, rows along every leaf's path --
+#include "plan_bands.inc"
 
     // ---- multi-GPU ---------------------------------------------------------------------------------------
     // The communicator of this context.  ncclCommInitRank blocks until every rank of the id has arrived -- for ever if one never does.
@@ -2348,6 +2361,9 @@ int rn_debug_cut_moments(rn_ctx *ctx, double *E, double *P, size_t n) { RN_GUARD
 int rn_plan_report(rn_ctx *ctx, size_t stages, double *perStage) { RN_GUARD(ctx); return ctx->impl->plan_report(stages, perStage); }
 int rn_plan_report_scenarios(rn_ctx *ctx, size_t leaves, double *perLeaf, int *leafNode) { RN_GUARD(ctx); return ctx->impl->plan_report_scenarios(leaves, perLeaf, leafNode); }
 int rn_plan_report_device(rn_ctx *ctx, void **perStage, void **perLeaf, size_t *leaves) { RN_GUARD(ctx); return ctx->impl->plan_report_device(perStage, perLeaf, leaves); }
+int rn_plan_quantiles(rn_ctx *ctx, int which, size_t nq, const double *q, size_t stages, double *out) { RN_GUARD(ctx); return ctx->impl->plan_quantiles(which, nq, q, stages, out); }
+int rn_plan_quantiles_device(rn_ctx *ctx, int which, size_t nq, const double *q, void **out) { RN_GUARD(ctx); return ctx->impl->plan_quantiles_device(which, nq, q, out); }
+int rn_plan_paths(rn_ctx *ctx, int which, size_t leaves, double *out, int *leafNode) { RN_GUARD(ctx); return ctx->impl->plan_paths(which, leaves, out, leafNode); }
 int rn_set_uncertainty(rn_ctx *ctx, int dflag, int pflag, double w) { RN_GUARD(ctx); return ctx->impl->set_uncertainty(dflag, pflag, w); }
 int rn_update_state_control(rn_ctx *ctx, const double *x, const double *u, const double *dm) { RN_GUARD(ctx); return ctx->impl->update_state_control(x, u, dm); }
 int rn_eliminate_input_disturbance_coupling(rn_ctx *ctx, const double *dh, const double *ah) { RN_GUARD(ctx); return ctx->impl->eliminate(dh, ah); }
@@ -2472,6 +2488,7 @@ int rn_create_sharded(const rn_dims *dims, const rn_tree *tree, const double *er
     if (rc == RN_OK) {
         rn::CtxBase *c = ctx->impl;
         c->set_global_nodes(part.globalNode, part.dims.nodes, dims->nodes);
+        c->set_full_tree(tree->nodesPerStageCumul, tree->ancestor, dims->N, dims->nodes);      // (rn_plan_quantiles / rn_plan_paths cover the whole tree)
         if (part.errorDemandNode && part.errorPriceNode) rc = c->set_tree_errors(part.errorDemandNode, part.errorPriceNode);
         if (rc == RN_OK) rc = c->comm_init(rank, nranks, id128);
         if (rc == RN_OK) rc = c->set_cut_stage(part.cutStage);
