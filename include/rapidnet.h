@@ -378,6 +378,40 @@ int rn_reserve_iterations(rn_ctx *ctx, int maxIterations);
 /* Extension (the reference always cold-starts, SmpcController.cu:1509): when on,
  * rn_control_action keeps the duals of the previous control step and only restarts the momentum. */
 int rn_set_warm_start(rn_ctx *ctx, int on);
+/* Extension (the other half; the reference always cold-starts, SmpcController.cu:1509): the warm start
+ * SHIFTED one stage toward the root.  In a receding horizon what was stage k + 1 is stage k of the next control step, so every node starts
+ * from the multiplier of the node that stood one stage below it on the branch that was taken, per unit of probability.
+ * The correspondence m (purely topological, built on the host): m(root) = child number rootChild of the root, 0-based in child order (a root
+ *   that is a leaf, N = 1: m(root) = root); for the r-th child j of i: child number min(r, nc - 1) of m(i) when m(i) has nc > 0 children,
+ *   else m(j) = m(i) -- the last stage repeats.
+ * The values: with y+ the updated dual of the last solve (RN_BUF_UPD_XI / RN_BUF_UPD_PSI; rows [node][2 nx + nu] in the context), d the stage
+ *   diagonal of the factor step in the same column order, p the probabilities in force (rn_set_tree_data), for node i, component c, m = m(i):
+ *     f = sqrt(p_i / p_m) * (d[stage(m)][c] / d[stage(i)][c])      in fp64, in this order (a quotient, a root, a quotient, a product)
+ *     y_new[i][c] = (T)( f * (double) y+[m][c] )                    one more product, rounded once to the context's type
+ *     f = 0 where p_i == 0, p_m == 0 or d[stage(i)][c] == 0
+ *   i.e. the multiplier per unit of probability is carried over: F_i' xi_i / p_i = F_m' xi_m / p_m with F_i = sqrt(p_i) diag(d_stage(i)).  A
+ *   zero of y+ enters as +0 (so that a shard, whose rows pass through a sum, holds the bits of one GPU).  fp64 arithmetic on fp32 contexts
+ *   too, with the probabilities as given.  The result is written to BOTH y (RN_BUF_XI / _PSI) and y+; the accelerated dual is marked not
+ *   current, as rn_set_warm_start's restart leaves it, and the next solve starts its momentum at theta = {1, 1}.  No atomics: two calls from
+ *   the same state give the same bits.
+ * rn_shift_warm_start: rootChild in [0, children of the root), or -1 for the root's child with the largest probability in force, ties to the
+ *   lowest index -- the one form that reads values back and so waits for the stream; otherwise one kernel and one copy on the context's
+ *   stream, no host synchronisation (the first call, and a call with another rootChild, also upload the correspondence).  It does NOT switch
+ *   the warm start on: with rn_set_warm_start off the next rn_control_action cold-starts as ever.  Call it between two control steps, before
+ *   the rn_control_action that is to start from the shifted duals.
+ * rn_set_shift_map: a forecaster's own correspondence in place of the rule: `nodes` entries for the nodes of the WHOLE tree (also on a
+ *   shard), each in [0, nodes) or -1 for "start this node from zero"; map == NULL returns to the rule.  With a caller's map in force
+ *   rootChild is ignored.  rn_get_shift_map: the map in force, or the rule's for that rootChild (on a shard -1 is refused: name the child).
+ * Sharded contexts (rn_create_sharded): every rank calls; each packs its rows of y+ and its probabilities into a zeroed table of the whole
+ *   tree, one sum all-reduce follows (exact: one rank at most holds a nonzero value at each entry), and each rank gathers its rows from the
+ *   table: one collective per control step.  The replicated crown gets the same bits on every rank.
+ * Errors: RN_E_STATE before a first solve, after a batch that failed half-way (until rn_apg_reset), on a context sharded by hand or without a
+ *   communicator, and while the algorithm is global FBE or NAMA (their L-BFGS memory belongs to the unshifted duals); RN_E_ARG for a rootChild
+ *   out of range, a map of another size or with an entry outside [-1, nodes).  Memory: the first shift allocates two ints per local node (on a
+ *   shard the whole tree's table, (2 nx + nu + 1) doubles per node, as well) and keeps them; a context that never shifts allocates nothing. */
+int rn_shift_warm_start(rn_ctx *ctx, int rootChild);
+int rn_set_shift_map(rn_ctx *ctx, size_t nodes, const int *map /* [nodes] or NULL */);
+int rn_get_shift_map(rn_ctx *ctx, int rootChild, size_t nodes, int *map /* [nodes] */);
 
 /* step-wise entry points mirroring the protected methods the reference's known-answer tests call */
 int rn_dual_extrapolation_step(rn_ctx *ctx, double lambda); /* SmpcController.cu:535-557  */

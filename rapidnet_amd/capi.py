@@ -60,6 +60,7 @@ SYMBOLS = [
     "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live", "rn_debug_stream_units",
     "rn_plan_report", "rn_plan_report_scenarios", "rn_plan_report_device",
     "rn_plan_quantiles", "rn_plan_quantiles_device", "rn_plan_paths",
+    "rn_shift_warm_start", "rn_set_shift_map", "rn_get_shift_map",
 ]
 
 
@@ -267,6 +268,9 @@ def load():
     lib.rn_plan_quantiles.argtypes = [vp, ip, C.c_size_t, dp, C.c_size_t, dp]
     lib.rn_plan_quantiles_device.argtypes = [vp, ip, C.c_size_t, dp, C.POINTER(vp)]
     lib.rn_plan_paths.argtypes = [vp, ip, C.c_size_t, dp, dp]
+    lib.rn_shift_warm_start.argtypes = [vp, ip]
+    lib.rn_set_shift_map.argtypes = [vp, C.c_size_t, dp]
+    lib.rn_get_shift_map.argtypes = [vp, ip, C.c_size_t, dp]
     _LIB = lib
     return lib
 
@@ -482,6 +486,28 @@ class Solver:
 
     def setWarmStart(self, on=True):
         self._check(self.lib.rn_set_warm_start(self.h, int(on)))
+
+    # ---- the warm start shifted one stage toward the root (rn_shift_warm_start ...) --------------------------------
+    def shiftWarmStart(self, root_child=-1):
+        """rn_shift_warm_start: y and y+ become the duals of the last solve moved one stage toward the root along child number root_child of
+        the root (-1: its most probable child under the probabilities in force).  Between two control steps; it does not switch the warm
+        start on (setWarmStart).  On a shard every rank calls it."""
+        self._check(self.lib.rn_shift_warm_start(self.h, int(root_child)))
+
+    def setShiftMap(self, node_map=None):
+        """rn_set_shift_map: a correspondence of one's own, an entry per node of the WHOLE tree (a node, or -1 for "from zero"); None: the
+        built-in rule again"""
+        if node_map is None:
+            self._check(self.lib.rn_set_shift_map(self.h, 0, None))
+            return
+        m = _i32(node_map)
+        self._check(self.lib.rn_set_shift_map(self.h, m.size, m.ctypes.data))
+
+    def getShiftMap(self, root_child=-1):
+        """rn_get_shift_map: the correspondence in force (the caller's, or the built-in rule's for root_child), [nodes of the whole tree]"""
+        m = np.zeros(self._treeNodes(), dtype=np.int32)
+        self._check(self.lib.rn_get_shift_map(self.h, int(root_child), m.size, m.ctypes.data))
+        return m
 
     def dualExtrapolationStep(self, lam):
         self._check(self.lib.rn_dual_extrapolation_step(self.h, float(lam)))

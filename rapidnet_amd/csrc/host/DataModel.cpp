@@ -195,6 +195,14 @@ SmpcConfiguration::SmpcConfiguration(string pathToFile) {
         if (momentumRestart != "off" && momentumRestart != "gradient")
             throw std::logic_error("controller configuration: momentumRestart must be \"off\" or \"gradient\" (got \"" + momentumRestart + "\")");
     }
+    // ... and what a control step inherits from the one before it (absent = "off": rapidnet.h, rn_set_warm_start / rn_shift_warm_start)
+    warmStart = "off";
+    if (doc.HasMember("warmStart")) {
+        _ASSERT(doc["warmStart"].IsString());
+        warmStart = doc["warmStart"].str;
+        if (warmStart != "off" && warmStart != "keep" && warmStart != "shift")
+            throw std::logic_error("controller configuration: warmStart must be \"off\", \"keep\" or \"shift\" (got \"" + warmStart + "\")");
+    }
     // ... and whether the APG solve of a control step ends on a residual tolerance (absent = 0: the reference's fixed maxIterations; rapidnet.h,
     // rn_set_stop_tolerance), checked every stopCheckEvery iterations (absent = 0: the library's default)
     stopTolerance = 0;

@@ -139,6 +139,10 @@ public:
     uint_t getStopCheckEvery() { return stopCheckEvery; }
     // "momentumRestart" (optional key, not in the reference's files): "off" (default) or "gradient" -- Engine.hpp, setRestart
     string getMomentumRestart() { return momentumRestart; }
+    // "warmStart" (optional key, not in the reference's files): "off" (default: every control step cold-starts, as the reference), "keep" (the
+    // duals of the previous step where they are -- Engine.hpp, setWarmStart) or "shift" (moved one stage toward the root first -- Engine.hpp,
+    // shiftWarmStart; SmpcController::controlAction calls it before every step but the first)
+    string getWarmStart() { return warmStart; }
     void setCurrentState();     // re-read from the configuration file (SmpcConfiguration.cu:240-256)
     void setPreviousControl();  // :261-277
     void setPreviousDemand();   // :283-299
@@ -151,7 +155,7 @@ private:
     uint_t NX, NU, ND, NV, lbfgsBufferSize, maxIteration, stopCheckEvery;
     std::vector<real_t> matL, matLhat, matCostW, matDiagPrecnd, currentX, prevU, prevDemand;
     real_t penaltyStateX, penaltySafetyX, stepSize, weightPrice, weightSmooth, weightSafety, stopTolerance;
-    string pathToConfiguration, pathToNetwork, pathToScenarioTree, pathToForecaster, algorithmName, operatorMode, operatorStorage, sweepPairing, momentumRestart;
+    string pathToConfiguration, pathToNetwork, pathToScenarioTree, pathToForecaster, algorithmName, operatorMode, operatorStorage, sweepPairing, momentumRestart, warmStart;
 };
 
 #endif

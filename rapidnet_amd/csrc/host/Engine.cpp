@@ -183,6 +183,7 @@ void Engine::create(int precision, int device, int operatorMode, int rank, int n
     if (ptrMySmpcConfig->getStopTolerance() > 0)   // (a file without the key makes exactly the calls it always made)
         check(rn_set_stop_tolerance(ctx, ptrMySmpcConfig->getStopTolerance(), (int)ptrMySmpcConfig->getStopCheckEvery()), "rn_set_stop_tolerance");
     if (ptrMySmpcConfig->getMomentumRestart() == "gradient") check(rn_set_restart(ctx, RN_RESTART_GRADIENT), "rn_set_restart");
+    if (ptrMySmpcConfig->getWarmStart() != "off") check(rn_set_warm_start(ctx, 1), "rn_set_warm_start");      // "keep" | "shift"
     // SmpcController::allocateApgAlgorithm (SmpcController.cu:124-151): per-iteration storage for maxIterations, allocated once
     check(rn_reserve_iterations(ctx, (int)ptrMySmpcConfig->getMaxIterations()), "rn_reserve_iterations");
     if (!apgFlag)   // SmpcController::allocateGlobalFbeAlgorithm / allocateNamaAlgorithm / allocateLbfgsBuffer (SmpcController.cu:234-330)
@@ -245,3 +246,9 @@ void Engine::calculateMatLandMatLhat() {
     useComputedL = true;
 }
 void Engine::setWarmStart(bool on) { check(rn_set_warm_start(ctx, on ? 1 : 0), "rn_set_warm_start"); }
+void Engine::shiftWarmStart(int rootChild) { check(rn_shift_warm_start(ctx, rootChild), "rn_shift_warm_start"); }
+void Engine::setShiftMap(const std::vector<int> &map) { check(rn_set_shift_map(ctx, map.size(), map.empty() ? nullptr : map.data()), "rn_set_shift_map"); }
+void Engine::getShiftMap(int rootChild, std::vector<int> &map) {
+    map.assign(ptrMyScenarioTree->getNumNodes(), 0);
+    check(rn_get_shift_map(ctx, rootChild, map.size(), map.data()), "rn_get_shift_map");
+}

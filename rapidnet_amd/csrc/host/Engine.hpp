@@ -128,6 +128,15 @@ public:
     real_t *getMatL() { return useComputedL ? computedL.data() : ptrMySmpcConfig->getMatL(); }
     real_t *getMatLhat() { return useComputedL ? computedLhat.data() : ptrMySmpcConfig->getMatLhat(); }
     void setWarmStart(bool on);
+    // The warm start shifted one stage toward the root (rapidnet.h, rn_shift_warm_start; the reference has no counterpart): between two control
+    // steps, the duals of the last solve move up the tree along child number rootChild of the root (-1: its most probable child), scaled to
+    // the multiplier per unit of probability; with setWarmStart(true) the next control step starts from them.  The constructors switch the
+    // warm start on for the configuration file's optional "warmStart" key "keep" or "shift" (absent or "off": the reference's cold start).
+    // setShiftMap: a correspondence of one's own, an entry per node of the whole tree (a node, or -1 for "from zero"); empty: the rule again.
+    // On a sharded engine every rank calls shiftWarmStart.
+    void shiftWarmStart(int rootChild = -1);
+    void setShiftMap(const std::vector<int> &map);
+    void getShiftMap(int rootChild, std::vector<int> &map);
     ScenarioTree *getScenarioTree() { return ptrMyScenarioTree; }
     DwnNetwork *getDwnNetwork() { return ptrMyNetwork; }
     SmpcConfiguration *getSmpcConfiguration() { return ptrMySmpcConfig; }

@@ -145,14 +145,19 @@ uint_t SmpcController::writePlanBands(std::fstream &out) {
     out.precision(digits);
     return 1;
 }
+void SmpcController::shiftBeforeStep() {
+    if (controlSteps > 0 && ptrMySmpcConfig->getWarmStart() == "shift") ptrMyEngine->shiftWarmStart(-1);
+}
 uint_t SmpcController::controlAction(real_t *u) {
     if (!factorStepFlag) { ptrMyEngine->factorStep(); factorStepFlag = true; }
+    shiftBeforeStep();
     size_t before[4];
     check(rn_device_memory_info(ptrMyEngine->getContext(), before), "rn_device_memory_info");
     const int rc = rn_control_action(ptrMyEngine->getContext(), ptrMySmpcConfig->getCurrentX(), ptrMySmpcConfig->getPrevU(),
                                      ptrMySmpcConfig->getPrevDemand(), ptrMyForecaster->getNominalDemand(),
                                      ptrMyForecaster->getNominalPrices(), ptrMySmpcConfig->getMaxIterations(), 0, u);
     if (rc != RN_OK) { std::cerr << "controlAction: " << rn_last_error(ptrMyEngine->getContext()) << std::endl; return 0; }
+    controlSteps++;
     if (deviceMemoryChanged(before)) return 0;
     return 1;   // devControlAction (lastControl) is only written by the stream overload (:1647), as in the reference
 }
@@ -162,6 +167,7 @@ uint_t SmpcController::controlAction(std::fstream &out) {
     if (!factorStepFlag) { ptrMyEngine->factorStep(); factorStepFlag = true; }
     const uint_t nu = ptrMySmpcConfig->getNU();
     std::vector<real_t> u(nu);
+    shiftBeforeStep();
     size_t before[4];
     check(rn_device_memory_info(ptrMyEngine->getContext(), before), "rn_device_memory_info");
     const int rc = rn_control_action(ptrMyEngine->getContext(), ptrMySmpcConfig->getCurrentX(), ptrMySmpcConfig->getPrevU(),
@@ -173,6 +179,7 @@ uint_t SmpcController::controlAction(std::fstream &out) {
     for (uint_t i = 0; i < nu; i++) out << u[i] << ", ";
     out << "]" << std::endl;
     lastControl = u;
+    controlSteps++;
     if (deviceMemoryChanged(before)) return 0;
     return 1;
 }

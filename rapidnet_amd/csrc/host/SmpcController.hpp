@@ -37,6 +37,10 @@ public:
         if (!factorStepFlag) { ptrMyEngine->factorStep(); factorStepFlag = true; }
         ptrMyEngine->setBounds(granularity, rows, xmin, xmax, xsafe, umin, umax);
     }
+    // The shifted warm start (Engine::shiftWarmStart, rapidnet.h rn_shift_warm_start) between two control steps.  With the configuration's
+    // "warmStart": "shift" both controlAction forms call it themselves before every step but the first -- in front of their leak check's
+    // window, since the first shift allocates its index arrays and keeps them -- along the root's most probable child.
+    void shiftWarmStart(int rootChild = -1) { ptrMyEngine->shiftWarmStart(rootChild); }
     void moveForewardInTime();                              // :1679-1716
     // in-built simulator of moveForewardInTime: false (default) = the reference as written, x+ = x + B u (its disturbance
     // term lands in the x of node 0 instead of the state update, :1695); true = x+ = x + e_0 + B u (DwnNetwork.cuh:41-57)
@@ -122,6 +126,8 @@ protected:
     real_t economicKpi, smoothKpi, safeKpi, networkKpi;
     Engine::PlanReport planReport;
     PlanBands planBands;
+    uint_t controlSteps = 0;      // control steps solved so far ("warmStart": "shift" moves the duals before every one but the first)
+    void shiftBeforeStep();
 };
 
 #endif

@@ -853,4 +853,67 @@ __global__ void __launch_bounds__(ELT_THREADS) k_restart_test(RestartArgs a) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// rn_shift_warm_start (include/rapidnet.h): the duals of the last solve moved one stage toward the root.  The reference has no counterpart.
+// One kernel, the phase a run-time argument uniform over the grid, the element type a flag (k_restart_test's idiom); one thread per
+// (node, component), rows contiguous, so a wave reads and writes whole lines.  No atomics: two calls give the same bits.
+//   phase 0  gather.  out[i][c] = (T)(f * y+[m][c]), m = srcRow[i] (-1: the row starts from zero),
+//            f = sqrt(p_i / p_m) * (d[stage(m)][c] / d[stage(i)][c]) in fp64 in this order, f = 0 where p_i == 0, p_m == 0 or d[stage(i)][c] == 0.
+//            The source is the context's own y+ and probabilities or, on a shard (table != nullptr), the summed table of the whole tree
+//            ([full nodes][ny + 1] doubles, p behind the row).  `out` is never the source: a row is read after another may have been written.
+//   phase 1  pack (sharded contexts).  Local rows, widened, and the local p go to row gmap[i] of the zeroed table; the replicated crown rows
+//            [0, crownNodes) only where writeCrown (rank 0), so that a sum over the ranks holds every entry once.
+struct ShiftArgs {
+    int phase, f64;
+    int nodes, ny;
+    const void *yp;               // y+ [nodes][ny] of T
+    void *out;                    // phase 0: [nodes][ny] of T
+    const void *dy;               // the stage diagonal [N][ny] of T
+    const void *prob;             // [nodes] of T ...
+    const double *prob64;         // ... or, where the context keeps them (fp32), the probabilities as given
+    const int *stageOf;           // [nodes]
+    const int *srcRow, *srcStage; // [nodes]: the row (of yp, or of table) a node inherits and that row's stage
+    double *table;                // shards: [full nodes][ny + 1]
+    const int *gmap;              // phase 1: full-tree row of every local node
+    int crownNodes, writeCrown;
+};
+template <typename T>
+__device__ __forceinline__ void shift_duals_body(const ShiftArgs &a) {
+#pragma clang fp contract(off)
+    const T *const yp = static_cast<const T *>(a.yp), *const dy = static_cast<const T *>(a.dy), *const prob = static_cast<const T *>(a.prob);
+    T *const out = static_cast<T *>(a.out);
+    const int ny = a.ny, tw = ny + 1;
+    const long long stride = (long long)gridDim.x * blockDim.x, gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a.phase == 1) {
+        const long long n = (long long)a.nodes * tw;
+        for (long long e = gid; e < n; e += stride) {
+            const int i = (int)(e / tw), c = (int)(e - (long long)i * tw);
+            if (i < a.crownNodes && !a.writeCrown) continue;
+            const double v = c < ny ? (double)yp[(size_t)i * ny + c] : (a.prob64 ? a.prob64[i] : (double)prob[i]);
+            a.table[(size_t)a.gmap[i] * tw + c] = v;
+        }
+        return;
+    }
+    const long long n = (long long)a.nodes * ny;
+    for (long long e = gid; e < n; e += stride) {
+        const int i = (int)(e / ny), c = (int)(e - (long long)i * ny);
+        const int m = a.srcRow[i];
+        double r = 0.0;
+        if (m >= 0) {
+            const double pi = a.prob64 ? a.prob64[i] : (double)prob[i];
+            const double pm = a.table ? a.table[(size_t)m * tw + ny] : (a.prob64 ? a.prob64[m] : (double)prob[m]);
+            const double di = (double)dy[(size_t)a.stageOf[i] * ny + c], dm = (double)dy[(size_t)a.srcStage[i] * ny + c];
+            const double v = a.table ? a.table[(size_t)m * tw + c] : (double)yp[(size_t)m * ny + c];
+            double f = 0.0;
+            if (pi != 0.0 && pm != 0.0 && di != 0.0) { const double s = sqrt(pi / pm), q = dm / di; f = s * q; }
+            r = f * (v + 0.0);      // (-0 enters as +0: a shard's rows have passed through a sum)
+        }
+        out[e] = (T)r;
+    }
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void __launch_bounds__(ELT_THREADS) k_shift_duals(ShiftArgs a) {
+    if (a.f64) shift_duals_body<double>(a); else shift_duals_body<float>(a);
+}
+
 }  // namespace rn

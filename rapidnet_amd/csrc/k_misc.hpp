@@ -464,8 +464,12 @@ __global__ void k_clamp_vec(void *u, const void *lo, const void *hi, int n, int 
 // Structured mode, composite operator (k_gemm_comp): the forward walk's affine terms join the product's constant operand, so that the walk's running
 // sums of [L v_i ; B L v_i] are u_i and x_i - x_anc themselves and the walk requests neither uhat nor eb (SweepArgs::lin bit 2):
 //   lvconst_i[0 .. nu) += uhat_i - uhat_anc   (root: - prevUhat) ;   lvconst_i[nu .. nu + nx) += eb_i - eb_anc   (root: eb_0)
+// The element type arrives as a flag and not as a template parameter (one kernel instead of two, as k_clamp_vec: the launch is once per
+// control step); the arithmetic is the typed one, bit for bit
 template <typename T>
-__global__ void k_fold_affine(T *lvconst, const T *uhat, const T *eb, const T *prevUhat, const int *parent, int nodes, int nu, int nx) {
+__device__ __forceinline__ void fold_affine_body(void *lvconst_, const void *uhat_, const void *eb_, const void *prevUhat_, const int *parent, int nodes, int nu, int nx) {
+    T *lvconst = static_cast<T *>(lvconst_);
+    const T *uhat = static_cast<const T *>(uhat_), *eb = static_cast<const T *>(eb_), *prevUhat = static_cast<const T *>(prevUhat_);
     const int w = nu + nx;
     const long long n = (long long)nodes * w;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
@@ -475,6 +479,11 @@ __global__ void k_fold_affine(T *lvconst, const T *uhat, const T *eb, const T *p
         else { const int j = t - nu; add = eb[(size_t)node * nx + j] - (par < 0 ? (T)0 : eb[(size_t)par * nx + j]); }
         lvconst[i] += add;
     }
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void k_fold_affine(void *lvconst, const void *uhat, const void *eb, const void *prevUhat, const int *parent, int nodes, int nu, int nx, int f64) {
+    if (f64) fold_affine_body<double>(lvconst, uhat, eb, prevUhat, parent, nodes, nu, nx);
+    else fold_affine_body<float>(lvconst, uhat, eb, prevUhat, parent, nodes, nu, nx);
 }
 
 }  // namespace rn

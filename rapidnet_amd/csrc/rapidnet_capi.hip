@@ -29,6 +29,7 @@
 #include "partition.hpp"
 #include "bounds.hpp"
 #include "bands_host.hpp"
+#include "shift_map.hpp"
 
 // Every kernel this file launches is compiled in ONE of the units k_stream.hip ... k_fbe.hip; here the instantiations are only declared.
 // (RN_NO_EXTERN_TEMPLATES: the one-unit build tools/gen_instantiations.py uses to find out what is launched.)
@@ -257,6 +258,9 @@ struct CtxBase {
     virtual int plan_quantiles_device(int, size_t, const double *, void **) = 0;
     virtual int plan_paths(int, size_t, double *, int *) = 0;
     virtual void set_full_tree(const int *, const int *, int, int) = 0;
+    virtual int shift_warm_start(int) = 0;
+    virtual int set_shift_map(size_t, const int *) = 0;
+    virtual int get_shift_map(int, size_t, int *) = 0;
 };
 
 // ---- in-process stand-in for the communicator (rn_debug_local_group_*): `n` contexts of one process, one host thread each ----
@@ -2044,6 +2048,9 @@ struct Ctx : CtxBase {
     // ---- what the plan at hand looks like across the tree: quantiles per stage, rows along every leaf's path --
 #include "plan_bands.inc"
 
+    // ---- the warm start shifted one stage toward the root of the scenario tree --------------------------------
+#include "shift_warm_start.inc"
+
     // ---- multi-GPU ---------------------------------------------------------------------------------------
     // The communicator of this context.  ncclCommInitRank blocks until every rank of the id has arrived -- for ever if one never does.
     // It therefore runs on a HELPER THREAD and the caller waits for it against the wall clock: after `timeoutSeconds` (< 0:
@@ -2364,6 +2371,9 @@ int rn_plan_report_device(rn_ctx *ctx, void **perStage, void **perLeaf, size_t *
 int rn_plan_quantiles(rn_ctx *ctx, int which, size_t nq, const double *q, size_t stages, double *out) { RN_GUARD(ctx); return ctx->impl->plan_quantiles(which, nq, q, stages, out); }
 int rn_plan_quantiles_device(rn_ctx *ctx, int which, size_t nq, const double *q, void **out) { RN_GUARD(ctx); return ctx->impl->plan_quantiles_device(which, nq, q, out); }
 int rn_plan_paths(rn_ctx *ctx, int which, size_t leaves, double *out, int *leafNode) { RN_GUARD(ctx); return ctx->impl->plan_paths(which, leaves, out, leafNode); }
+int rn_shift_warm_start(rn_ctx *ctx, int rootChild) { RN_GUARD(ctx); return ctx->impl->shift_warm_start(rootChild); }
+int rn_set_shift_map(rn_ctx *ctx, size_t nodes, const int *map) { RN_GUARD(ctx); return ctx->impl->set_shift_map(nodes, map); }
+int rn_get_shift_map(rn_ctx *ctx, int rootChild, size_t nodes, int *map) { RN_GUARD(ctx); return ctx->impl->get_shift_map(rootChild, nodes, map); }
 int rn_set_uncertainty(rn_ctx *ctx, int dflag, int pflag, double w) { RN_GUARD(ctx); return ctx->impl->set_uncertainty(dflag, pflag, w); }
 int rn_update_state_control(rn_ctx *ctx, const double *x, const double *u, const double *dm) { RN_GUARD(ctx); return ctx->impl->update_state_control(x, u, dm); }
 int rn_eliminate_input_disturbance_coupling(rn_ctx *ctx, const double *dh, const double *ah) { RN_GUARD(ctx); return ctx->impl->eliminate(dh, ah); }

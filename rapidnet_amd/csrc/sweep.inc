@@ -302,8 +302,8 @@
         if (d_MCp) launch_gemm<EPI_LV>(d_LBLp, d.nu + d.nx, d.nv, d_vconst, d.nv, d_lvconst, d.nu + d.nx, nullptr, 0);      // [L ; B L] c_i
         if (lin_fold()) {
             const long long tot = (long long)d.nodes * (d.nu + d.nx);
-            hipLaunchKernelGGL(k_fold_affine<T>, dim3((unsigned)std::min<long long>((tot + 255) / 256, (long long)numCUs * 8)), dim3(256), 0, stream, d_lvconst, d_uhat, d_eb, d_prevUhat,
-                               d_parent, d.nodes, d.nu, d.nx);
+            hipLaunchKernelGGL(k_fold_affine<>, dim3((unsigned)std::min<long long>((tot + 255) / 256, (long long)numCUs * 8)), dim3(256), 0, stream, (void *)d_lvconst, (const void *)d_uhat,
+                               (const void *)d_eb, (const void *)d_prevUhat, (const int *)d_parent, d.nodes, d.nu, d.nx, sizeof(T) == 8 ? 1 : 0);
         }
         RN_HIP(hipGetLastError());
         linConstValid = true;
