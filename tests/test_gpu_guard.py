@@ -147,6 +147,15 @@ def test_split_last_round_under_guard(guard, cases):
     guard["contexts"] = len(cases)
 
 
+def test_long_horizon_under_guard(guard):
+    """a chain of 37 stages (`m42_37` of tests/test_long_horizon_shapes.py), dense and structured: the second and later batches of prefetched
+    stages of the chain walks -- requests past the chain's end are clamped into it --, the fused walk + dual update's LDS tile of N rows and
+    the chain walk riding in it; one step from non-trivial duals and two optimistic batches + an exact one"""
+    import test_gpu_long_horizon as lhz
+
+    guard["contexts"] = lhz.guard_body()
+
+
 def test_barcelona31_under_guard(guard):
     """The full-size K = 31 Barcelona config: the kernel instantiations and launch shapes of the headline workload (G = 8 spans,
     two slots per thread, pipelined slab products, k_dual_stage tiles)."""
