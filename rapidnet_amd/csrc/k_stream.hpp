@@ -55,6 +55,16 @@ __device__ __forceinline__ bool stream_nz(float v) { return (__float_as_uint(v) 
 // nGroups * RN_GROUP + nHead live ones: the live count mod the group size goes FIRST (they are met in increasing order either way), as a partial group (RN_LOADH /
 // RN_USEH: the first nHead, whole ones) in the second buffer, with the first full group requested right behind it: the chunk's last loads are then those of a full
 // group.  The steady state has no branch inside, so the compiler's vmcnt waits are exact: while group g is consumed, group g+1 (and then g+2) is in flight.
+// THE WAIT COUNTS.  A request of the partial group and its use stand under two `if (d < nHead)` that the compiler cannot pair: it sees a path on which a buffer's
+// request is never waited for, carries that around the chunk loop, and in front of the next write to those registers -- the ADDRESS of a request is formed in the
+// register it loads into -- it waits for everything in flight (s_waitcnt vmcnt(0)).  In the ISA of the first version every request of the partial group was thus
+// issued only when the one before it had ARRIVED: one round trip per unit of the head, and with the skip a block is little more than a head (about 20 live units
+// of 60: a head of 4 and two groups).  RN_LANDED(n) states what the schedule guarantees at a point -- at most the n most recent requests are
+// still in flight -- as an s_waitcnt of the walk's own; it waits for nothing at run time, since what it names has been consumed: behind the partial group's use
+// (only the first full group, RN_GROUP_LOADS requests, can be in flight) and at the end of a chunk (nothing is).  The compiler's counts start from there, and the
+// head's requests and the first full group's go out back to back.
+__host__ __device__ constexpr int stream_vmcnt(int n) { return (n & 15) | ((n >> 4) << 14) | 0x0F70; }      // gfx9 encoding of s_waitcnt: vmcnt(n), the other counters free
+#define RN_LANDED(n) __builtin_amdgcn_s_waitcnt(stream_vmcnt(n));
 #define RN_LOADG(buf, sv) _Pragma("unroll") for (int d = 0; d < RN_GROUP; d++) { RN_POP(sv, d) RN_LOAD1(buf, sv, d) }
 #define RN_USEG(buf, sv) _Pragma("unroll") for (int d = 0; d < RN_GROUP; d++) RN_USE1(buf, sv, d)
 #define RN_LOADH(buf, sv) _Pragma("unroll") for (int d = 0; d < RN_GROUP - 1; d++) if (d < nHead) { RN_POP(sv, d) RN_LOAD1(buf, sv, d) }
@@ -64,6 +74,7 @@ __device__ __forceinline__ bool stream_nz(float v) { return (__float_as_uint(v) 
     if (nGroups > 0) RN_LOADG(bufA, sA)                                                                                \
     RN_USEH(bufB, sB)                                                                                                  \
     if (nGroups > 0) {                                                                                                 \
+        RN_LANDED(RN_GROUP_LOADS)                                                                                      \
         int g = 0;                                                                                                     \
         for (; g + 2 < nGroups; g += 2) {                                                                              \
             RN_LOADG(bufB, sB)                                                                                         \
@@ -78,7 +89,8 @@ __device__ __forceinline__ bool stream_nz(float v) { return (__float_as_uint(v) 
         } else {                                                                                                       \
             RN_USEG(bufA, sA)                                                                                          \
         }                                                                                                              \
-    }
+    }                                                                                                                  \
+    RN_LANDED(0)
 template <typename T, typename VT, int VPL, int NL, int D, int NR>
 __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *sh_y, const T *sh_y2, const unsigned long long *sh_nz, int skip, int span0, int span1, int G, int ny,
                                             int spanSlots, const int (&off)[NL], const int (&cj)[NL], const T (&msk)[NL], T (&part)[NL][VPL],
@@ -96,6 +108,7 @@ __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *
     for (int j = 0; j < NL; j++) offB[j] = (unsigned)off[j] * 16u;
 #define RN_POP(sv, d) { sv[d] = __builtin_amdgcn_readfirstlane(cb + __builtin_ctzll(mf)); mf &= mf - 1ull; }
 #define RN_GROUP D
+#define RN_GROUP_LOADS (D * NL)
 #define RN_LOAD1(buf, sv, d)                                                                                           \
     _Pragma("unroll") for (int j = 0; j < NL; j++)                                                                     \
         buf[d][j] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (size_t)sv[d] * spanBytes + offB[j]));
@@ -155,6 +168,7 @@ __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *
         }
     }
 #undef RN_GROUP
+#undef RN_GROUP_LOADS
 #undef RN_POP
 #undef RN_LOAD1
 #undef RN_USE1
@@ -191,6 +205,7 @@ __device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, cons
     const unsigned spanBytes = (unsigned)spanSlots * 16u;
     const unsigned offB[2] = {(unsigned)off[0] * 16u, (unsigned)off[1] * 16u};
 #define RN_GROUP DU
+#define RN_GROUP_LOADS DU
 #define RN_POP(sv, d) { sv[d] = __builtin_amdgcn_readfirstlane(ub + __builtin_ctzll(mf)); mf &= mf - 1ull; }
 #define RN_LOAD1(buf, sv, d) buf[d] = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (size_t)(sv[d] >> 1) * spanBytes + ((sv[d] & 1) ? offB[1] : offB[0])));
 #define RN_USE1(buf, sv, d) {                                                                                          \
@@ -246,6 +261,7 @@ __device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, cons
         }
     }
 #undef RN_GROUP
+#undef RN_GROUP_LOADS
 #undef RN_POP
 #undef RN_LOAD1
 #undef RN_USE1
@@ -254,6 +270,7 @@ __device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, cons
 #undef RN_LOADH
 #undef RN_USEH
 #undef RN_STREAM_GROUPS
+#undef RN_LANDED
 }
 // Which slots of a span thread `tid` owns: off[j] (clamped to a slot of the span for idle threads), their columns cj[j] inside the span, msk[j] = 1
 // for an owned slot.  Slots tid, tid + 512, ...; NL = 2 with an even G: slot tid of each HALF of the span (stream_walk_half).
