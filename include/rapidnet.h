@@ -413,6 +413,48 @@ int rn_shift_warm_start(rn_ctx *ctx, int rootChild);
 int rn_set_shift_map(rn_ctx *ctx, size_t nodes, const int *map /* [nodes] or NULL */);
 int rn_get_shift_map(rn_ctx *ctx, int rootChild, size_t nodes, int *map /* [nodes] */);
 
+/* ---- the dual Lipschitz constant, estimated on the device ---------------------------------------------------------------------------
+ * APG's step size must be margin / L with L = lambda_max(M), M = K H^-1 K' the dual Hessian of the operators the context holds.  The
+ * reference has no counterpart: its stepSize is a figure computed offline (MATLAB) and written into the configuration file.  Here the
+ * context estimates L of what it HOLDS -- caller-owned blocks, re-weighted probabilities and fp32-stored blocks included -- by power
+ * iteration over its Hessian sweep (the linear map of rn_compute_hessian_oracle).  With w_0 = the start vector, for k = 1 .. maxIterations:
+ *     s = <w, w> ;  t = <v, w> (k >= 2) ;  v = w / sqrt(s) ;  w = M v
+ * and record j (j = 1 .. iterations run), formed from the w of application j: NORM = sqrt(s) (<= lambda_max), RAYLEIGH = |t| (<= NORM),
+ * RESIDUAL = sqrt(max(s - t^2, 0)) / sqrt(s) = |w - rho v| / |w| for the unit v.  `out` is the last record plus the number of
+ * applications run; `history` (may be NULL) receives all records.  The estimate is a LOWER bound of L -- hence the margin of the step
+ * rule -- and RESIDUAL says how far the iteration is from an eigenvector; a tree with single-child stages can make 40 iterations undershoot.
+ * Start vector: startXi / startPsi in the layout of rn_set(RN_BUF_XI / RN_BUF_PSI), or both NULL for the library's own: the element in
+ *   column c (c < 2 nx: xi; 2 nx + j: psi) of the node with index g in the WHOLE tree is, with i = g (2 nx + nu) + c in unsigned 64-bit
+ *   arithmetic,  x = seed + (i + 1) 0x9E3779B97F4A7C15;  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;
+ *   x ^= x >> 31;  value = (double)(x >> 11) 2^-52 - 1,  rounded to the context's type: a shard starts from the one-GPU context's vector.
+ * Arithmetic: sums in fp64 (fp32 contexts too), fixed order, no atomics: two calls return the same bits.  No host synchronisation between
+ *   iterations: tol == 0 runs exactly maxIterations applications with one synchronisation at the end; tol > 0 reads the latest record every
+ *   checkEvery iterations (<= 0: 20) and stops when RESIDUAL <= tol.  s - t^2 is formed in fp64, so RESIDUAL has a cancellation floor near
+ *   sqrt(n 2^-53): a tolerance below about 1e-6 cannot be met.
+ * State: a call between any two entry points leaves every RN_BUF_* buffer, the L-BFGS memory, the history and the batch state untouched;
+ *   it needs rn_factor_step only (not the affine terms), under every algorithm, operator mode and storage type.  The first call allocates
+ *   buffers of its own (about 2 (2 nx + nu) + nx + nu + nv reals per node, rn_device_memory_info) and keeps them; a context that never asks
+ *   allocates and launches nothing.  Sharded contexts (rn_create_sharded): every rank calls; all ranks hold the same bits.
+ * Errors: RN_E_STATE before rn_factor_step, after a batch that failed half-way (until rn_apg_reset), on a shard of several ranks without a
+ *   communicator; RN_E_ARG for maxIterations < 1, a negative or NaN tol, exactly one start pointer, a NULL out, or a start vector whose
+ *   norm is 0 or not finite (seen in the first record).
+ * rn_get_lipschitz: the record held and whether it is stale: rn_factor_step, rn_set_operator, rn_set_operators[_device],
+ *   rn_set_operator_storage and rn_set_tree_data[_device] with probabilities mark it stale (bounds, tree errors alone, forecasts and the
+ *   state do not enter M).  RN_E_STATE if none was ever computed. */
+enum { RN_LIP_NORM = 0, RN_LIP_RAYLEIGH, RN_LIP_RESIDUAL, RN_LIP_ITERATIONS, RN_LIP_COLS };
+int rn_estimate_lipschitz(rn_ctx *ctx, int maxIterations, double tol, int checkEvery,
+                          const double *startXi /* nodes*2nx or NULL */, const double *startPsi /* nodes*nu or NULL */,
+                          unsigned long long seed, double out[RN_LIP_COLS], double *history /* [maxIterations][3] or NULL */);
+int rn_get_lipschitz(rn_ctx *ctx, double out[RN_LIP_COLS], int *stale);
+/* The step size from the estimate (opt-in).  RN_STEP_FIXED (default): stepSize is rn_set_parameters', nothing is launched.
+ * RN_STEP_LIPSCHITZ: rn_control_action, rn_algorithm_apg, rn_apg_solve and rn_algorithm_global_fbe / rn_algorithm_nama estimate on entry
+ * when no estimate is held or the held one is stale (`iterations` applications, <= 0: 40; the library's start, seed 0) and run with
+ * stepSize = margin / NORM, margin in (0, 1]; the penalties are rn_set_parameters'.  rn_set_parameters' own step size is kept and returns
+ * with RN_STEP_FIXED.  rn_get_step_rule: any pointer may be NULL; stepSizeInForce is what the next iteration would use. */
+enum { RN_STEP_FIXED = 0, RN_STEP_LIPSCHITZ = 1 };
+int rn_set_step_rule(rn_ctx *ctx, int rule, double margin /* (0,1] */, int iterations /* <=0: 40 */);
+int rn_get_step_rule(rn_ctx *ctx, int *rule, double *margin, int *iterations, double *stepSizeInForce);
+
 /* step-wise entry points mirroring the protected methods the reference's known-answer tests call */
 int rn_dual_extrapolation_step(rn_ctx *ctx, double lambda); /* SmpcController.cu:535-557  */
 int rn_solve_step(rn_ctx *ctx);                             /* SmpcController.cu:563-755  */

@@ -27,6 +27,9 @@ PAIR_OFF, PAIR_ON, PAIR_AUTO = 0, 1, 2
 PAIRINGS = {"off": PAIR_OFF, "on": PAIR_ON, "auto": PAIR_AUTO}
 RESTART_OFF, RESTART_GRADIENT = 0, 1   # rn_set_restart
 RESTARTS = {"off": RESTART_OFF, "gradient": RESTART_GRADIENT}
+STEP_FIXED, STEP_LIPSCHITZ = 0, 1       # rn_set_step_rule
+STEP_RULES = {"fixed": STEP_FIXED, "lipschitz": STEP_LIPSCHITZ}
+LIP_COLUMNS = ("norm", "rayleigh", "residual", "iterations")      # rn_estimate_lipschitz, RN_LIP_*
 BOUNDS_SHARED, BOUNDS_PER_STAGE, BOUNDS_PER_NODE = 0, 1, 2      # rn_set_bounds
 BOUNDS = {"shared": BOUNDS_SHARED, "stage": BOUNDS_PER_STAGE, "node": BOUNDS_PER_NODE}
 # include/rapidnet_debug.h, RN_KNOB_*
@@ -61,6 +64,7 @@ SYMBOLS = [
     "rn_plan_report", "rn_plan_report_scenarios", "rn_plan_report_device",
     "rn_plan_quantiles", "rn_plan_quantiles_device", "rn_plan_paths",
     "rn_shift_warm_start", "rn_set_shift_map", "rn_get_shift_map",
+    "rn_estimate_lipschitz", "rn_get_lipschitz", "rn_set_step_rule", "rn_get_step_rule",
 ]
 
 
@@ -271,6 +275,10 @@ def load():
     lib.rn_shift_warm_start.argtypes = [vp, ip]
     lib.rn_set_shift_map.argtypes = [vp, C.c_size_t, dp]
     lib.rn_get_shift_map.argtypes = [vp, ip, C.c_size_t, dp]
+    lib.rn_estimate_lipschitz.argtypes = [vp, ip, C.c_double, ip, dp, dp, C.c_ulonglong, dp, dp]
+    lib.rn_get_lipschitz.argtypes = [vp, dp, C.POINTER(C.c_int)]
+    lib.rn_set_step_rule.argtypes = [vp, ip, C.c_double, ip]
+    lib.rn_get_step_rule.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)]
     _LIB = lib
     return lib
 
@@ -301,7 +309,7 @@ class Solver:
 
     def __init__(self, network, tree, config, precision="f64", device=0, structured=False, rank=0, nranks=1, cut_stage=0,
                  unique_id=None, knobs=None, operator_mode=None, operator_storage="native", sweep_pairing="auto", stop_tolerance=0.0,
-                 stop_check_every=0, restart="off"):
+                 stop_check_every=0, restart="off", step_rule=None):
         """nranks > 1: `tree` is the FULL scenario tree and the context is rank `rank`'s shard of it (rn_create_sharded:
         partition, communicator from `unique_id` -- None = none, the exchange is a test's job --, cut stage, children
         moments); self.nodes is then the LOCAL node count and self.global_nodes maps local -> full-tree node ids.
@@ -357,6 +365,8 @@ class Solver:
             self.setStopTolerance(stop_tolerance, stop_check_every)
         if restart != "off":
             self.setRestart(restart)
+        if step_rule is not None:      # ("lipschitz", or a tuple (rule, margin, iterations); a context that never asks makes no call)
+            self.setStepRule(*((step_rule,) if isinstance(step_rule, str) else tuple(step_rule)))
         for k, v in (knobs or {}).items():
             self.debugSetKnob(k, v)
 
@@ -508,6 +518,48 @@ class Solver:
         m = np.zeros(self._treeNodes(), dtype=np.int32)
         self._check(self.lib.rn_get_shift_map(self.h, int(root_child), m.size, m.ctypes.data))
         return m
+
+    # ---- the dual Lipschitz constant and the step size from it (rn_estimate_lipschitz ...) -----------------------------
+    def estimateLipschitz(self, max_iterations=40, tol=0.0, check_every=0, start=None, seed=0, history=False):
+        """rn_estimate_lipschitz: power iteration over the context's Hessian sweep.  start: None (the library's hashed start of `seed`) or
+        (xi [nodes, 2nx], psi [nodes, nu]) in the layout of set(BUF_XI / BUF_PSI).  Returns dict(norm, rayleigh, residual, iterations) of the last
+        record -- norm is the estimate, a lower bound of lambda_max -- and, with history, "history": [iterations run, 3].  On a shard every
+        rank calls it."""
+        n = int(max_iterations)
+        out = np.zeros(len(LIP_COLUMNS))
+        hist = np.zeros((max(n, 1), 3)) if history else None
+        xi = psi = None
+        if start is not None:
+            xi, psi = _f64(start[0]), _f64(start[1])
+            assert xi.size == self.nodes * 2 * self.nx and psi.size == self.nodes * self.nu
+        self._check(self.lib.rn_estimate_lipschitz(self.h, n, float(tol), int(check_every), xi.ctypes.data if xi is not None else None,
+                                                   psi.ctypes.data if psi is not None else None, int(seed), out.ctypes.data,
+                                                   hist.ctypes.data if history else None))
+        r = dict(zip(LIP_COLUMNS, (float(v) for v in out)))
+        r["iterations"] = int(r["iterations"])
+        if history:
+            r["history"] = hist[: r["iterations"]]
+        return r
+
+    def lipschitz(self):
+        """rn_get_lipschitz: the record held plus "stale" (the operators have changed since: factor step, own blocks, probabilities)"""
+        out, stale = np.zeros(len(LIP_COLUMNS)), C.c_int(0)
+        self._check(self.lib.rn_get_lipschitz(self.h, out.ctypes.data, C.byref(stale)))
+        r = dict(zip(LIP_COLUMNS, (float(v) for v in out)))
+        r["iterations"] = int(r["iterations"])
+        r["stale"] = bool(stale.value)
+        return r
+
+    def setStepRule(self, rule="lipschitz", margin=0.9, iterations=0):
+        """rn_set_step_rule: "fixed" (stepSize as configured) | "lipschitz" (the solves run with margin / norm, estimated on entry when
+        no estimate is held or it is stale; iterations <= 0: 40)"""
+        self._check(self.lib.rn_set_step_rule(self.h, STEP_RULES[rule] if isinstance(rule, str) else int(rule), float(margin), int(iterations)))
+
+    def stepRule(self):
+        """rn_get_step_rule: dict(rule, margin, iterations, step_size_in_force)"""
+        r, m, i, s = C.c_int(0), C.c_double(0), C.c_int(0), C.c_double(0)
+        self._check(self.lib.rn_get_step_rule(self.h, C.byref(r), C.byref(m), C.byref(i), C.byref(s)))
+        return dict(rule={v: k for k, v in STEP_RULES.items()}[r.value], margin=m.value, iterations=i.value, step_size_in_force=s.value)
 
     def dualExtrapolationStep(self, lam):
         self._check(self.lib.rn_dual_extrapolation_step(self.h, float(lam)))

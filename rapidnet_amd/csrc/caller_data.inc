@@ -226,6 +226,7 @@
         RN_CHECK(opsMode != RN_OPS_STRUCTURED, RN_E_STATE, "rn_set_operator: the context was created with RN_OPS_STRUCTURED (no per-node blocks); use RN_OPS_AUTO or RN_OPS_DENSE");
         RN_HIP(hipSetDevice(device));
         if (structured) { if (int rc = materialise_dense()) return rc; }
+        lip_invalidate();
         std::vector<double> blk((size_t)ny * LD);
         if (int rc = download_block(node, blk.data())) return rc;
         for (int c = 0; c < g.cols; c++) for (int r = 0; r < nv; r++) blk[(size_t)(g.c0 + c) * LD + g.r0 + r] = host[r + (size_t)c * nv];
@@ -333,6 +334,7 @@
         for (int i = 0; i < 4; i++) a[i] = CallerArray{op[i], nodes * op_elems(i), "nodes x nv x columns", nullptr};
         if (int rc = check_caller_arrays(what, callerPrec, dev, a, 4)) return rc;
         if (set && structured) { if (int rc = materialise_dense()) return rc; }     // (RN_OPS_AUTO, first block of the caller's: allocates and synchronises, once)
+        if (set) lip_invalidate();
         if (!dev) return pack_staged(set, a);
         pack_launch(set, callerPrec == RN_F64, op, 0, d.nodes);
         RN_HIP(hipGetLastError());
@@ -426,6 +428,7 @@
                 treeCheckPending = false; treeBad = false; treeBadCount = 0; hProbStale = false;
             }
             affine_ready = false; linConstValid = false; aux_dirty = true;      // the affine terms and every control-step constant read p
+            lip_invalidate();      // (the operators carry powers of p_i: a held Lipschitz estimate is the old tree's)
         }
         if ((prob || errD) && cutStage > 0 && nranks > 1 && !lib) moments_set = false;   // sharded by hand: the caller's moments are the old tree's
         return RN_OK;

@@ -111,6 +111,68 @@ __device__ __forceinline__ double fold_dot0(const double *partials, int nblocks)
     return r;
 }
 
+// One step of the power iteration behind rn_estimate_lipschitz (lipschitz.inc): with s = <w, w> and t = <v, w> -- dots 0 and 1 of a k_dots
+// launch over (w, w) and (v, w) -- the kernel writes v = w * (1 / sqrt(s)) and workgroup 0 leaves the record {sqrt(s), |t|,
+// sqrt(max(s - t^2, 0)) / sqrt(s)} in row `row` of the device history table, so the loop around the Hessian sweep needs no host
+// synchronisation.  EVERY workgroup folds the `nblocks` partials of both dots itself, in k_dots_finish's order (fold_dot0's scheme, per
+// column), so s and t are bitwise what a k_dots_finish launch would have left -- or, sharded contexts, reads them from scal[0..1] where
+// that launch and the all-reduce over the ranks have left them.  The element type arrives as a flag (one kernel instead of two, as
+// k_clamp_vec); the reciprocal is rounded to the context's type and the product is the typed one.
+//   cnt = 1 (the first step: no v yet): t = 0;   normalise = 0 (the closing step and the early-stop checks): the record only, grid of 1
+struct PowerArgs {
+    void *v; const void *w;
+    const double *partials; int nblocks, cnt;
+    const double *scal;      // non-null: s and t as reduced over the ranks
+    double *hist; int row;   // row < 0: no record (the first step)
+    long long n;
+    int normalise, f64;
+};
+__device__ __forceinline__ double fold_dot_col(const double *partials, int nblocks, int j) {
+    __shared__ double psh[ELT_THREADS];
+    double s = 0;
+    for (int b = threadIdx.x; b < nblocks; b += ELT_THREADS) s += partials[(size_t)b * DOT_MAX + j];
+    psh[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = ELT_THREADS / 2; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) psh[threadIdx.x] += psh[threadIdx.x + w];
+        __syncthreads();
+    }
+    const double r = psh[0];
+    __syncthreads();
+    return r;
+}
+template <typename T>
+__device__ __forceinline__ void power_scale_body(const PowerArgs &g, double s) {
+    typedef typename VecOf<T>::type VT;
+    constexpr int VN = VecOf<T>::N;
+    T *v = static_cast<T *>(g.v);
+    const T *w = static_cast<const T *>(g.w);
+    const T inv = (T)(1.0 / sqrt(s));
+    const long long nvec = g.n / VN;      // (v and w are allocations of their own: 16-byte aligned)
+    const long long stride = (long long)gridDim.x * ELT_THREADS, gid = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    for (long long i = gid; i < nvec; i += stride) {
+        VT x = reinterpret_cast<const VT *>(w)[i];
+#pragma unroll
+        for (int e = 0; e < VN; e++) x[e] = x[e] * inv;
+        reinterpret_cast<VT *>(v)[i] = x;
+    }
+    for (long long i = nvec * VN + gid; i < g.n; i += stride) v[i] = w[i] * inv;
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void __launch_bounds__(ELT_THREADS) k_power_step(PowerArgs g) {
+    double s, t = 0;
+    if (g.scal) { s = g.scal[0]; if (g.cnt > 1) t = g.scal[1]; }
+    else { s = fold_dot_col(g.partials, g.nblocks, 0); if (g.cnt > 1) t = fold_dot_col(g.partials, g.nblocks, 1); }
+    if (g.row >= 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+        const double nrm = sqrt(s), gap = s - t * t;
+        g.hist[(size_t)g.row * 3 + 0] = nrm;
+        g.hist[(size_t)g.row * 3 + 1] = fabs(t);
+        g.hist[(size_t)g.row * 3 + 2] = sqrt(gap > 0 ? gap : 0.0) / nrm;
+    }
+    if (!g.normalise) return;
+    if (g.f64) power_scale_body<double>(g, s); else power_scale_body<float>(g, s);
+}
+
 // L-BFGS two-loop updates (SmpcController::twoLoopRecursionLbfgs, SmpcController.cu:1175-1229); scal[0] holds the
 // dot product just reduced by k_dots_finish, alphaArr the first loop's coefficients.
 //   mode 0: alpha_c = rho_c <S_c, dir> ; dir -= alpha_c Y_c         (vec = Y_c)

@@ -51,7 +51,7 @@
             DA(d_prevY, n) DA(d_g, n) DA(d_gPrev, n) DA(d_dir, n) DA(d_hxDir, n) DA(d_S, n) DA(d_Yv, n)
             DA(d_xdir, N_ * d.nx) DA(d_udir, N_ * d.nu)
             DA(d_matS, (size_t)(bufferSize + 1) * n) DA(d_matY, (size_t)(bufferSize + 1) * n)
-            DA(d_zero, N_ * (size_t)std::max(d.nu, std::max(d.nx, d.nv)))
+            if (!d_zero) { DA(d_zero, N_ * (size_t)std::max(d.nu, std::max(d.nx, d.nv))) }      // (an earlier rn_estimate_lipschitz may have made it)
             valueBlocks = std::min((d.nodes + VALUE_TILE - 1) / VALUE_TILE, 1024);
             DA(d_dotPartials, (size_t)ELT_MAX_BLOCKS * DOT_MAX) DA(d_dotPartials2, (size_t)ELT_MAX_BLOCKS * DOT_MAX) DA(d_valPartials, (size_t)valueBlocks * DOT_MAX)
             DA(d_scal, FBE_SCALARS) DA(d_alphaArr, 64)
@@ -574,6 +574,7 @@
         RN_CHECK(maxIt >= 0, RN_E_ARG, "rn_algorithm_global_fbe / rn_algorithm_nama: negative iteration count");
         RN_FBE_READY("rn_algorithm_global_fbe / rn_algorithm_nama")
         if (int rc = fbe_reset()) return rc;
+        if (int rc = step_rule_on_entry()) return rc;
         if (maxIt > infHistCap) {          // 1 024 iterations are there from rn_set_algorithm on; a longer loop gets a larger array (the old one stays until rn_destroy)
             const int cap = std::max(1024, 2 * maxIt);
             if (int rc = dalloc(&d_infHist, (size_t)4 * cap)) return rc;

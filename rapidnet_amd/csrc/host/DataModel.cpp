@@ -217,6 +217,26 @@ SmpcConfiguration::SmpcConfiguration(string pathToFile) {
         if (every < 0) throw std::logic_error("controller configuration: stopCheckEvery must be >= 0");
         stopCheckEvery = (uint_t)every;
     }
+    // ... and where the step size comes from (absent = "fixed": the file's own "stepSize", the reference's offline figure; "lipschitz":
+    // stepSizeMargin / the estimate of the dual Lipschitz constant the engine makes of the operators it holds -- rapidnet.h, rn_set_step_rule)
+    stepSizeRule = "fixed";
+    if (doc.HasMember("stepSizeRule")) {
+        _ASSERT(doc["stepSizeRule"].IsString());
+        stepSizeRule = doc["stepSizeRule"].str;
+        if (stepSizeRule != "fixed" && stepSizeRule != "lipschitz")
+            throw std::logic_error("controller configuration: stepSizeRule must be \"fixed\" or \"lipschitz\" (got \"" + stepSizeRule + "\")");
+    }
+    stepSizeMargin = 0.9;
+    if (doc.HasMember("stepSizeMargin")) {
+        stepSizeMargin = scalarReal(doc, "stepSizeMargin");
+        if (!(stepSizeMargin > 0 && stepSizeMargin <= 1)) throw std::logic_error("controller configuration: stepSizeMargin must lie in (0, 1]");
+    }
+    lipschitzIterations = 0;
+    if (doc.HasMember("lipschitzIterations")) {
+        const real_t it = scalarReal(doc, "lipschitzIterations");
+        if (!(it >= 1) || it != std::floor(it) || it > 1e6) throw std::logic_error("controller configuration: lipschitzIterations must be a whole number >= 1");
+        lipschitzIterations = (uint_t)it;
+    }
     lbfgsBufferSize = scalarInt(doc, "lbfgsBufferSize");
     pathToConfiguration = pathToFile;
     // relative paths in the configuration are relative to the configuration file's directory when they do not

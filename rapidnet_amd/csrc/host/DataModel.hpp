@@ -143,6 +143,12 @@ public:
     // duals of the previous step where they are -- Engine.hpp, setWarmStart) or "shift" (moved one stage toward the root first -- Engine.hpp,
     // shiftWarmStart; SmpcController::controlAction calls it before every step but the first)
     string getWarmStart() { return warmStart; }
+    // "stepSizeRule" (optional key, not in the reference's files): "fixed" (default: the file's "stepSize", the reference's offline figure) or
+    // "lipschitz" (stepSizeMargin, default 0.9, over the engine's own estimate of the dual Lipschitz constant, lipschitzIterations power
+    // sweeps, default 0 = the library's 40) -- Engine.hpp, setStepRule
+    string getStepSizeRule() { return stepSizeRule; }
+    real_t getStepSizeMargin() { return stepSizeMargin; }
+    uint_t getLipschitzIterations() { return lipschitzIterations; }
     void setCurrentState();     // re-read from the configuration file (SmpcConfiguration.cu:240-256)
     void setPreviousControl();  // :261-277
     void setPreviousDemand();   // :283-299
@@ -152,7 +158,9 @@ public:
     ~SmpcConfiguration() {}
 
 private:
-    uint_t NX, NU, ND, NV, lbfgsBufferSize, maxIteration, stopCheckEvery;
+    uint_t NX, NU, ND, NV, lbfgsBufferSize, maxIteration, stopCheckEvery, lipschitzIterations;
+    real_t stepSizeMargin;
+    string stepSizeRule;
     std::vector<real_t> matL, matLhat, matCostW, matDiagPrecnd, currentX, prevU, prevDemand;
     real_t penaltyStateX, penaltySafetyX, stepSize, weightPrice, weightSmooth, weightSafety, stopTolerance;
     string pathToConfiguration, pathToNetwork, pathToScenarioTree, pathToForecaster, algorithmName, operatorMode, operatorStorage, sweepPairing, momentumRestart, warmStart;

@@ -184,6 +184,8 @@ void Engine::create(int precision, int device, int operatorMode, int rank, int n
         check(rn_set_stop_tolerance(ctx, ptrMySmpcConfig->getStopTolerance(), (int)ptrMySmpcConfig->getStopCheckEvery()), "rn_set_stop_tolerance");
     if (ptrMySmpcConfig->getMomentumRestart() == "gradient") check(rn_set_restart(ctx, RN_RESTART_GRADIENT), "rn_set_restart");
     if (ptrMySmpcConfig->getWarmStart() != "off") check(rn_set_warm_start(ctx, 1), "rn_set_warm_start");      // "keep" | "shift"
+    if (ptrMySmpcConfig->getStepSizeRule() == "lipschitz")   // (a file without the key makes exactly the calls it always made)
+        check(rn_set_step_rule(ctx, RN_STEP_LIPSCHITZ, ptrMySmpcConfig->getStepSizeMargin(), (int)ptrMySmpcConfig->getLipschitzIterations()), "rn_set_step_rule");
     // SmpcController::allocateApgAlgorithm (SmpcController.cu:124-151): per-iteration storage for maxIterations, allocated once
     check(rn_reserve_iterations(ctx, (int)ptrMySmpcConfig->getMaxIterations()), "rn_reserve_iterations");
     if (!apgFlag)   // SmpcController::allocateGlobalFbeAlgorithm / allocateNamaAlgorithm / allocateLbfgsBuffer (SmpcController.cu:234-330)
@@ -244,6 +246,35 @@ void Engine::calculateMatLandMatLhat() {
         throw std::logic_error("calculateMatLandMatLhat: null space of E has dimension " + std::to_string(nu - rank) + ", the configuration says nv = " +
                                std::to_string(ptrMySmpcConfig->getNV()));
     useComputedL = true;
+}
+Engine::LipschitzEstimate Engine::estimateLipschitz(int maxIterations, real_t tol, int checkEvery, const std::vector<real_t> &start, unsigned long long seed, bool history) {
+    LipschitzEstimate e;
+    const size_t nodes = getNumLocalNodes(), nxi = nodes * 2 * ptrMySmpcConfig->getNX(), npsi = nodes * ptrMySmpcConfig->getNU();
+    if (!start.empty() && start.size() != nxi + npsi) throw std::invalid_argument("estimateLipschitz: the start vector holds xi [nodes][2nx] followed by psi [nodes][nu]");
+    if (history) e.history.assign((size_t)(maxIterations > 0 ? maxIterations : 0) * 3, 0.0);
+    double out[RN_LIP_COLS] = {0, 0, 0, 0};
+    check(rn_estimate_lipschitz(ctx, maxIterations, tol, checkEvery, start.empty() ? nullptr : start.data(), start.empty() ? nullptr : start.data() + nxi, seed, out,
+                                history ? e.history.data() : nullptr), "rn_estimate_lipschitz");
+    e.norm = out[RN_LIP_NORM]; e.rayleigh = out[RN_LIP_RAYLEIGH]; e.residual = out[RN_LIP_RESIDUAL]; e.iterations = (uint_t)out[RN_LIP_ITERATIONS];
+    if (history) e.history.resize((size_t)e.iterations * 3);
+    return e;
+}
+bool Engine::getLipschitz(LipschitzEstimate &e) {
+    double out[RN_LIP_COLS] = {0, 0, 0, 0};
+    int stale = 0;
+    const int rc = rn_get_lipschitz(ctx, out, &stale);
+    if (rc == RN_E_STATE) return false;
+    check(rc, "rn_get_lipschitz");
+    e.norm = out[RN_LIP_NORM]; e.rayleigh = out[RN_LIP_RAYLEIGH]; e.residual = out[RN_LIP_RESIDUAL]; e.iterations = (uint_t)out[RN_LIP_ITERATIONS];
+    e.stale = stale != 0;
+    e.history.clear();
+    return true;
+}
+void Engine::setStepRule(int rule, real_t margin, int iterations) { check(rn_set_step_rule(ctx, rule, margin, iterations), "rn_set_step_rule"); }
+int Engine::getStepRule(real_t *margin, int *iterations, real_t *stepSizeInForce) {
+    int rule = RN_STEP_FIXED;
+    check(rn_get_step_rule(ctx, &rule, margin, iterations, stepSizeInForce), "rn_get_step_rule");
+    return rule;
 }
 void Engine::setWarmStart(bool on) { check(rn_set_warm_start(ctx, on ? 1 : 0), "rn_set_warm_start"); }
 void Engine::shiftWarmStart(int rootChild) { check(rn_shift_warm_start(ctx, rootChild), "rn_shift_warm_start"); }

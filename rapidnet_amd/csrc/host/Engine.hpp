@@ -137,6 +137,25 @@ public:
     void shiftWarmStart(int rootChild = -1);
     void setShiftMap(const std::vector<int> &map);
     void getShiftMap(int rootChild, std::vector<int> &map);
+    // The dual Lipschitz constant of the operators the engine holds, by power sweeps on the device (rapidnet.h, rn_estimate_lipschitz; the reference
+    // takes stepSize from an offline MATLAB figure in the configuration file).  The estimate is a LOWER bound of lambda_max -- hence the margin of
+    // the step rule; residual says how far the iteration is from an eigenvector.  After factorStep(); caller-owned blocks, new probabilities and a
+    // new factor step make the held estimate stale (getLipschitz).  start: empty for the library's own start vector of `seed`, or xi [nodes][2nx]
+    // followed by psi [nodes][nu].  On a sharded engine every rank calls it.
+    struct LipschitzEstimate {
+        real_t norm = 0, rayleigh = 0, residual = 0;
+        uint_t iterations = 0;
+        bool stale = false;
+        std::vector<real_t> history;      // [iterations][3] when asked for
+    };
+    LipschitzEstimate estimateLipschitz(int maxIterations = 40, real_t tol = 0, int checkEvery = 0, const std::vector<real_t> &start = std::vector<real_t>(),
+                                        unsigned long long seed = 0, bool history = false);
+    bool getLipschitz(LipschitzEstimate &held);      // false: none was computed yet
+    // RN_STEP_FIXED: the configuration's stepSize; RN_STEP_LIPSCHITZ: margin / norm, estimated on entry of a solve when no estimate is held or it is
+    // stale (rapidnet.h, rn_set_step_rule).  The constructors take the rule from the configuration file's optional "stepSizeRule" /
+    // "stepSizeMargin" / "lipschitzIterations" keys (absent: fixed, the reference's behaviour).
+    void setStepRule(int rule, real_t margin = 0.9, int iterations = 0);
+    int getStepRule(real_t *margin = nullptr, int *iterations = nullptr, real_t *stepSizeInForce = nullptr);
     ScenarioTree *getScenarioTree() { return ptrMyScenarioTree; }
     DwnNetwork *getDwnNetwork() { return ptrMyNetwork; }
     SmpcConfiguration *getSmpcConfiguration() { return ptrMySmpcConfig; }

@@ -148,9 +148,17 @@ uint_t SmpcController::writePlanBands(std::fstream &out) {
 void SmpcController::shiftBeforeStep() {
     if (controlSteps > 0 && ptrMySmpcConfig->getWarmStart() == "shift") ptrMyEngine->shiftWarmStart(-1);
 }
+void SmpcController::estimateBeforeStep() {
+    if (ptrMySmpcConfig->getStepSizeRule() != "lipschitz") return;
+    Engine::LipschitzEstimate held;
+    if (ptrMyEngine->getLipschitz(held)) return;      // (a stale one is renewed by the control step itself: its buffers exist)
+    const int it = (int)ptrMySmpcConfig->getLipschitzIterations();
+    ptrMyEngine->estimateLipschitz(it > 0 ? it : 40);
+}
 uint_t SmpcController::controlAction(real_t *u) {
     if (!factorStepFlag) { ptrMyEngine->factorStep(); factorStepFlag = true; }
     shiftBeforeStep();
+    estimateBeforeStep();
     size_t before[4];
     check(rn_device_memory_info(ptrMyEngine->getContext(), before), "rn_device_memory_info");
     const int rc = rn_control_action(ptrMyEngine->getContext(), ptrMySmpcConfig->getCurrentX(), ptrMySmpcConfig->getPrevU(),
@@ -168,6 +176,7 @@ uint_t SmpcController::controlAction(std::fstream &out) {
     const uint_t nu = ptrMySmpcConfig->getNU();
     std::vector<real_t> u(nu);
     shiftBeforeStep();
+    estimateBeforeStep();
     size_t before[4];
     check(rn_device_memory_info(ptrMyEngine->getContext(), before), "rn_device_memory_info");
     const int rc = rn_control_action(ptrMyEngine->getContext(), ptrMySmpcConfig->getCurrentX(), ptrMySmpcConfig->getPrevU(),

@@ -41,6 +41,11 @@ public:
     // "warmStart": "shift" both controlAction forms call it themselves before every step but the first -- in front of their leak check's
     // window, since the first shift allocates its index arrays and keeps them -- along the root's most probable child.
     void shiftWarmStart(int rootChild = -1) { ptrMyEngine->shiftWarmStart(rootChild); }
+    // The step size the next iteration would use: the configuration's "stepSize", or -- "stepSizeRule": "lipschitz" -- stepSizeMargin over the
+    // engine's estimate of the dual Lipschitz constant (Engine::setStepRule, rapidnet.h rn_set_step_rule).  With the rule both controlAction forms
+    // make the FIRST estimate themselves, in front of their leak check's window (it allocates its vectors and keeps them); a stale estimate --
+    // new probabilities, blocks of the caller's -- is renewed inside the control step, in the buffers it has.
+    real_t getStepSizeInForce() { real_t s = 0; ptrMyEngine->getStepRule(nullptr, nullptr, &s); return s; }
     void moveForewardInTime();                              // :1679-1716
     // in-built simulator of moveForewardInTime: false (default) = the reference as written, x+ = x + B u (its disturbance
     // term lands in the x of node 0 instead of the state update, :1695); true = x+ = x + e_0 + B u (DwnNetwork.cuh:41-57)
@@ -128,6 +133,7 @@ protected:
     PlanBands planBands;
     uint_t controlSteps = 0;      // control steps solved so far ("warmStart": "shift" moves the duals before every one but the first)
     void shiftBeforeStep();
+    void estimateBeforeStep();
 };
 
 #endif

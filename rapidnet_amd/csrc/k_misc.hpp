@@ -410,8 +410,12 @@ __global__ void __launch_bounds__(AFF_THREADS) k_affine_beta(AffineArgs<T> a) {
 // small utilities ------------------------------------------------------------------------------------
 // (one workgroup each, once per control step; the columns are requested eight at a time -- one at a time the loop was a chain of
 //  `cols` dependent round trips, 35-50 us for a 63 x 114 matrix -- and added in the same order as before)
+// k_bw0: the element type arrives as a flag and not as a template parameter (one kernel instead of two, as k_clamp_vec below: one workgroup once
+// per control step); the products and the order of the sums are the typed ones, bit for bit
 template <typename T>
-__global__ void k_bw0(const T *__restrict__ B, int nx, int nu, const T *__restrict__ prevU, const T *__restrict__ prevUhat, T *__restrict__ bw0) {   // bw0 = B (prevU - prevUhat)
+__device__ __forceinline__ void bw0_body(const void *B_, int nx, int nu, const void *prevU_, const void *prevUhat_, void *bw0_) {   // bw0 = B (prevU - prevUhat)
+    const T *__restrict__ B = static_cast<const T *>(B_), *__restrict__ prevU = static_cast<const T *>(prevU_), *__restrict__ prevUhat = static_cast<const T *>(prevUhat_);
+    T *__restrict__ bw0 = static_cast<T *>(bw0_);
     for (int r = threadIdx.x; r < nx; r += blockDim.x) {
         T s = 0;
         for (int j0 = 0; j0 < nu; j0 += 8) {
@@ -423,6 +427,10 @@ __global__ void k_bw0(const T *__restrict__ B, int nx, int nu, const T *__restri
         }
         bw0[r] = s;
     }
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void k_bw0(const void *B, int nx, int nu, const void *prevU, const void *prevUhat, void *bw0, int f64) {
+    if (f64) bw0_body<double>(B, nx, nu, prevU, prevUhat, bw0); else bw0_body<float>(B, nx, nu, prevU, prevUhat, bw0);
 }
 template <typename T>
 __global__ void k_gemv_small(const T *__restrict__ M, int rows, int cols, const T *__restrict__ x, T *__restrict__ y) {   // y = M x, one block

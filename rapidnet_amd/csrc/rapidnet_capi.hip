@@ -52,6 +52,8 @@
 #endif
 #ifndef RN_OPT_LOCAL_MIN
 #define RN_OPT_LOCAL_MIN 16   // shortest rn_apg_iterate batch that takes the optimistic single-GPU path
+#define RN_LIP_CHECK_EVERY 20     // rn_estimate_lipschitz: iterations between two looks at the residual when the caller names none
+#define RN_LIP_RULE_ITERATIONS 40 // rn_set_step_rule: applications per estimate when the caller names none
 #define RN_STOP_CHECK_EVERY 20   // rn_apg_solve / rn_set_stop_tolerance: iterations per batch when the caller names none
 #endif
 #ifndef RN_OPT_BACKOFF
@@ -261,6 +263,10 @@ struct CtxBase {
     virtual int shift_warm_start(int) = 0;
     virtual int set_shift_map(size_t, const int *) = 0;
     virtual int get_shift_map(int, size_t, int *) = 0;
+    virtual int estimate_lipschitz(int, double, int, const double *, const double *, unsigned long long, double *, double *) = 0;
+    virtual int get_lipschitz(double *, int *) = 0;
+    virtual int set_step_rule(int, double, int) = 0;
+    virtual int get_step_rule(int *, double *, int *, double *) = 0;
 };
 
 // ---- in-process stand-in for the communicator (rn_debug_local_group_*): `n` contexts of one process, one host thread each ----
@@ -1025,6 +1031,7 @@ struct Ctx : CtxBase {
         RN_HIP(hipMemsetAsync(d_my, 0, (size_t)d.nodes * 2 * nv * sizeof(T), stream));   // structured mode never writes m1
         if (int rc = launch_expand()) return rc;
         factored = true;
+        lip_invalidate();
         if (int rc = refresh_bounds_copies()) return rc;
         RN_HIP(hipStreamSynchronize(stream));
         return RN_OK;
@@ -1107,7 +1114,7 @@ struct Ctx : CtxBase {
     }
     int set_parameters(double step, double px, double pxs) override {
         RN_CHECK(step > 0 && std::isfinite(step), RN_E_ARG, "rn_set_parameters: stepSize must be positive");
-        stepSize = step; penX = px; penXs = pxs;
+        stepFixed = step; apply_step_size(step); penX = px; penXs = pxs;      // (under RN_STEP_LIPSCHITZ the next solve replaces the step size on entry)
         return RN_OK;
     }
 
@@ -1758,6 +1765,7 @@ struct Ctx : CtxBase {
     // what rn_algorithm_apg and rn_control_action run after their reset: one batch of maxIt iterations -- today's path, untouched -- unless
     // rn_set_stop_tolerance named a tolerance
     int apg_run(int maxIt, double *primalInfs) override {
+        if (stepRule != RN_STEP_FIXED) { RN_CHECK(factored && affine_ready, RN_E_STATE, "rn_apg_iterate before the factor step / affine terms"); if (int rc = step_rule_on_entry()) return rc; }
         if (stopTol > 0 || restartMode == RN_RESTART_GRADIENT) {   // (restart without a tolerance: batches of stopEvery, never stopping early)
             RN_CHECK(factored && affine_ready, RN_E_STATE, "rn_apg_iterate before the factor step / affine terms");
             RN_CHECK(maxIt >= 0, RN_E_ARG, "rn_apg_iterate: negative iteration count");
@@ -1780,6 +1788,7 @@ struct Ctx : CtxBase {
         RN_CHECK(factored && affine_ready, RN_E_STATE, "rn_apg_solve before the factor step / affine terms");
         *iterationsRun = 0;
         if (int rc = apg_reset()) return rc;
+        if (int rc = step_rule_on_entry()) return rc;
         const int rc = solve_loop(maxIt, tol, every > 0 ? every : RN_STOP_CHECK_EVERY, primalInfs);
         *iterationsRun = (int)lastSolve[0];
         return rc;
@@ -2050,6 +2059,7 @@ struct Ctx : CtxBase {
 
     // ---- the warm start shifted one stage toward the root of the scenario tree --------------------------------
 #include "shift_warm_start.inc"
+#include "lipschitz.inc"
 
     // ---- multi-GPU ---------------------------------------------------------------------------------------
     // The communicator of this context.  ncclCommInitRank blocks until every rank of the id has arrived -- for ever if one never does.
@@ -2240,6 +2250,7 @@ struct Ctx : CtxBase {
         RN_CHECK(!factored, RN_E_STATE, "rn_set_operator_storage must precede rn_factor_step");
         storeReq = storage;
         block_layout();
+        lip_invalidate();
         return RN_OK;
     }
     int set_sweep_pairing(int mode) override {
@@ -2374,6 +2385,12 @@ int rn_plan_paths(rn_ctx *ctx, int which, size_t leaves, double *out, int *leafN
 int rn_shift_warm_start(rn_ctx *ctx, int rootChild) { RN_GUARD(ctx); return ctx->impl->shift_warm_start(rootChild); }
 int rn_set_shift_map(rn_ctx *ctx, size_t nodes, const int *map) { RN_GUARD(ctx); return ctx->impl->set_shift_map(nodes, map); }
 int rn_get_shift_map(rn_ctx *ctx, int rootChild, size_t nodes, int *map) { RN_GUARD(ctx); return ctx->impl->get_shift_map(rootChild, nodes, map); }
+int rn_estimate_lipschitz(rn_ctx *ctx, int maxIterations, double tol, int checkEvery, const double *startXi, const double *startPsi, unsigned long long seed, double *out, double *history) {
+    RN_GUARD(ctx); return ctx->impl->estimate_lipschitz(maxIterations, tol, checkEvery, startXi, startPsi, seed, out, history);
+}
+int rn_get_lipschitz(rn_ctx *ctx, double *out, int *stale) { RN_GUARD(ctx); return ctx->impl->get_lipschitz(out, stale); }
+int rn_set_step_rule(rn_ctx *ctx, int rule, double margin, int iterations) { RN_GUARD(ctx); return ctx->impl->set_step_rule(rule, margin, iterations); }
+int rn_get_step_rule(rn_ctx *ctx, int *rule, double *margin, int *iterations, double *inForce) { RN_GUARD(ctx); return ctx->impl->get_step_rule(rule, margin, iterations, inForce); }
 int rn_set_uncertainty(rn_ctx *ctx, int dflag, int pflag, double w) { RN_GUARD(ctx); return ctx->impl->set_uncertainty(dflag, pflag, w); }
 int rn_update_state_control(rn_ctx *ctx, const double *x, const double *u, const double *dm) { RN_GUARD(ctx); return ctx->impl->update_state_control(x, u, dm); }
 int rn_eliminate_input_disturbance_coupling(rn_ctx *ctx, const double *dh, const double *ah) { RN_GUARD(ctx); return ctx->impl->eliminate(dh, ah); }

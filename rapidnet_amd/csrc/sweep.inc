@@ -576,7 +576,12 @@
     // sweep always leaves them (d_xdir, d_udir, d_hxDir).  Bitwise the results of two launch_sweep calls.
     // batch: the rn_apg_iterate batch this sweep is an iteration of (nullptr: none -- the sweep then reads and writes a batch of its own, in which
     // every flag is false)
-    int launch_sweep(Batch *batch, int phase = 0, const T *hessianInput = nullptr, bool primalOut = true, const T *hessianInput2 = nullptr) {
+    // hessOut (with hessianInput, no pair): the Hessian sweep leaves x, u, H * dir and v in the caller's buffers instead of d_xdir, d_udir,
+    // d_hxDir and d_v, and does not run the once-per-control-step refresh (lipschitz.inc: a context without FBE buffers, at any point
+    // between two entry points)
+    struct HessOut { T *x, *u, *hx, *v; };
+    int launch_sweep(Batch *batch, int phase = 0, const T *hessianInput = nullptr, bool primalOut = true, const T *hessianInput2 = nullptr, const HessOut *hessOut = nullptr) {
+        RN_CHECK(!hessOut || (hessianInput && !hessianInput2 && primalOut), RN_E_STATE, "launch_sweep: an output override belongs to a single Hessian sweep");
         Batch none{};
         Batch &bt = batch ? *batch : none;
         SweepArgs<T> a = sweep_args(bt);
@@ -588,6 +593,7 @@
             a.beta = d_zero; a.uhat = d_zero; a.e = d_zero; a.eb = d_zero; a.bw0 = d_zero;
             a.curX = d_zero; a.prevU = d_zero; a.prevUhat = d_zero;
             a.x = d_xdir; a.u = d_udir; a.hx = d_hxDir;
+            if (hessOut) { a.x = hessOut->x; a.u = hessOut->u; a.hx = hessOut->hx; a.v = hessOut->v; }
         }
         const bool pair = hessianInput2 != nullptr;
         if (pair) {
@@ -604,9 +610,11 @@
             a.peer = h_peer; a.peerSeq = peerSeq; a.peerTail = (bt.pendingFin && bt.carry_tail()) ? 1 : 0;
         }
         // (1) all per-node mat-vecs of the backward sweep in one streaming launch
-        if (aux_dirty) {   // iteration-invariant pieces of the forward sweep (once per control step)
+        // (a Hessian sweep with outputs of its own -- the Lipschitz estimate -- reads none of them and may run before the affine terms exist: the
+        //  refresh stays with the first sweep that needs it)
+        if (aux_dirty && !hessOut) {   // iteration-invariant pieces of the forward sweep (once per control step)
             launch_gemm<EPI_Z>(d_Bp, d.nx, d.nu, d_uhat, d.nu, d_eb, d.nx, d_e, d.nx);            // eb_i = e_i + B uhat_i
-            hipLaunchKernelGGL(k_bw0<T>, dim3(1), dim3(128), 0, stream, d_B, d.nx, d.nu, d_prevU, d_prevUhat, d_bw0);
+            hipLaunchKernelGGL(k_bw0<>, dim3(1), dim3(128), 0, stream, (const void *)d_B, d.nx, d.nu, (const void *)d_prevU, (const void *)d_prevUhat, (void *)d_bw0, sizeof(T) == 8 ? 1 : 0);
             aux_dirty = false;
             linConstValid = false;      // (the affine terms may have changed: beta)
         }
