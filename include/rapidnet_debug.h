@@ -95,6 +95,17 @@ int rn_debug_stream_live(rn_ctx *ctx, long long out[4]);
  * span and the figures are rn_debug_stream_live's first two with G.  Same synchronisation, same errors. */
 int rn_debug_stream_units(rn_ctx *ctx, long long out[3]);
 
+/* The product of k_stream_gemv alone, for a test that holds it to a GEMV: runs ONLY the streaming launch, with the arguments rn_solve_step would
+ * give it on this context at the accelerated dual as it stands (what RN_BUF_ACC_* shows) -- the same instantiation, split, skip and half-span
+ * choices as a sweep -- synchronises and copies out, widened to double: my [nodes][2 nv] = [m1_i; m2_i] = A_i w_i (for the blocks of a split last
+ * round: the partial of the first workgroup, columns [0, splitSpanHalf * G)); my2 [nodes - splitFirst][2 nv], the second workgroups' partials
+ * (NULL: not wanted; RN_E_ARG when given for a launch that is not split).  pair = 1: one launch with TWO right-hand sides as NAMA pairs its Hessian
+ * sweeps -- the second is y (RN_BUF_XI / RN_BUF_PSI), its product goes to myB [nodes][2 nv]; the launch runs unsplit, as a paired sweep does.
+ * RN_E_STATE unless rn_get_sweep_pairing reports the pair active.  pair = 0 ignores myB.  RN_E_STATE in the structured mode (no blocks) and before
+ * the factor step.  Changes no iterate (the products and a_i are scratch that every sweep overwrites) and launches nothing but that kernel;
+ * rn_debug_stream_live / _units report this launch afterwards. */
+int rn_debug_stream_product(rn_ctx *ctx, int pair, double *my, double *my2, double *myB);
+
 /* The gradient restart test (rn_set_restart, rapidnet.h) alone: runs k_restart_test on the context's current w (the last sweep's input, what
  * RN_BUF_ACC_* shows), y+ and y and returns out = {g, na2, nb2} -- the kernel can be checked without running a solve.  Allocates the kernel's
  * partials on first use; changes no iterate.  On a sharded context every rank calls it (it contains the ranks' all-reduce). */

@@ -60,7 +60,7 @@ SYMBOLS = [
     "rn_debug_set_allreduce", "rn_debug_local_group_create", "rn_debug_local_group_join", "rn_debug_local_group_destroy",
     "rn_guard_check", "rn_device_memory_info", "rn_reserve_iterations", "rn_profile_read_collective", "rn_debug_inject_allocation", "rn_guard_report", "rn_debug_guard_poke",
     "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_set_bounds", "rn_set_bounds_device", "rn_get_bounds_layout", "rn_get_bounds", "rn_debug_cut_moments",
-    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live", "rn_debug_stream_units",
+    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live", "rn_debug_stream_units", "rn_debug_stream_product",
     "rn_plan_report", "rn_plan_report_scenarios", "rn_plan_report_device",
     "rn_plan_quantiles", "rn_plan_quantiles_device", "rn_plan_paths",
     "rn_shift_warm_start", "rn_set_shift_map", "rn_get_shift_map",
@@ -257,6 +257,7 @@ def load():
     lib.rn_debug_stream_info.argtypes = [vp, dp]
     lib.rn_debug_stream_live.argtypes = [vp, dp]
     lib.rn_debug_stream_units.argtypes = [vp, dp]
+    lib.rn_debug_stream_product.argtypes = [vp, C.c_int, dp, dp, dp]
     lib.rn_profile_read_collective.argtypes = [vp, dp, dp]
     lib.rn_set_tree_data.argtypes = [vp, C.c_size_t, dp, dp, dp]
     lib.rn_set_tree_data_device.argtypes = [vp, C.c_size_t, ip, vp, vp, vp]
@@ -979,6 +980,22 @@ class Solver:
         out = np.zeros(3, dtype=np.int64)
         self._check(self.lib.rn_debug_stream_units(self.h, out.ctypes.data))
         return dict(zip(("liveUnits", "units", "columnsPerUnit"), (int(v) for v in out)))
+
+    def streamProduct(self, pair=False):
+        """rn_debug_stream_product (include/rapidnet_debug.h): k_stream_gemv alone at the accelerated dual (BUF_ACC_*), as a sweep of this context
+        would launch it.  Returns {"my": [nodes][2 nv]}; on a context with a split last round also "my2": [nodes - splitFirst][2 nv], the second
+        workgroups' partials ("my" then holds the first workgroups' for those blocks); pair=True: one launch with y (BUF_XI / BUF_PSI) as the
+        second right-hand side, its product in "myB" (unsplit: no "my2")."""
+        rows = 2 * self.nv
+        out = {"my": np.zeros((self.nodes, rows))}
+        first = self.streamInfo()["splitFirst"]
+        if pair:
+            out["myB"] = np.zeros((self.nodes, rows))
+        elif 0 <= first < self.nodes:
+            out["my2"] = np.zeros((self.nodes - first, rows))
+        self._check(self.lib.rn_debug_stream_product(self.h, int(bool(pair)), out["my"].ctypes.data, out["my2"].ctypes.data if "my2" in out else None,
+                                                     out["myB"].ctypes.data if pair else None))
+        return out
 
     def debugGuardPoke(self, nbytes):
         self._check(self.lib.rn_debug_guard_poke(self.h, int(nbytes)))

@@ -50,6 +50,13 @@ namespace rn {
 // walk of NL = 1, 3, 4.
 __device__ __forceinline__ bool stream_nz(double v) { return ((unsigned long long)__double_as_longlong(v) << 1) != 0ull; }
 __device__ __forceinline__ bool stream_nz(float v) { return (__float_as_uint(v) << 1) != 0u; }
+// The multiply-add of both walks.  In the fp32 kernels it is ONE fused operation, said so here and not left to the compiler's contraction: that fused most
+// of them (v_pk_fma_f32) and left some as v_pk_mul_f32 + v_pk_add_f32 -- which ones depended on the instantiation (NL = 1: 12 to 14 packed pairs per right-hand
+// side, NL = 2 with two right-hand sides: one), so the same column rounded once in one instantiation and twice in another, and two right-hand sides in one pass
+// were not the bits of two launches (tests/test_gpu_stream_product.py).  The fp64 sums are written as they always were -- every one of them is contracted to
+// v_fma_f64 / v_fmac_f64 in every instantiation -- and those kernels' code is unchanged.
+__device__ __forceinline__ double stream_fma(double a, double b, double c) { return c + a * b; }
+__device__ __forceinline__ float stream_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 // The group schedule of both walks.  Each walk defines RN_GROUP (its group size: D spans, or DU units), RN_POP (the next live index of the chunk's mask into sv[d]),
 // RN_LOAD1 / RN_USE1 (request / consume what a thread owns of span or unit sv[d]) and the buffers bufA / bufB with their index sets sA / sB.  A chunk's nLive =
 // nGroups * RN_GROUP + nHead live ones: the live count mod the group size goes FIRST (they are met in increasing order either way), as a partial group (RN_LOADH /
@@ -115,10 +122,10 @@ __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *
 #define RN_USE1(buf, sv, d)                                                                                            \
     _Pragma("unroll") for (int j = 0; j < NL; j++) {                                                                   \
         const T yc = sh_y[sv[d] * G + cj[j]] * msk[j];                                                                 \
-        _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] += (T)buf[d][j][e] * yc;                            \
+        _Pragma("unroll") for (int e = 0; e < VPL; e++) part[j][e] = stream_fma((T)buf[d][j][e], yc, part[j][e]);      \
         if (NR == 2) {      /* (fp32 blocks under fp64 sums: the lane's values are converted once and meet both columns) */ \
             const T yc2 = sh_y2[sv[d] * G + cj[j]] * msk[j];                                                           \
-            _Pragma("unroll") for (int e = 0; e < VPL; e++) part2[j][e] += (T)buf[d][j][e] * yc2;                      \
+            _Pragma("unroll") for (int e = 0; e < VPL; e++) part2[j][e] = stream_fma((T)buf[d][j][e], yc2, part2[j][e]); \
         }                                                                                                              \
     }
     for (int cb = span0; cb < span1; cb += 64) {      // chunks of 64 spans: a group never crosses a chunk
@@ -158,11 +165,11 @@ __device__ __forceinline__ void stream_walk(const VT *__restrict__ Ab, const T *
                 const bool ok = msk[j] != (T)0 && c < ny;
                 const T yc = ok ? sh_y[c] : (T)0;
 #pragma unroll
-                for (int e = 0; e < VPL; e++) part[j][e] += (T)bufR[j][e] * yc;
+                for (int e = 0; e < VPL; e++) part[j][e] = stream_fma((T)bufR[j][e], yc, part[j][e]);
                 if (NR == 2) {
                     const T yc2 = ok ? sh_y2[c] : (T)0;
 #pragma unroll
-                    for (int e = 0; e < VPL; e++) part2[j][e] += (T)bufR[j][e] * yc2;
+                    for (int e = 0; e < VPL; e++) part2[j][e] = stream_fma((T)bufR[j][e], yc2, part2[j][e]);
                 }
             }
         }
@@ -213,11 +220,11 @@ __device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, cons
         const int cy = (sv[d] >> 1) * G + (h1 ? cj[1] : cj[0]);                                                        \
         const T yv = sh_y[cy];                                                                                         \
         const T ya = h1 ? (T)0 : yv, yb = h1 ? yv : (T)0;                                                              \
-        _Pragma("unroll") for (int e = 0; e < VPL; e++) { part[0][e] += (T)buf[d][e] * ya; part[1][e] += (T)buf[d][e] * yb; } \
+        _Pragma("unroll") for (int e = 0; e < VPL; e++) { part[0][e] = stream_fma((T)buf[d][e], ya, part[0][e]); part[1][e] = stream_fma((T)buf[d][e], yb, part[1][e]); } \
         if (NR == 2) {                                                                                                 \
             const T yv2 = sh_y2[cy];                                                                                   \
             const T ya2 = h1 ? (T)0 : yv2, yb2 = h1 ? yv2 : (T)0;                                                      \
-            _Pragma("unroll") for (int e = 0; e < VPL; e++) { part2[0][e] += (T)buf[d][e] * ya2; part2[NR == 2 ? 1 : 0][e] += (T)buf[d][e] * yb2; } \
+            _Pragma("unroll") for (int e = 0; e < VPL; e++) { part2[0][e] = stream_fma((T)buf[d][e], ya2, part2[0][e]); part2[NR == 2 ? 1 : 0][e] = stream_fma((T)buf[d][e], yb2, part2[NR == 2 ? 1 : 0][e]); } \
         }                                                                                                              \
     }
     for (int ub = u0; ub < u1; ub += 64) {      // chunks of 64 units (ub is even: a span's two units share a chunk); a group never crosses a chunk
@@ -251,11 +258,11 @@ __device__ __forceinline__ void stream_walk_half(const VT *__restrict__ Ab, cons
                     const VT bufR = __builtin_nontemporal_load(reinterpret_cast<const VT *>(Abb + (ok ? (size_t)rag * spanBytes + offB[h] : (size_t)0)));
                     const T yc = ok ? sh_y[c] : (T)0;
 #pragma unroll
-                    for (int e = 0; e < VPL; e++) part[h][e] += (T)bufR[e] * yc;
+                    for (int e = 0; e < VPL; e++) part[h][e] = stream_fma((T)bufR[e], yc, part[h][e]);
                     if (NR == 2) {
                         const T yc2 = ok ? sh_y2[c] : (T)0;
 #pragma unroll
-                        for (int e = 0; e < VPL; e++) part2[NR == 2 ? h : 0][e] += (T)bufR[e] * yc2;
+                        for (int e = 0; e < VPL; e++) part2[NR == 2 ? h : 0][e] = stream_fma((T)bufR[e], yc2, part2[NR == 2 ? h : 0][e]);
                     }
                 }
         }
@@ -351,7 +358,7 @@ struct StreamDepth {
 // storage is behind rn_set_sweep_pairing(RN_PAIR_ON) (Ctx::stream_pair_ok); not measured on an MI355X yet.
 // LDS: NR * (ny + G * LD) values of T (fp32 storage, NR = 2: up to the CU's 160 KB, Ctx::launch_stream).  HBM bytes per node, fp32 storage: LD*ny*4 + NR*(ny + 2nv + nx)*8.
 // Registers with fp32 storage (hipcc's resource report, SPLIT = false | true; NL = 2 with the walk over half-spans, the others with the walk over live spans): NL = 1:
-// 120 | 64 VGPRs, NL = 2: 211 | 125 (span walk: 184 | 156), NL = 3: 193 | 188, NL = 4: 255 | 248; no scratch (ST = T = float, NL = 2: 137 | 125, double: 123 | 125 -- span
+// 120 | 64 VGPRs, NL = 2: 211 | 125 (span walk: 184 | 156), NL = 3: 193 | 188, NL = 4: 255 | 248; no scratch (ST = T = float, NL = 2: 129 | 125 with stream_fma, double: 123 | 125 -- span
 // walk 160 | 122 and 147 | 123).  NR = 2 (SPLIT = false): NL = 1: 138, NL = 2: 247 (span walk: 215), NL = 3: 210, NL = 4: 229 (groups of one span); no scratch, two waves
 // per SIMD from NL = 2 on.
 template <typename T, int NL, bool SPLIT, int NR = 1, typename ST = T>

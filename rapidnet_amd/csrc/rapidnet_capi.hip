@@ -183,6 +183,7 @@ struct CtxBase {
     virtual int algorithmic_bytes(double *, double *) const = 0;
     virtual int stream_live(long long *) = 0;
     virtual int stream_units(long long *) = 0;
+    virtual int stream_product(int, double *, double *, double *) = 0;
     virtual int synchronize() = 0;
     virtual void *stream_handle() = 0;
     virtual int comm_init(int, int, const void *, double timeoutSeconds = -1.0) = 0;
@@ -1934,6 +1935,26 @@ struct Ctx : CtxBase {
         RN_CHECK(!structured && lastStreamGrid > 0 && d_streamLive, RN_E_STATE, "rn_debug_stream_live: no streaming launch yet");
         return stream_live_sum(out, nullptr);
     }
+    // rn_debug_stream_product (include/rapidnet_debug.h): launch_stream alone, with the arguments a sweep of this context would give it at the
+    // accelerated dual RN_BUF_ACC_* shows; pair: the context's y (RN_BUF_XI / RN_BUF_PSI) as the second right-hand side of an NR = 2 launch,
+    // unsplit as launch_sweep runs a pair.  The products are scratch of the next sweep's: no iterate changes.
+    int stream_product(int pair, double *my, double *my2, double *myB) override {
+        RN_CHECK(my && (pair == 0 || pair == 1) && (!pair || myB), RN_E_ARG, "rn_debug_stream_product: my is required, pair is 0 or 1, and pair = 1 needs myB");
+        RN_CHECK(factored && !structured && p_acc_view && p_xi, RN_E_STATE, "rn_debug_stream_product: dense per-node blocks exist after rn_factor_step on a context that is not structured");
+        RN_CHECK(!pair || pair_active(), RN_E_STATE, "rn_debug_stream_product: pair = 1 needs the pair buffers and a launch that can run unsplit (rn_get_sweep_pairing: active)");
+        RN_HIP(hipSetDevice(device));
+        SweepArgs<T> a = sweep_args(Batch{});
+        a.w = p_acc_view;
+        if (pair && store32()) a.splitFirst = d.nodes;
+        RN_CHECK(!my2 || a.splitFirst < d.nodes, RN_E_ARG, "rn_debug_stream_product: my2 belongs to a launch with a split last round");
+        const StreamRhs2<T> r2{p_xi, d_myB, d_qaB};
+        if (int rc = launch_stream(a, pair ? &r2 : nullptr)) return rc;
+        RN_HIP(hipGetLastError());
+        if (int rc = download(my, d_my, (size_t)d.nodes * 2 * d.nv)) return rc;
+        if (my2) { if (int rc = download(my2, d_my2, (size_t)(d.nodes - a.splitFirst) * 2 * d.nv)) return rc; }
+        if (pair) { if (int rc = download(myB, d_myB, (size_t)d.nodes * 2 * d.nv)) return rc; }
+        return RN_OK;
+    }
     int counters(long *out) override {
         RN_CHECK(out, RN_E_ARG, "rn_get_counters: null output");
         out[0] = optBatches; out[1] = exactBatches; out[2] = fallbacks; out[3] = optHold;
@@ -2557,6 +2578,7 @@ int rn_debug_set_knob(rn_ctx *ctx, int knob, int value) { RN_GUARD(ctx); return 
 int rn_debug_stream_info(rn_ctx *ctx, int info[4]) { RN_GUARD(ctx); return ctx->impl->stream_info(info); }
 int rn_debug_stream_live(rn_ctx *ctx, long long out[4]) { RN_GUARD(ctx); return ctx->impl->stream_live(out); }
 int rn_debug_stream_units(rn_ctx *ctx, long long out[3]) { RN_GUARD(ctx); return ctx->impl->stream_units(out); }
+int rn_debug_stream_product(rn_ctx *ctx, int pair, double *my, double *my2, double *myB) { RN_GUARD(ctx); return ctx->impl->stream_product(pair, my, my2, myB); }
 int rn_debug_restart_test(rn_ctx *ctx, double out[3]) { RN_GUARD(ctx); return ctx->impl->debug_restart_test(out); }
 int rn_debug_peer_seq(rn_ctx *ctx, unsigned int seq) { RN_GUARD(ctx); return ctx->impl->debug_peer_seq(seq); }
 int rn_guard_report(long out[2]) { if (!out) return RN_E_ARG; out[0] = rn::g_guardContexts.load(); out[1] = rn::g_guardBadBytes.load(); return RN_OK; }
