@@ -322,9 +322,6 @@ __global__ void __launch_bounds__(ELT_THREADS) k_dual_fused(DualArgs<T> a) {
 // sqrt(p_i) one more, and all seven loads of a vector are requested together: one memory round trip, no dependent chain.
 // Same arithmetic, element by element, as k_dual_fused (dual_elem); the partials (one per workgroup) are folded by the same
 // bookkeeping code.
-#ifndef RN_DUAL_ABL
-#define RN_DUAL_ABL 0   // timing ablations of k_dual_stage (tools/sweep_variants.sh; results are WRONG when set): bit 0 = no table loads,
-#endif                  // bit 1 = no reductions / partials, bit 2 = no stores, bit 3 = no store of the extrapolated dual w (4 streams instead of 5)
 struct DualStageShape {
     int cs, K, node0;        // first regular stage, nodes per regular stage, first node of stage cs
     int bps, crownBlocks;    // workgroups per regular stage; leading workgroups that cover the nodes [0, node0)
@@ -364,15 +361,11 @@ __device__ __forceinline__ void dual_slot_load(DualSlot<T> &s, const DualArgs<T>
     if (crownBlock) stage = a.stageOf[node];
     s.hx = reinterpret_cast<const VT *>(a.hx)[s.iv]; s.w = reinterpret_cast<const VT *>(a.w)[s.iv];
     s.yp = reinterpret_cast<const VT *>(a.yprev)[s.iv];
-#if RN_DUAL_ABL & 1
-    s.sp = (T)1; for (int e = 0; e < VN; e++) { s.dy[e] = (T)1; s.blo[e] = (T)-1; s.bhi[e] = (T)stage; }
-#else
     s.sp = a.sqrtp[node];
     s.dy = *reinterpret_cast<const VT *>(a.dy + (size_t)stage * a.ny + s.c);
     const int bc = stage * a.bStrideStage + node * a.bStrideNode + s.c;
     s.blo = *reinterpret_cast<const VT *>(a.blo + bc);
     s.bhi = *reinterpret_cast<const VT *>(a.bhi + bc);
-#endif
 }
 template <typename T, bool MATERIALIZE, bool SCALE = false>
 __device__ __forceinline__ void dual_slot_use(const DualSlot<T> &s, const DualArgs<T> &a, T ln, DualAcc<T> &r) {
@@ -393,7 +386,6 @@ __device__ __forceinline__ void dual_slot_use(const DualSlot<T> &s, const DualAr
         const T hxv = SCALE ? k * s.hx[e] : s.hx[e];
         const DualOut<T> o = dual_elem<T, false>(hxv, s.w[e], lo, hi, s.yp[e], a.lambda, a.invLambda, ln, (T)0);
         yn[e] = o.yn; wn[e] = o.wn; z[e] = o.z; res[e] = o.res;
-#if !(RN_DUAL_ABL & 2)
         const double dd = counted ? (double)o.diff * (double)o.diff : 0.0;
         r.d2x += isBox ? dd : 0.0;
         r.d2s += (isXi && !isBox) ? dd : 0.0;
@@ -403,19 +395,34 @@ __device__ __forceinline__ void dual_slot_use(const DualSlot<T> &s, const DualAr
         const bool upP = !isXi && (fabs(rv) > fabs(r.valPsi) || r.idxPsi == 0xffffffffu);
         r.valXi = upX ? rv : r.valXi; r.idxXi = upX ? ie : r.idxXi;
         r.valPsi = upP ? rv : r.valPsi; r.idxPsi = upP ? ie : r.idxPsi;
-#endif
     }
-#if RN_DUAL_ABL & 4
-    if (yn[0] == (T)1.2345e-30) reinterpret_cast<VT *>(a.ynew)[s.iv] = wn;
-#else
     reinterpret_cast<VT *>(a.ynew)[s.iv] = yn;
-#if RN_DUAL_ABL & 8
-    if (yn[0] == (T)1.2345e-30)
-#endif
     reinterpret_cast<VT *>(a.wnext)[s.iv] = wn;
     if (MATERIALIZE) { reinterpret_cast<VT *>(a.z)[s.iv] = z; reinterpret_cast<VT *>(a.res)[s.iv] = res; }
-#endif
-    (void)counted;
+}
+// The workgroup's epilogue (k_dual_stage, k_down_chain_dual; ELT_THREADS threads, all of them arrive): the threads' running reductions folded
+// into ONE partial -- across a wave by DPP, across the waves through sh_p ([ELT_THREADS / 64]) in ascending order by thread 0, which stores it.
+template <typename T>
+__device__ __forceinline__ void dual_acc_store(const DualAcc<T> &r, Partial *sh_p, Partial *out) {
+    double valXi = r.valXi, valPsi = r.valPsi;
+    long long idxXi = r.idxXi == 0xffffffffu ? 0x7fffffffffffffffLL : (long long)r.idxXi;
+    long long idxPsi = r.idxPsi == 0xffffffffu ? 0x7fffffffffffffffLL : (long long)r.idxPsi;
+    double absXi = r.idxXi == 0xffffffffu ? -1.0 : fabs(valXi), absPsi = r.idxPsi == 0xffffffffu ? -1.0 : fabs(valPsi);
+    const double d2x = wave_sum_f64(r.d2x), d2s = wave_sum_f64(r.d2s);
+    wave_argmax(absXi, valXi, idxXi);
+    wave_argmax(absPsi, valPsi, idxPsi);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) sh_p[wave] = Partial{d2x, d2s, absXi, valXi, absPsi, valPsi, idxXi, idxPsi};
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        Partial p = sh_p[0];
+        for (int k = 1; k < ELT_THREADS / 64; k++) {
+            p.d2x += sh_p[k].d2x; p.d2s += sh_p[k].d2s;
+            better(p.absXi, p.valXi, p.idxXi, sh_p[k].absXi, sh_p[k].valXi, sh_p[k].idxXi);
+            better(p.absPsi, p.valPsi, p.idxPsi, sh_p[k].absPsi, sh_p[k].valPsi, sh_p[k].idxPsi);
+        }
+        *out = p;
+    }
 }
 // PIPE = 1: one vector at a time;  PIPE = 2: double-buffered -- the loads of trip t+1 are requested before trip t is consumed, so
 // a wave always has a trip in flight (the kernel lives on memory-level parallelism: its VALU phase is a gap in the streams)
@@ -454,29 +461,7 @@ __global__ void __launch_bounds__(ELT_THREADS) k_dual_stage(DualArgs<T> a, DualS
             if (hasB) dual_slot_use<T, MATERIALIZE, SCALE>(sB, a, ln, r);
         }
     }
-#if RN_DUAL_ABL & 2
-    if (r.d2x == 1.2345e-30) a.partials[blockIdx.x] = Partial{r.d2x, r.d2s, 0, r.valXi, 0, r.valPsi, r.idxXi, r.idxPsi};
-    return;
-#endif
-    double valXi = r.valXi, valPsi = r.valPsi;
-    long long idxXi = r.idxXi == 0xffffffffu ? 0x7fffffffffffffffLL : (long long)r.idxXi;
-    long long idxPsi = r.idxPsi == 0xffffffffu ? 0x7fffffffffffffffLL : (long long)r.idxPsi;
-    double absXi = r.idxXi == 0xffffffffu ? -1.0 : fabs(valXi), absPsi = r.idxPsi == 0xffffffffu ? -1.0 : fabs(valPsi);
-    const double d2x = wave_sum_f64(r.d2x), d2s = wave_sum_f64(r.d2s);
-    wave_argmax(absXi, valXi, idxXi);
-    wave_argmax(absPsi, valPsi, idxPsi);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) sh_p[wave] = Partial{d2x, d2s, absXi, valXi, absPsi, valPsi, idxXi, idxPsi};
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        Partial p = sh_p[0];
-        for (int k = 1; k < ELT_THREADS / 64; k++) {
-            p.d2x += sh_p[k].d2x; p.d2s += sh_p[k].d2s;
-            better(p.absXi, p.valXi, p.idxXi, sh_p[k].absXi, sh_p[k].valXi, sh_p[k].idxXi);
-            better(p.absPsi, p.valPsi, p.idxPsi, sh_p[k].absPsi, sh_p[k].valPsi, sh_p[k].idxPsi);
-        }
-        a.partials[blockIdx.x] = p;
-    }
+    dual_acc_store(r, sh_p, a.partials + blockIdx.x);
 }
 
 // one workgroup: fold the block partials; decide whether the soft-constraint branch trips

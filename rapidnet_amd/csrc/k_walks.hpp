@@ -22,8 +22,11 @@ static_assert(CHAIN_THREADS == ELT_THREADS, "the bookkeeping workgroup of k_up_c
 #endif
 constexpr int CHAIN_PF = RN_CHAIN_PF;
 constexpr int CROWN_THREADS = 1024;   // stages prefetched per round trip (the recursion itself is a running sum)
-// (the walk is spelled out twice, here and in k_up_chain_cut: shared through a device function it measured 8 us slower on the
-//  493-scenario tree -- 20.1 instead of 11.8 us)
+// (the walk is spelled out twice, here and in k_up_chain_cut.  Shared as a force-inlined template up_chain_walk<T, SPLIT, PF, TopOut>(a, nodeTop, t,
+//  top_out) -- one component of one chain, top_out(column, value) a lambda that stores the top's rho / kappa / q into k_up_chain_cut's LDS tile and does
+//  nothing in k_up_chain -- registers, LDS and occupancy were the same and the results bitwise equal; k_up_chain measured 9.72-9.76 against 9.84-10.04 us
+//  on the 493-scenario tree, but k_up_chain_cut<double, SPLIT> on rank 0 of an 8-way split 12.08-12.20 against 11.72-11.92 us in alternating runs: the
+//  same loads and sums scheduled differently, with the peer arguments loaded again behind the walk.  profiles/ab_walk_refactor.txt)
 // SPLIT: the instantiation that adds the second partial m2 of k_stream_gemv's split last round (the other one is the walk as it always was)
 #ifndef RN_UP_PF
 #define RN_UP_PF 24
@@ -740,30 +743,223 @@ __global__ void __launch_bounds__(CUT_THREADS) k_cut_partial_sums(SweepArgs<T> a
 constexpr int CROWN_MAX_DEPTH = 8;
 template <typename T>
 __device__ __forceinline__ void down_crown_node(const SweepArgs<T> &a, int stage, int pos, int tid, int nthreads);
+// Where the forward walks below leave a node's values (u, x and bw they store themselves):
+//   crown_u / crown_x: crown node `node` of `stage`, the dd-th ancestor of the chain top (down_crown_path: its one node, dd = 0)
+//   chain_u / chain_x: row `row` of the chain (stage c* + row), with the preconditioner entries d0 / d1 the walk requested (DY; zero otherwise)
+// HxSink: Hx to global memory -- UNSC ? the primal value : sqrt(p_i) d_k o value (sp: sqrt(p) of the chain, constant along it)
+template <typename T, bool UNSC>
+struct HxSink {
+    T *hx;
+    const T *sqrtp, *dy;
+    int ny, nx;
+    T sp;
+    __device__ __forceinline__ void crown_u(int, int node, int stage, int t, T uv) const {
+        const T spc = sqrtp[node];
+        hx[(size_t)node * ny + 2 * nx + t] = UNSC ? uv : spc * dy[(size_t)stage * ny + 2 * nx + t] * uv;
+    }
+    __device__ __forceinline__ void crown_x(int, int node, int stage, int j0, T xr) const {
+        const T spc = sqrtp[node];
+        hx[(size_t)node * ny + j0] = UNSC ? xr : spc * dy[(size_t)stage * ny + j0] * xr;
+        hx[(size_t)node * ny + nx + j0] = UNSC ? xr : spc * dy[(size_t)stage * ny + nx + j0] * xr;
+    }
+    __device__ __forceinline__ void chain_u(int, size_t node, int t, T uv, T d0) const { hx[node * ny + 2 * nx + t] = UNSC ? uv : sp * d0 * uv; }
+    __device__ __forceinline__ void chain_x(int, size_t node, int j0, T xr, T d0, T d1) const {
+        hx[node * ny + j0] = UNSC ? xr : sp * d0 * xr;
+        hx[node * ny + nx + j0] = UNSC ? xr : sp * d1 * xr;
+    }
+};
+// LdsPrimalSink: the primal values (x | x | u) into an LDS tile [rows][ny]; the chain's rows first, the crown rows from crownRow0
+template <typename T>
+struct LdsPrimalSink {
+    T *shx;
+    int ny, nx, crownRow0;
+    __device__ __forceinline__ void crown_u(int dd, int, int, int t, T uv) const { shx[(size_t)(crownRow0 + dd) * ny + 2 * nx + t] = uv; }
+    __device__ __forceinline__ void crown_x(int dd, int, int, int j0, T xr) const {
+        shx[(size_t)(crownRow0 + dd) * ny + j0] = xr;
+        shx[(size_t)(crownRow0 + dd) * ny + nx + j0] = xr;
+    }
+    __device__ __forceinline__ void chain_u(int row, size_t, int t, T uv, T) const { shx[(size_t)row * ny + 2 * nx + t] = uv; }
+    __device__ __forceinline__ void chain_x(int row, size_t, int j0, T xr, T, T) const {
+        shx[(size_t)row * ny + j0] = xr;
+        shx[(size_t)row * ny + nx + j0] = xr;
+    }
+};
+// The top-to-leaf walk of chain s over the stages [c*, kEnd), kEnd > c*: thread t owns one component (from tFirst in steps of CHAIN_THREADS).
+// fold: the running sums start at the root and come down the crown path anc[] (leaf-most first), whose nodes with writer[dd] are written on
+// the way; otherwise they start from what a crown launch stored for `par`, the parent of the chain top.  DY: the preconditioner entries of
+// the chain's stages are requested for the sink.  storePrimal: u and x of the chain's nodes are stored (the crown's: a.writePrimal).
+// Request order (round 6): the first batch of the chain's rows needs nothing but the chain's number, so it is requested FIRST; the crown path's
+// rows are requested right behind the batch -- one round trip for both instead of three.
+template <typename T, int PF, bool DY, typename Sink>
+__device__ __forceinline__ void down_chain_walk(const SweepArgs<T> &a, int s, int kEnd, bool fold, const int (&anc)[CROWN_MAX_DEPTH], const bool (&writer)[CROWN_MAX_DEPTH],
+                                                int par, bool storePrimal, int tFirst, const Sink &sink) {
+    const int nx = a.nx, nu = a.nu, ny = a.ny, w = nu + nx;
+    const int top = a.chainStage;
+    const size_t nodeTop = (size_t)(a.chain0 + s);   // every stage >= c* has K nodes: node of stage k in this chain = nodeTop + (k - c*) K
+    const T *__restrict__ lvb = a.lvb;
+    const T *__restrict__ uhat = a.uhat;
+    const T *__restrict__ eb = a.eb;
+    const T *__restrict__ dyAll = a.tr.dy;
+    // a.lin & 4 (structured mode, composite operator): the affine terms uhat_i - uhat_anc, eb_i - eb_anc are part of the product's constant operand
+    // (Ctx::lin_const_refresh), so lvb's running sums ARE u_i and B u_i + e-sums: the walk requests neither uhat nor eb
+    const bool AF = (a.lin & 4) != 0;
+    for (int t = tFirst; t < w; t += CHAIN_THREADS) {
+        if (t < nu) {
+            T dv[PF], uh[PF], d0[PF];
+            auto request = [&](int k) {
+#pragma unroll
+                for (int j = 0; j < PF; j++) {
+                    const int kk = k + j < kEnd ? k + j : kEnd - 1;
+                    const size_t node = nodeTop + (size_t)(kk - top) * a.K;
+                    dv[j] = lvb[node * w + t];
+                    uh[j] = AF ? (T)0 : uhat[node * nu + t];
+                    d0[j] = DY ? dyAll[(size_t)kk * ny + 2 * nx + t] : (T)0;
+                }
+            };
+            request(top);
+            T run;
+            if (fold) {
+                run = AF ? a.prevU[t] : a.prevU[t] - a.prevUhat[t];
+                T lv[CROWN_MAX_DEPTH], uhc[CROWN_MAX_DEPTH];
+#pragma unroll
+                for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
+                    if (dd < top) { lv[dd] = lvb[(size_t)anc[dd] * w + t]; uhc[dd] = AF ? (T)0 : uhat[(size_t)anc[dd] * nu + t]; }
+#pragma unroll
+                for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
+                    if (dd < top) {
+                        const T uv = uhc[dd] + run + lv[dd];              // same association as down_crown_node
+                        run = uv - uhc[dd];                                // what a child reads back: u_par - uhat_par
+                        if (writer[dd]) {
+                            if (a.writePrimal) a.u[(size_t)anc[dd] * nu + t] = uv;
+                            sink.crown_u(dd, anc[dd], top - 1 - dd, t, uv);
+                        }
+                    }
+            } else if (AF) run = par < 0 ? a.prevU[t] : a.u[(size_t)par * nu + t];
+            else run = par < 0 ? (a.prevU[t] - a.prevUhat[t]) : (a.u[(size_t)par * nu + t] - a.uhat[(size_t)par * nu + t]);
+            for (int k = top; k < kEnd; k += PF) {
+#pragma unroll
+                for (int j = 0; j < PF; j++) {
+                    if (k + j < kEnd) {
+                        const size_t node = nodeTop + (size_t)(k + j - top) * a.K;
+                        run += dv[j];
+                        const T uv = uh[j] + run;
+                        if (storePrimal) a.u[node * nu + t] = uv;
+                        sink.chain_u(k + j - top, node, t, uv, d0[j]);
+                    }
+                }
+                if (k + PF < kEnd) request(k + PF);
+            }
+        } else {
+            const int j0 = t - nu;
+            T dv[PF], ev[PF], d0[PF], d1[PF];
+            auto request = [&](int k) {
+#pragma unroll
+                for (int j = 0; j < PF; j++) {
+                    const int kk = k + j < kEnd ? k + j : kEnd - 1;
+                    const size_t node = nodeTop + (size_t)(kk - top) * a.K;
+                    dv[j] = lvb[node * w + nu + j0];
+                    ev[j] = AF ? (T)0 : eb[node * nx + j0];
+                    d0[j] = DY ? dyAll[(size_t)kk * ny + j0] : (T)0;
+                    d1[j] = DY ? dyAll[(size_t)kk * ny + nx + j0] : (T)0;
+                }
+            };
+            request(top);
+            T bw, xr;
+            if (fold) {
+                bw = a.bw0[j0]; xr = a.curX[j0];
+                T lv[CROWN_MAX_DEPTH], evc[CROWN_MAX_DEPTH];
+#pragma unroll
+                for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
+                    if (dd < top) { lv[dd] = lvb[(size_t)anc[dd] * w + nu + j0]; evc[dd] = AF ? (T)0 : eb[(size_t)anc[dd] * nx + j0]; }
+#pragma unroll
+                for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
+                    if (dd < top) {
+                        bw = bw + lv[dd];
+                        xr = xr + evc[dd] + bw;
+                        if (writer[dd]) {
+                            a.bw[(size_t)anc[dd] * nx + j0] = bw;
+                            if (a.writePrimal) a.x[(size_t)anc[dd] * nx + j0] = xr;
+                            sink.crown_x(dd, anc[dd], top - 1 - dd, j0, xr);
+                        }
+                    }
+            } else {
+                bw = par < 0 ? a.bw0[j0] : a.bw[(size_t)par * nx + j0];
+                xr = par < 0 ? a.curX[j0] : a.x[(size_t)par * nx + j0];
+            }
+            for (int k = top; k < kEnd; k += PF) {
+#pragma unroll
+                for (int j = 0; j < PF; j++) {
+                    if (k + j < kEnd) {
+                        const size_t node = nodeTop + (size_t)(k + j - top) * a.K;
+                        bw += dv[j];
+                        xr += ev[j] + bw;
+                        if (storePrimal) a.x[node * nx + j0] = xr;
+                        sink.chain_x(k + j - top, node, j0, xr, d0[j], d1[j]);
+                    }
+                }
+                if (k + PF < kEnd) request(k + PF);
+            }
+        }
+    }
+}
+// Sharded runs (foldCrown = 2): a workgroup of its own writes crown node j of stage kj, walking root -> j itself (every input of the path is
+// already there: independent loads, then a short running sum with down_crown_node's association)
+template <typename T, typename Sink>
+__device__ __forceinline__ void down_crown_path(const SweepArgs<T> &a, int j, int kj, const Sink &sink) {
+    const int nx = a.nx, nu = a.nu, w = nu + nx;
+    const T *__restrict__ lvb = a.lvb;
+    const T *__restrict__ uhat = a.uhat;
+    const T *__restrict__ eb = a.eb;
+    const bool AF = (a.lin & 4) != 0;
+    int pth[CROWN_MAX_DEPTH];              // pth[0] = j, pth[kj] = root
+    {
+        int n = j;
+#pragma unroll
+        for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++) { pth[dd] = n; if (dd < kj) n = a.tr.parent[n]; }
+    }
+    for (int t = threadIdx.x; t < w; t += CHAIN_THREADS) {
+        if (t < nu) {
+            T run = AF ? a.prevU[t] : a.prevU[t] - a.prevUhat[t];
+            T lv[CROWN_MAX_DEPTH], uh[CROWN_MAX_DEPTH];
+#pragma unroll
+            for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
+                if (dd <= kj) { lv[dd] = lvb[(size_t)pth[dd] * w + t]; uh[dd] = AF ? (T)0 : uhat[(size_t)pth[dd] * nu + t]; }
+            T uv = 0;
+#pragma unroll
+            for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
+                if (dd <= kj) { uv = uh[dd] + run + lv[dd]; run = uv - uh[dd]; }
+            if (a.writePrimal) a.u[(size_t)j * nu + t] = uv;
+            sink.crown_u(0, j, kj, t, uv);
+        } else {
+            const int j0 = t - nu;
+            T bw = a.bw0[j0], xr = a.curX[j0];
+            T lv[CROWN_MAX_DEPTH], ev[CROWN_MAX_DEPTH];
+#pragma unroll
+            for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
+                if (dd <= kj) { lv[dd] = lvb[(size_t)pth[dd] * w + nu + j0]; ev[dd] = AF ? (T)0 : eb[(size_t)pth[dd] * nx + j0]; }
+#pragma unroll
+            for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
+                if (dd <= kj) { bw = bw + lv[dd]; xr = xr + ev[dd] + bw; }
+            a.bw[(size_t)j * nx + j0] = bw;
+            if (a.writePrimal) a.x[(size_t)j * nx + j0] = xr;
+            sink.crown_x(0, j, kj, j0, xr);
+        }
+    }
+}
 // UNSC (inner iterations of a device-resident batch whose dual update is k_dual_stage<..., HXM = 2>): the Hx buffer receives the PRIMAL values
 // (x_i | x_i | u_i) and the dual update applies the scaling sqrt(p_i) d_k -- it has that factor in registers for the bounds anyway, the product is
 // the same two roundings -- so the walk does not request the preconditioner table at all (a third to a half of its load instructions)
 template <typename T, bool UNSC = false, int PF = CHAIN_PF>
 __global__ void __launch_bounds__(CHAIN_THREADS) k_down_chain(SweepArgs<T> a, int foldCrown) {
     // foldCrown = 2 (sharded runs): the grid has one more workgroup per crown node behind the K chain workgroups; it writes that
-    // node (root -> node walk at the end of this kernel) while the chain workgroups walk their chains, instead of 18 of the 62
+    // node (down_crown_path) while the chain workgroups walk their chains, instead of 18 of the 62
     // chain workgroups doing it after their own chain (15.2 -> see DESIGN.md section 6 for the measured effect)
-    // Request order (round 6): the first batch of the chain's rows needs nothing but the chain's number, so it is requested FIRST; the crown path
-    // comes from a per-chain table (SweepArgs::chainAnc: one 32-byte scalar load instead of a parent -> parent chase of dependent table loads),
-    // its rows are requested right behind the batch -- one round trip for both instead of three.
     const bool crownWriter = (int)blockIdx.x >= a.K;
     const int s = crownWriter ? 0 : (int)blockIdx.x;
-    const int nx = a.nx, nu = a.nu, ny = a.ny, w = nu + nx;
     const int top = a.chainStage;
     const int ntop = a.chain0 + s;
-    const size_t nodeTop = (size_t)ntop;   // every stage >= c* has K nodes: node of stage k in this chain = nodeTop + (k - c*) K
-    const T sp = a.tr.sqrtp[ntop];   // p is constant along a chain
-    const T *__restrict__ lvb = a.lvb;
-    const T *__restrict__ uhat = a.uhat;
-    const T *__restrict__ eb = a.eb;
-    const T *__restrict__ dyAll = a.tr.dy;
-    const int *__restrict__ cum = a.tr.stageCum;
-    // crown path, leaf-most first: anc[0] = parent of the chain top (stage top-1) ... anc[top-1] = root
+    // crown path, leaf-most first: anc[0] = parent of the chain top (stage top-1) ... anc[top-1] = root -- from a per-chain table
+    // (SweepArgs::chainAnc: one 32-byte scalar load instead of a parent -> parent chase of dependent table loads)
     int anc[CROWN_MAX_DEPTH];
     bool writer[CROWN_MAX_DEPTH];
     if (foldCrown) {
@@ -775,156 +971,11 @@ __global__ void __launch_bounds__(CHAIN_THREADS) k_down_chain(SweepArgs<T> a, in
         }
     }
     const int par = foldCrown ? 0 : a.tr.parent[ntop];
-    // a.lin & 4 (structured mode, composite operator): the affine terms uhat_i - uhat_anc, eb_i - eb_anc are part of the product's constant operand
-    // (Ctx::lin_const_refresh), so lvb's running sums ARE u_i and B u_i + e-sums: the walk requests neither uhat nor eb
-    const bool AF = (a.lin & 4) != 0;
-    for (int t = crownWriter ? w : (int)threadIdx.x; t < w; t += CHAIN_THREADS) {
-        if (t < nu) {
-            T dv[PF], uh[PF], d0[PF];
-            auto request = [&](int k) {
-#pragma unroll
-                for (int j = 0; j < PF; j++) {
-                    const int kk = k + j < a.N ? k + j : a.N - 1;
-                    const size_t node = nodeTop + (size_t)(kk - top) * a.K;
-                    dv[j] = lvb[node * w + t];
-                    uh[j] = AF ? (T)0 : uhat[node * nu + t];
-                    d0[j] = UNSC ? (T)0 : dyAll[(size_t)kk * ny + 2 * nx + t];
-                }
-            };
-            request(top);
-            T run;
-            if (foldCrown) {
-                run = AF ? a.prevU[t] : a.prevU[t] - a.prevUhat[t];
-                T lv[CROWN_MAX_DEPTH], uhc[CROWN_MAX_DEPTH];
-#pragma unroll
-                for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
-                    if (dd < top) { lv[dd] = lvb[(size_t)anc[dd] * w + t]; uhc[dd] = AF ? (T)0 : uhat[(size_t)anc[dd] * nu + t]; }
-#pragma unroll
-                for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
-                    if (dd < top) {
-                        const int k = top - 1 - dd;                       // stage of anc[dd]
-                        const T uv = uhc[dd] + run + lv[dd];              // same association as down_crown_node
-                        run = uv - uhc[dd];                                // what a child reads back: u_par - uhat_par
-                        if (writer[dd]) {
-                            const T spc = a.tr.sqrtp[anc[dd]];
-                            if (a.writePrimal) a.u[(size_t)anc[dd] * nu + t] = uv;
-                            a.hx[(size_t)anc[dd] * ny + 2 * nx + t] = UNSC ? uv : spc * dyAll[(size_t)k * ny + 2 * nx + t] * uv;
-                        }
-                    }
-            } else if (AF) run = par < 0 ? a.prevU[t] : a.u[(size_t)par * nu + t];
-            else run = par < 0 ? (a.prevU[t] - a.prevUhat[t]) : (a.u[(size_t)par * nu + t] - a.uhat[(size_t)par * nu + t]);
-            for (int k = top; k < a.N; k += PF) {
-#pragma unroll
-                for (int j = 0; j < PF; j++) {
-                    if (k + j < a.N) {
-                        const size_t node = nodeTop + (size_t)(k + j - top) * a.K;
-                        run += dv[j];
-                        const T uv = uh[j] + run;
-                        if (a.writePrimal) a.u[node * nu + t] = uv;
-                        a.hx[node * ny + 2 * nx + t] = UNSC ? uv : sp * d0[j] * uv;
-                    }
-                }
-                if (k + PF < a.N) request(k + PF);
-            }
-        } else {
-            const int j0 = t - nu;
-            T dv[PF], ev[PF], d0[PF], d1[PF];
-            auto request = [&](int k) {
-#pragma unroll
-                for (int j = 0; j < PF; j++) {
-                    const int kk = k + j < a.N ? k + j : a.N - 1;
-                    const size_t node = nodeTop + (size_t)(kk - top) * a.K;
-                    dv[j] = lvb[node * w + nu + j0];
-                    ev[j] = AF ? (T)0 : eb[node * nx + j0];
-                    d0[j] = UNSC ? (T)0 : dyAll[(size_t)kk * ny + j0];
-                    d1[j] = UNSC ? (T)0 : dyAll[(size_t)kk * ny + nx + j0];
-                }
-            };
-            request(top);
-            T bw, xr;
-            if (foldCrown) {
-                bw = a.bw0[j0]; xr = a.curX[j0];
-                T lv[CROWN_MAX_DEPTH], evc[CROWN_MAX_DEPTH];
-#pragma unroll
-                for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
-                    if (dd < top) { lv[dd] = lvb[(size_t)anc[dd] * w + nu + j0]; evc[dd] = AF ? (T)0 : eb[(size_t)anc[dd] * nx + j0]; }
-#pragma unroll
-                for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
-                    if (dd < top) {
-                        const int k = top - 1 - dd;
-                        bw = bw + lv[dd];
-                        xr = xr + evc[dd] + bw;
-                        if (writer[dd]) {
-                            const T spc = a.tr.sqrtp[anc[dd]];
-                            a.bw[(size_t)anc[dd] * nx + j0] = bw;
-                            if (a.writePrimal) a.x[(size_t)anc[dd] * nx + j0] = xr;
-                            a.hx[(size_t)anc[dd] * ny + j0] = UNSC ? xr : spc * dyAll[(size_t)k * ny + j0] * xr;
-                            a.hx[(size_t)anc[dd] * ny + nx + j0] = UNSC ? xr : spc * dyAll[(size_t)k * ny + nx + j0] * xr;
-                        }
-                    }
-            } else {
-                bw = par < 0 ? a.bw0[j0] : a.bw[(size_t)par * nx + j0];
-                xr = par < 0 ? a.curX[j0] : a.x[(size_t)par * nx + j0];
-            }
-            for (int k = top; k < a.N; k += PF) {
-#pragma unroll
-                for (int j = 0; j < PF; j++) {
-                    if (k + j < a.N) {
-                        const size_t node = nodeTop + (size_t)(k + j - top) * a.K;
-                        bw += dv[j];
-                        xr += ev[j] + bw;
-                        if (a.writePrimal) a.x[node * nx + j0] = xr;
-                        a.hx[node * ny + j0] = UNSC ? xr : sp * d0[j] * xr;
-                        a.hx[node * ny + nx + j0] = UNSC ? xr : sp * d1[j] * xr;
-                    }
-                }
-                if (k + PF < a.N) request(k + PF);
-            }
-        }
-    }
-    if (foldCrown == 2) {
-        // sharded runs: crown node j is written by workgroup j mod gridDim, which walks root -> j itself (every input
-        // of the path is already there: independent loads, then a short running sum with down_crown_node's association)
-        const int nCrown = cum[top];
-        for (int j = crownWriter ? (int)blockIdx.x - a.K : nCrown; j < nCrown; j += nCrown) {
-            const int kj = a.tr.stageOf[j];
-            int pth[CROWN_MAX_DEPTH];              // pth[0] = j, pth[kj] = root
-            {
-                int n = j;
-#pragma unroll
-                for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++) { pth[dd] = n; if (dd < kj) n = a.tr.parent[n]; }
-            }
-            const T spj = a.tr.sqrtp[j];
-            for (int t = threadIdx.x; t < w; t += CHAIN_THREADS) {
-                if (t < nu) {
-                    T run = AF ? a.prevU[t] : a.prevU[t] - a.prevUhat[t];
-                    T lv[CROWN_MAX_DEPTH], uh[CROWN_MAX_DEPTH];
-#pragma unroll
-                    for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
-                        if (dd <= kj) { lv[dd] = lvb[(size_t)pth[dd] * w + t]; uh[dd] = AF ? (T)0 : uhat[(size_t)pth[dd] * nu + t]; }
-                    T uv = 0;
-#pragma unroll
-                    for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
-                        if (dd <= kj) { uv = uh[dd] + run + lv[dd]; run = uv - uh[dd]; }
-                    if (a.writePrimal) a.u[(size_t)j * nu + t] = uv;
-                    a.hx[(size_t)j * ny + 2 * nx + t] = UNSC ? uv : spj * dyAll[(size_t)kj * ny + 2 * nx + t] * uv;
-                } else {
-                    const int j0 = t - nu;
-                    T bw = a.bw0[j0], xr = a.curX[j0];
-                    T lv[CROWN_MAX_DEPTH], ev[CROWN_MAX_DEPTH];
-#pragma unroll
-                    for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
-                        if (dd <= kj) { lv[dd] = lvb[(size_t)pth[dd] * w + nu + j0]; ev[dd] = AF ? (T)0 : eb[(size_t)pth[dd] * nx + j0]; }
-#pragma unroll
-                    for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
-                        if (dd <= kj) { bw = bw + lv[dd]; xr = xr + ev[dd] + bw; }
-                    a.bw[(size_t)j * nx + j0] = bw;
-                    if (a.writePrimal) a.x[(size_t)j * nx + j0] = xr;
-                    a.hx[(size_t)j * ny + j0] = UNSC ? xr : spj * dyAll[(size_t)kj * ny + j0] * xr;
-                    a.hx[(size_t)j * ny + nx + j0] = UNSC ? xr : spj * dyAll[(size_t)kj * ny + nx + j0] * xr;
-                }
-            }
-        }
+    const HxSink<T, UNSC> sink{a.hx, a.tr.sqrtp, a.tr.dy, a.ny, a.nx, a.tr.sqrtp[ntop]};   // p is constant along a chain
+    down_chain_walk<T, PF, !UNSC>(a, s, a.N, foldCrown != 0, anc, writer, par, a.writePrimal != 0, crownWriter ? a.nu + a.nx : (int)threadIdx.x, sink);
+    if (crownWriter) {      // (the grid has these workgroups when foldCrown == 2 only, one per crown node)
+        const int j = (int)blockIdx.x - a.K;
+        down_crown_path<T>(a, j, a.tr.stageOf[j], sink);
     }
 }
 template <typename T>
@@ -1006,14 +1057,9 @@ __global__ void __launch_bounds__(CHAIN_THREADS, 2) k_down_chain_dual(SweepArgs<
     const int r0 = crownWriter ? 0 : (int)((long long)part * L / P), r1 = crownWriter ? 0 : (int)((long long)(part + 1) * L / P);
     const int kEnd = top + r1;                         // stages [top, kEnd) are walked
     const bool primalWg = part == P - 1, crownRowsWg = part == 0;
-    const bool AF = (a.lin & 4) != 0;       // the affine terms ride in lvb: neither uhat nor eb is requested (k_down_chain)
     const int ntop = a.chain0 + s;
     const size_t nodeTop = (size_t)ntop;
     const T sp = a.tr.sqrtp[ntop];
-    const T *__restrict__ lvb = a.lvb;
-    const T *__restrict__ uhat = a.uhat;
-    const T *__restrict__ eb = a.eb;
-    const T *__restrict__ dyAll = a.tr.dy;
     int anc[CROWN_MAX_DEPTH];
     bool writer[CROWN_MAX_DEPTH];
     {      // the crown path from the per-chain table (k_down_chain: one scalar load instead of a chase of dependent ones)
@@ -1030,140 +1076,16 @@ __global__ void __launch_bounds__(CHAIN_THREADS, 2) k_down_chain_dual(SweepArgs<
         for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++) if ((int)threadIdx.x == dd && writer[dd]) nd = anc[dd];
         sh_rowNode[threadIdx.x] = nd;
     }
-    // ---- phase A: the walk (k_down_chain, foldCrown 1 / 2), the PRIMAL values (x | x | u) of the rows into LDS: phase B applies the scaling
-    // sqrt(p_i) d_k -- it has that factor in registers for the bounds anyway, the product is the same two roundings (k_down_chain UNSC) -- so the walk
-    // requests no preconditioner entries, and Hx, when it is asked for (writePrimal), is stored by the workgroup that updates the row
-    auto put = [&](int row, int c, T val) { shx[(size_t)row * ny + c] = val; };
-    for (int t = crownWriter ? w : (int)threadIdx.x; t < w; t += CHAIN_THREADS) {
-        if (t < nu) {
-            T dv[CHAIN_PF], uh2[CHAIN_PF];
-            auto request = [&](int k) {
-#pragma unroll
-                for (int j = 0; j < CHAIN_PF; j++) {
-                    const int kk = k + j < kEnd ? k + j : kEnd - 1;
-                    const size_t node = nodeTop + (size_t)(kk - top) * a.K;
-                    dv[j] = lvb[node * w + t];
-                    uh2[j] = AF ? (T)0 : uhat[node * nu + t];
-                }
-            };
-            if (kEnd > top) request(top);          // needs nothing but the chain's number: requested first (k_down_chain)
-            T run = AF ? a.prevU[t] : a.prevU[t] - a.prevUhat[t];
-            T lv[CROWN_MAX_DEPTH], uh[CROWN_MAX_DEPTH];
-#pragma unroll
-            for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
-                if (dd < top) { lv[dd] = lvb[(size_t)anc[dd] * w + t]; uh[dd] = AF ? (T)0 : uhat[(size_t)anc[dd] * nu + t]; }
-#pragma unroll
-            for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
-                if (dd < top) {
-                    const int k = top - 1 - dd;
-                    const T uv = uh[dd] + run + lv[dd];
-                    run = uv - uh[dd];
-                    if (writer[dd]) {
-                        if (a.writePrimal) a.u[(size_t)anc[dd] * nu + t] = uv;
-                        put(L + dd, 2 * nx + t, uv);
-                    }
-                }
-            for (int k = top; k < kEnd; k += CHAIN_PF) {
-#pragma unroll
-                for (int j = 0; j < CHAIN_PF; j++) {
-                    if (k + j < kEnd) {
-                        const size_t node = nodeTop + (size_t)(k + j - top) * a.K;
-                        run += dv[j];
-                        const T uv = uh2[j] + run;
-                        if (a.writePrimal && primalWg) a.u[node * nu + t] = uv;
-                        put(k + j - top, 2 * nx + t, uv);
-                    }
-                }
-                if (k + CHAIN_PF < kEnd) request(k + CHAIN_PF);
-            }
-        } else {
-            const int j0 = t - nu;
-            T dv[CHAIN_PF], ev[CHAIN_PF];
-            auto request = [&](int k) {
-#pragma unroll
-                for (int j = 0; j < CHAIN_PF; j++) {
-                    const int kk = k + j < kEnd ? k + j : kEnd - 1;
-                    const size_t node = nodeTop + (size_t)(kk - top) * a.K;
-                    dv[j] = lvb[node * w + nu + j0];
-                    ev[j] = AF ? (T)0 : eb[node * nx + j0];
-                }
-            };
-            if (kEnd > top) request(top);
-            T bw = a.bw0[j0], xr = a.curX[j0];
-            T lv[CROWN_MAX_DEPTH], ev0[CROWN_MAX_DEPTH];
-#pragma unroll
-            for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
-                if (dd < top) { lv[dd] = lvb[(size_t)anc[dd] * w + nu + j0]; ev0[dd] = AF ? (T)0 : eb[(size_t)anc[dd] * nx + j0]; }
-#pragma unroll
-            for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
-                if (dd < top) {
-                    const int k = top - 1 - dd;
-                    bw = bw + lv[dd];
-                    xr = xr + ev0[dd] + bw;
-                    if (writer[dd]) {
-                        a.bw[(size_t)anc[dd] * nx + j0] = bw;
-                        if (a.writePrimal) a.x[(size_t)anc[dd] * nx + j0] = xr;
-                        put(L + dd, j0, xr);
-                        put(L + dd, nx + j0, xr);
-                    }
-                }
-            for (int k = top; k < kEnd; k += CHAIN_PF) {
-#pragma unroll
-                for (int j = 0; j < CHAIN_PF; j++) {
-                    if (k + j < kEnd) {
-                        const size_t node = nodeTop + (size_t)(k + j - top) * a.K;
-                        bw += dv[j];
-                        xr += ev[j] + bw;
-                        if (a.writePrimal && primalWg) a.x[node * nx + j0] = xr;
-                        put(k + j - top, j0, xr);
-                        put(k + j - top, nx + j0, xr);
-                    }
-                }
-                if (k + CHAIN_PF < kEnd) request(k + CHAIN_PF);
-            }
-        }
-    }
+    // ---- phase A: down_chain_walk, the walk of k_down_chain (foldCrown 1 / 2), with the PRIMAL values (x | x | u) of the rows into LDS: phase B applies
+    // the scaling sqrt(p_i) d_k -- it has that factor in registers for the bounds anyway, the product is the same two roundings (k_down_chain UNSC) -- so
+    // the walk requests no preconditioner entries, and Hx, when it is asked for (writePrimal), is stored by the workgroup that updates the row.
+    // kEnd > top on every chain workgroup: the host clamps P to L (Ctx::fuse_split), so r1 >= 1 -- the walk's first request needs that.
+    const LdsPrimalSink<T> sink{shx, ny, nx, crownWriter ? 0 : L};
+    down_chain_walk<T, CHAIN_PF, false>(a, s, kEnd, true, anc, writer, 0, a.writePrimal && primalWg, crownWriter ? w : (int)threadIdx.x, sink);
     int cwNode = -1, cwStage = 0;
     if (crownWriter) {      // sharded runs (foldCrown = 2): this workgroup writes crown node j (root -> j walk), row 0
-        const int j = (int)blockIdx.x - a.K * P;
-        cwNode = j; cwStage = a.tr.stageOf[j];
-        const int kj = cwStage;
-        int pth[CROWN_MAX_DEPTH];
-        {
-            int n = j;
-#pragma unroll
-            for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++) { pth[dd] = n; if (dd < kj) n = a.tr.parent[n]; }
-        }
-        const T spj = a.tr.sqrtp[j];
-        for (int t = threadIdx.x; t < w; t += CHAIN_THREADS) {
-            if (t < nu) {
-                T run = AF ? a.prevU[t] : a.prevU[t] - a.prevUhat[t];
-                T lv[CROWN_MAX_DEPTH], uh[CROWN_MAX_DEPTH];
-#pragma unroll
-                for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
-                    if (dd <= kj) { lv[dd] = lvb[(size_t)pth[dd] * w + t]; uh[dd] = AF ? (T)0 : uhat[(size_t)pth[dd] * nu + t]; }
-                T uv = 0;
-#pragma unroll
-                for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
-                    if (dd <= kj) { uv = uh[dd] + run + lv[dd]; run = uv - uh[dd]; }
-                if (a.writePrimal) a.u[(size_t)j * nu + t] = uv;
-                put(0, 2 * nx + t, uv);
-            } else {
-                const int j0 = t - nu;
-                T bw = a.bw0[j0], xr = a.curX[j0];
-                T lv[CROWN_MAX_DEPTH], ev[CROWN_MAX_DEPTH];
-#pragma unroll
-                for (int dd = 0; dd < CROWN_MAX_DEPTH; dd++)
-                    if (dd <= kj) { lv[dd] = lvb[(size_t)pth[dd] * w + nu + j0]; ev[dd] = AF ? (T)0 : eb[(size_t)pth[dd] * nx + j0]; }
-#pragma unroll
-                for (int dd = CROWN_MAX_DEPTH - 1; dd >= 0; dd--)
-                    if (dd <= kj) { bw = bw + lv[dd]; xr = xr + ev[dd] + bw; }
-                a.bw[(size_t)j * nx + j0] = bw;
-                if (a.writePrimal) a.x[(size_t)j * nx + j0] = xr;
-                put(0, j0, xr);
-                put(0, nx + j0, xr);
-            }
-        }
+        cwNode = (int)blockIdx.x - a.K * P; cwStage = a.tr.stageOf[cwNode];
+        down_crown_path<T>(a, cwNode, cwStage, sink);
     }
     __syncthreads();
     // ---- phase B: the dual update of the rows' elements (dual_slot_use's arithmetic; LAZY = 0)
@@ -1243,25 +1165,7 @@ __global__ void __launch_bounds__(CHAIN_THREADS, 2) k_down_chain_dual(SweepArgs<
         __syncthreads();
         up_chain_lin_walk<T>(a, s, shx, (int)threadIdx.x, CHAIN_THREADS);
     }
-    double valXi = r.valXi, valPsi = r.valPsi;
-    long long idxXi = r.idxXi == 0xffffffffu ? 0x7fffffffffffffffLL : (long long)r.idxXi;
-    long long idxPsi = r.idxPsi == 0xffffffffu ? 0x7fffffffffffffffLL : (long long)r.idxPsi;
-    double absXi = r.idxXi == 0xffffffffu ? -1.0 : fabs(valXi), absPsi = r.idxPsi == 0xffffffffu ? -1.0 : fabs(valPsi);
-    const double d2x = wave_sum_f64(r.d2x), d2s = wave_sum_f64(r.d2s);
-    wave_argmax(absXi, valXi, idxXi);
-    wave_argmax(absPsi, valPsi, idxPsi);
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) sh_p[wave] = Partial{d2x, d2s, absXi, valXi, absPsi, valPsi, idxXi, idxPsi};
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        Partial p = sh_p[0];
-        for (int k = 1; k < CHAIN_THREADS / 64; k++) {
-            p.d2x += sh_p[k].d2x; p.d2s += sh_p[k].d2s;
-            better(p.absXi, p.valXi, p.idxXi, sh_p[k].absXi, sh_p[k].valXi, sh_p[k].idxXi);
-            better(p.absPsi, p.valPsi, p.idxPsi, sh_p[k].absPsi, sh_p[k].valPsi, sh_p[k].idxPsi);
-        }
-        da.partials[blockIdx.x] = p;
-    }
+    dual_acc_store(r, sh_p, da.partials + blockIdx.x);
 }
 
 
