@@ -101,6 +101,8 @@ enum {
     RN_BUF_LBFGS_DIR_XI, RN_BUF_LBFGS_DIR_PSI,             /* devVecLbfgsDirXi / Psi                                    */
     RN_BUF_PRIMAL_XI_DIR, RN_BUF_PRIMAL_PSI_DIR,           /* devVecPrimalXiDir / PsiDir                                */
     RN_BUF_XDIR, RN_BUF_UDIR,                              /* devVecXdir nodes*nx, devVecUdir nodes*nu                  */
+    /* Extension (rn_solve_certificate): x(y), u(y) of the last certificate, nodes*nx and nodes*nu; size 0 before the first; read-only */
+    RN_BUF_CERT_X, RN_BUF_CERT_U,
     RN_BUF_COUNT
 };
 
@@ -454,6 +456,43 @@ int rn_get_lipschitz(rn_ctx *ctx, double out[RN_LIP_COLS], int *stale);
 enum { RN_STEP_FIXED = 0, RN_STEP_LIPSCHITZ = 1 };
 int rn_set_step_rule(rn_ctx *ctx, int rule, double margin /* (0,1] */, int iterations /* <=0: 40 */);
 int rn_get_step_rule(rn_ctx *ctx, int *rule, double *margin, int *iterations, double *stepSizeInForce);
+
+/* ---- the solve certificate: dual bound and optimality gap of the multiplier at hand ---------------------------------------------------
+ * Extension.  Built on the reference's solveStep (SmpcController.cu:563-755: the minimiser of the Lagrangian), proximalFunG (:759-835: the
+ * sets and penalties of g) and computeValueFbe (:1066-1146: the primal terms sum_i p_i (du' W du + alpha' u)); the reference itself reports
+ * no bound.  In the scaled space of the sweep and the prox (DESIGN.md "the solve certificate"): f(z) = sum_i p_i (du_i' W du_i + alpha_i' u_i) on
+ * the dynamics, Hz = (F_i x_i, G_i u_i), g = gamma_x dist(., [xmin, xmax]) + gamma_s dist(., {>= xs}) + indicator of [umin, umax], both
+ * distances tree-global.  y = (xi_b, xi_s, psi) is the multiplier the context would warm-start from: what rn_get(RN_BUF_UPD_XI / _UPD_PSI)
+ * shows.  z(y) is the minimiser of the Lagrangian at y: one sweep at y, on the context's stream, in the operator form in force.
+ *   COST    f(z(y))                                  INNER   <xi, F x> + <psi, G u>
+ *   SUPPORT sum max(xi_b xmin, xi_b xmax) + sum xi_s xs + sum max(psi umin, psi umax)
+ *   DUAL    COST + INNER - SUPPORT: a lower bound of the optimal value when VALID = 1
+ *   NORM_X  |xi_b|_2   NORM_S  |xi_s|_2   XIS_POS  max(xi_s, 0) over all entries
+ *   VALID   1 when NORM_X <= gamma_x (1 + 4 2^-53 sqrt(n)), the same for NORM_S with gamma_s, and XIS_POS <= 2^-53 NORM_S (n: entries of one
+ *           half over the whole tree); else 0 -- y is outside the domain of g* -- and DUAL is still the number above, never -inf
+ *   DIST_X, DIST_S  distances of Hz(y) from the two x sets    PRIMAL  COST + gamma_x DIST_X + gamma_s DIST_S
+ *   U_EXCESS  largest violation of the u box by u(y), physical units, on the bounds table in force (rn_set_bounds)
+ *   GAP     PRIMAL - DUAL: an upper bound of the suboptimality of z(y) ONLY when U_EXCESS = 0 (and VALID = 1)
+ *   ABS_TERMS  sum of the absolute values of the terms of COST (per node: p_i |alpha_i' u_i| + p_i |du_i' W du_i|), INNER and SUPPORT (per
+ *           entry): the scale on which DUAL, PRIMAL and GAP are judged
+ * The scaled bounds are formed as the dual update forms them (sqrt(p_i) d_c times the row of the table in force, in the context's type);
+ * gamma_x, gamma_s are rn_set_parameters' penalties.  After rn_apg_reset, before any iteration, y = 0: DUAL is the unconstrained minimum.
+ * Arithmetic: every product and sum in fp64 whatever the context's precision, one fixed order (k_certificate, k_plan.hpp; COST: a node's
+ *   terms as rn_plan_report's node phase sums them, then the nodes), no floating-point atomics: two calls give the same bits.
+ * State: the call leaves every other RN_BUF_*, the batch state, the history and the checkpoints bit for bit; the next rn_apg_iterate continues
+ *   as if it had not happened.  It does change what rn_algorithmic_bytes / rn_debug_stream_live report as "the most recent launch" (the
+ *   sweep at y is one).  The first call allocates buffers of the certificate's own (about 2 nx + 2 nu + nv + 9 reals per node) and keeps them;
+ *   later calls allocate nothing, a context that never asks allocates and launches nothing.  RN_BUF_CERT_X / RN_BUF_CERT_U hold x(y), u(y) afterwards.
+ * rn_solve_certificate synchronises once; rn_solve_certificate_device leaves the record (RN_CERT_COLS doubles, device memory, valid until
+ *   the next certificate on this context) and does not synchronise.
+ * Sharded contexts: every rank calls; the sums are all-reduced with the replicated crown counted on one rank, U_EXCESS and XIS_POS by MAX;
+ *   every rank holds the same bits.
+ * Errors: RN_E_STATE before the affine terms of a control step exist or before rn_apg_reset, after a batch that failed half-way, on a cut
+ *   context of several ranks without a communicator, and while the algorithm is global FBE or NAMA (their multiplier is another buffer). */
+enum { RN_CERT_DUAL = 0, RN_CERT_PRIMAL, RN_CERT_GAP, RN_CERT_COST, RN_CERT_INNER, RN_CERT_SUPPORT, RN_CERT_DIST_X, RN_CERT_DIST_S,
+       RN_CERT_U_EXCESS, RN_CERT_NORM_X, RN_CERT_NORM_S, RN_CERT_XIS_POS, RN_CERT_ABS_TERMS, RN_CERT_VALID, RN_CERT_COLS = 16 };
+int rn_solve_certificate(rn_ctx *ctx, double out[RN_CERT_COLS]);
+int rn_solve_certificate_device(rn_ctx *ctx, void **record);
 
 /* step-wise entry points mirroring the protected methods the reference's known-answer tests call */
 int rn_dual_extrapolation_step(rn_ctx *ctx, double lambda); /* SmpcController.cu:535-557  */

@@ -115,6 +115,11 @@ int rn_debug_restart_test(rn_ctx *ctx, double out[3]);
  * context made by rn_create_sharded): E [nParents][nd], P [nParents], widened from the context's type.  RN_E_STATE while none are set. */
 int rn_debug_cut_moments(rn_ctx *ctx, double *E, double *P, size_t nParents);
 
+/* Hz(y) = (F x(y), G u(y)) as the sweep of the last rn_solve_certificate left it and as k_certificate read it: hzXi [nodes][2 nx], hzPsi
+ * [nodes][nu], widened from the context's type -- so that a test can hand the kernel's own inputs to a restatement of the record.
+ * RN_E_STATE before the first certificate.  Changes nothing. */
+int rn_debug_certificate_hz(rn_ctx *ctx, double *hzXi, double *hzPsi);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,7 +47,7 @@ UNITS = {
     "k_misc": ["common.hpp", "k_misc.hpp", "k_plan.hpp"],
     "k_fbe": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "fbe_kernels.hpp"],
     "rapidnet_capi": ["common.hpp", "k_dual.hpp", "k_walks.hpp", "k_slab.hpp", "k_stream.hpp", "stream_bits.hpp", "k_misc.hpp", "k_plan.hpp", "kernels.hpp", "fbe_kernels.hpp", "fbe_methods.inc",
-                      "sweep.inc", "caller_data.inc", "plan_report.inc", "plan_bands.inc", "shift_warm_start.inc", "lipschitz.inc", "partition.hpp", "bounds.hpp", "bands_host.hpp", "shift_map.hpp"],
+                      "sweep.inc", "caller_data.inc", "plan_report.inc", "plan_bands.inc", "shift_warm_start.inc", "lipschitz.inc", "certificate.inc", "partition.hpp", "bounds.hpp", "bands_host.hpp", "shift_map.hpp"],
 }
 OBJ_DIR = os.path.join(HERE, "build")
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-pass-failed"]
@@ -169,6 +169,7 @@ TEST_PLAN_BANDS = os.path.join(BIN_DIR, "test_plan_bands")
 TEST_BANDS_HOST = os.path.join(BIN_DIR, "test_bands_host")
 TEST_SHIFT_WARM_START = os.path.join(BIN_DIR, "test_shift_warm_start")
 TEST_LIPSCHITZ = os.path.join(BIN_DIR, "test_lipschitz")
+TEST_CERTIFICATE = os.path.join(BIN_DIR, "test_certificate")
 
 
 def build_host(force=False):
@@ -255,6 +256,11 @@ def build_host(force=False):
         subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_LIPSCHITZ, test_src, "-L" + HERE, "-lrapidnet_host",
                                "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
         _stamp(TEST_LIPSCHITZ, [test_src] + deps + hdr)
+    test_src = os.path.join(ROOT, "tests", "cpp", "test_certificate.cpp")
+    if force or _stale(TEST_CERTIFICATE, [test_src] + deps + hdr):
+        subprocess.check_call(["g++", "-std=c++14", "-O2", "-Wall", "-o", TEST_CERTIFICATE, test_src, "-L" + HERE, "-lrapidnet_host",
+                               "-lrapidnet_hip", "-Wl,-rpath,$ORIGIN/.."])
+        _stamp(TEST_CERTIFICATE, [test_src] + deps + hdr)
     return LIB_HOST
 
 

@@ -15,7 +15,7 @@ RN_F32, RN_F64 = 0, 1
  BUF_XMIN, BUF_XMAX, BUF_XS, BUF_UMIN, BUF_UMAX,
  BUF_PREV_XI, BUF_PREV_PSI, BUF_LBFGS_CUR_YVEC_XI, BUF_LBFGS_CUR_YVEC_PSI, BUF_LBFGS_PREV_YVEC_XI,
  BUF_LBFGS_PREV_YVEC_PSI, BUF_LBFGS_DIR_XI, BUF_LBFGS_DIR_PSI, BUF_PRIMAL_XI_DIR, BUF_PRIMAL_PSI_DIR,
- BUF_XDIR, BUF_UDIR) = range(36)
+ BUF_XDIR, BUF_UDIR, BUF_CERT_X, BUF_CERT_U) = range(38)
 ALG_APG, ALG_GLOBAL_FBE, ALG_NAMA = 0, 1, 2
 ALGORITHMS = {"proximalAlgorithm": ALG_APG, "globalFbeAlgorithm": ALG_GLOBAL_FBE, "namaAlgorithm": ALG_NAMA}  # Engine.cu:151-163
 OP_PHI, OP_PSI, OP_D, OP_F, OP_OMEGA, OP_THETA, OP_G = range(7)
@@ -30,6 +30,9 @@ RESTARTS = {"off": RESTART_OFF, "gradient": RESTART_GRADIENT}
 STEP_FIXED, STEP_LIPSCHITZ = 0, 1       # rn_set_step_rule
 STEP_RULES = {"fixed": STEP_FIXED, "lipschitz": STEP_LIPSCHITZ}
 LIP_COLUMNS = ("norm", "rayleigh", "residual", "iterations")      # rn_estimate_lipschitz, RN_LIP_*
+# rn_solve_certificate: the named columns of the record, in the order of RN_CERT_* (the record is padded to CERT_COLS doubles)
+CERT_COLUMNS = ("dual", "primal", "gap", "cost", "inner", "support", "distX", "distS", "uExcess", "normX", "normS", "xisPos", "absTerms", "valid")
+CERT_COLS = 16
 BOUNDS_SHARED, BOUNDS_PER_STAGE, BOUNDS_PER_NODE = 0, 1, 2      # rn_set_bounds
 BOUNDS = {"shared": BOUNDS_SHARED, "stage": BOUNDS_PER_STAGE, "node": BOUNDS_PER_NODE}
 # include/rapidnet_debug.h, RN_KNOB_*
@@ -65,6 +68,7 @@ SYMBOLS = [
     "rn_plan_quantiles", "rn_plan_quantiles_device", "rn_plan_paths",
     "rn_shift_warm_start", "rn_set_shift_map", "rn_get_shift_map",
     "rn_estimate_lipschitz", "rn_get_lipschitz", "rn_set_step_rule", "rn_get_step_rule",
+    "rn_solve_certificate", "rn_solve_certificate_device", "rn_debug_certificate_hz",
 ]
 
 
@@ -278,6 +282,9 @@ def load():
     lib.rn_get_shift_map.argtypes = [vp, ip, C.c_size_t, dp]
     lib.rn_estimate_lipschitz.argtypes = [vp, ip, C.c_double, ip, dp, dp, C.c_ulonglong, dp, dp]
     lib.rn_get_lipschitz.argtypes = [vp, dp, C.POINTER(C.c_int)]
+    lib.rn_solve_certificate.argtypes = [vp, dp]
+    lib.rn_solve_certificate_device.argtypes = [vp, C.POINTER(C.c_void_p)]
+    lib.rn_debug_certificate_hz.argtypes = [vp, dp, dp]
     lib.rn_set_step_rule.argtypes = [vp, ip, C.c_double, ip]
     lib.rn_get_step_rule.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double)]
     _LIB = lib
@@ -838,6 +845,28 @@ class Solver:
         a, b, n = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
         self._check(self.lib.rn_plan_report_device(self.h, C.byref(a), C.byref(b), C.byref(n)))
         return a.value, b.value, n.value
+
+    # ---- dual bound and optimality gap of the multiplier at hand (rn_solve_certificate ...) ------------------------
+    def solveCertificate(self):
+        """rn_solve_certificate: {column: value} for CERT_COLUMNS at y = (BUF_UPD_XI, BUF_UPD_PSI).  "dual" is a lower bound of the optimal
+        value only with "valid" == 1; "gap" bounds the suboptimality of z(y) only with "uExcess" == 0.  One sweep plus two launches and one
+        synchronisation; the solve continues as if the call had not happened.  BUF_CERT_X / BUF_CERT_U hold x(y), u(y) afterwards."""
+        out = np.zeros(CERT_COLS)
+        self._check(self.lib.rn_solve_certificate(self.h, out.ctypes.data))
+        return dict(zip(CERT_COLUMNS, (float(v) for v in out)))
+
+    def solveCertificateDevice(self):
+        """rn_solve_certificate_device: the address of the record (CERT_COLS doubles, device memory), valid until the next certificate;
+        nothing is waited for"""
+        a = C.c_void_p()
+        self._check(self.lib.rn_solve_certificate_device(self.h, C.byref(a)))
+        return a.value
+
+    def debugCertificateHz(self):
+        """rn_debug_certificate_hz (include/rapidnet_debug.h): (Hz_xi [nodes * 2 nx], Hz_psi [nodes * nu]) of the last certificate's sweep"""
+        a, b = np.zeros(self.nodes * 2 * self.nx), np.zeros(self.nodes * self.nu)
+        self._check(self.lib.rn_debug_certificate_hz(self.h, a.ctypes.data, b.ctypes.data))
+        return a, b
 
     # ---- what the plan at hand looks like across the tree (rn_plan_quantiles, rn_plan_paths) -----------------------
     def _band(self, which):

@@ -48,6 +48,8 @@
             case RN_BUF_ALPHA: *n = N_ * d.nu; return d_alpha;
             case RN_BUF_XDIR: *n = d_xdir ? N_ * d.nx : 0; return d_xdir;
             case RN_BUF_UDIR: *n = d_udir ? N_ * d.nu : 0; return d_udir;
+            case RN_BUF_CERT_X: *n = certTaken ? N_ * d.nx : 0; return certTaken ? d_certX : nullptr;      // (rn_solve_certificate: x(y), u(y); read-only)
+            case RN_BUF_CERT_U: *n = certTaken ? N_ * d.nu : 0; return certTaken ? d_certU : nullptr;
             default: *n = 0; return nullptr;
         }
     }
@@ -119,6 +121,10 @@
         if (id == RN_BUF_V) {
             if (write && whole) vPending = false;
             else if (int rc = v_flush()) return rc;
+        }
+        if (id == RN_BUF_CERT_X || id == RN_BUF_CERT_U) {
+            RN_CHECK(!write, RN_E_ARG, fn + ": the certificate's x(y), u(y) are read-only");
+            RN_CHECK(certTaken, RN_E_ARG, fn + ": no certificate was taken yet (rn_solve_certificate): the buffer is empty");
         }
         T *p = plain(id, &cnt);
         RN_CHECK(p != nullptr, RN_E_ARG, fn + ": unknown buffer id");

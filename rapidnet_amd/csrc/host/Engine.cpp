@@ -133,6 +133,7 @@ void Engine::evaluatePlan(PlanReport &r) {
     check(rn_plan_report(ctx, r.stages, r.perStage.data()), "rn_plan_report");
     check(rn_plan_report_scenarios(ctx, r.scenarios, r.perScenario.data(), r.leafNode.data()), "rn_plan_report_scenarios");
 }
+void Engine::solveCertificate(real_t out[RN_CERT_COLS]) { check(rn_solve_certificate(ctx, out), "rn_solve_certificate"); }
 void Engine::planQuantiles(int which, const std::vector<real_t> &levels, std::vector<real_t> &out) {
     const size_t stages = ptrMyScenarioTree->getPredHorizon(), dim = which == RN_BAND_U ? ptrMySmpcConfig->getNU() : ptrMySmpcConfig->getNX();
     out.assign(stages * dim * levels.size(), 0.0);

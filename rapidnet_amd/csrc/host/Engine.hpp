@@ -107,6 +107,11 @@ public:
     };
     size_t getNumLocalScenarios();                   // local nodes at the last stage: the rows of PlanReport::perScenario
     void evaluatePlan(PlanReport &report);
+    // Dual bound and optimality gap of the multiplier the engine would warm-start from (rapidnet.h, rn_solve_certificate; the reference reports
+    // none): out[RN_CERT_DUAL] is a lower bound of the optimal expected cost when out[RN_CERT_VALID] is 1, out[RN_CERT_GAP] bounds the
+    // suboptimality of the plan one gradient step past the last iterate only when out[RN_CERT_U_EXCESS] is 0.  One sweep; the solve goes on as
+    // if nobody had asked.  After a solve (APG only); on a sharded engine every rank calls it and all hold the same bits.
+    void solveCertificate(real_t out[RN_CERT_COLS]);
     // What the plan looks like across the tree (rapidnet.h, rn_plan_quantiles / rn_plan_paths; the reference has no counterpart): weighted
     // quantiles of every component of x (RN_BAND_X) or u (RN_BAND_U) per stage at `levels`, out [stages][dim][levels]; and the rows along
     // every scenario's path, out [scenarios][stages][dim] with leafNode [scenarios], the node of the whole tree each path ends in.  After

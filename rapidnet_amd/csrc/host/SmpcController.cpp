@@ -114,6 +114,23 @@ uint_t SmpcController::writePlanReport(std::fstream &out) {
     out.precision(digits);
     return 1;
 }
+const std::vector<real_t> &SmpcController::getSolveCertificate() {
+    solveCertificate.assign(RN_CERT_COLS, 0.0);
+    ptrMyEngine->solveCertificate(solveCertificate.data());
+    return solveCertificate;
+}
+uint_t SmpcController::writeSolveCertificate(std::fstream &out) {
+    if (!out.is_open()) return 0;
+    static const char *const columns[RN_CERT_VALID + 1] = {"dual", "primal", "gap", "cost", "inner", "support", "distX", "distS", "uExcess", "normX", "normS",
+                                                           "xisPos", "absTerms", "valid"};
+    const std::vector<real_t> &r = getSolveCertificate();
+    const std::streamsize digits = out.precision(17);
+    out << "\"solveCertificate\" : {";
+    for (int c = 0; c <= RN_CERT_VALID; c++) out << (c ? ", " : "") << "\"" << columns[c] << "\": " << r[c];
+    out << "}" << std::endl;
+    out.precision(digits);
+    return 1;
+}
 const SmpcController::PlanBands &SmpcController::getPlanBands(const std::vector<real_t> &levels) {
     PlanBands &b = planBands;
     b.stages = ptrMyEngine->getScenarioTree()->getPredHorizon();

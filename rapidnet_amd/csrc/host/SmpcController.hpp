@@ -70,6 +70,10 @@ public:
     // ... written as one more entry of the control output: "planReport" : {"columns": [...], "perStage": [[...]], "leafNode": [...],
     // "perScenario": [[...]]}, a JSON object with 17 significant digits.  controlAction(fstream&)'s own output is unchanged.
     uint_t writePlanReport(std::fstream &controlOutputJson);
+    // Dual bound and optimality gap of the solve at hand (Engine::solveCertificate): the record by column RN_CERT_*, and written as one more
+    // entry of the control output: "solveCertificate" : {"dual": ..., "primal": ..., "gap": ..., ..., "valid": ...}.  AFTER controlAction.
+    const std::vector<real_t> &getSolveCertificate();
+    uint_t writeSolveCertificate(std::fstream &controlOutputJson);
     // What the plan of the last control step looks like across the tree (Engine::planQuantiles / planPaths, rapidnet.h rn_plan_quantiles):
     // the fan chart of every tank level and pump flow -- quantiles per stage at `levels` -- and every scenario's trajectory.  To be called
     // AFTER controlAction, like getPlanReport: the first call allocates its tables on the device and keeps them.
@@ -130,6 +134,7 @@ protected:
     std::vector<real_t> vecPrimalInfs, vecValueFbe, vecTau, lastControl;
     real_t economicKpi, smoothKpi, safeKpi, networkKpi;
     Engine::PlanReport planReport;
+    std::vector<real_t> solveCertificate;
     PlanBands planBands;
     uint_t controlSteps = 0;      // control steps solved so far ("warmStart": "shift" moves the duals before every one but the first)
     void shiftBeforeStep();

@@ -703,13 +703,21 @@ __global__ void __launch_bounds__(ELT_THREADS) k_absmax(const T *res, long long 
 
 // Hx from the primal values k_down_chain<T, true> left in its place (every node): hx = (sqrt(p_i) d_k) * value -- the expression of
 // k_dual_stage<..., SCALE>; only for a consumer of Hx other than that kernel behind an unscaled walk (does not happen in the batch loops as they are).
+// The element type arrives as a flag and not as a template parameter (one kernel instead of two, as k_extrapolate<0>: the launch is outside the
+// batch loops); the arithmetic is the typed one, bit for bit.
 template <typename T>
-__global__ void __launch_bounds__(ELT_THREADS) k_hx_scale(T *hx, const T *sqrtp, const T *dy, const int *stageOf, int ny, long long total) {
+__device__ __forceinline__ void hx_scale_body(void *hx_, const void *sqrtp_, const void *dy_, const int *stageOf, int ny, long long total) {
+    T *hx = static_cast<T *>(hx_);
+    const T *sqrtp = static_cast<const T *>(sqrtp_), *dy = static_cast<const T *>(dy_);
     for (long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x; i < total; i += (long long)gridDim.x * ELT_THREADS) {
         const long long node = i / ny;
         const int r = (int)(i - node * ny);
         hx[i] = (sqrtp[node] * dy[(size_t)stageOf[node] * ny + r]) * hx[i];
     }
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void __launch_bounds__(ELT_THREADS) k_hx_scale(void *hx, const void *sqrtp, const void *dy, const int *stageOf, int ny, long long total, int f64) {
+    if (f64) hx_scale_body<double>(hx, sqrtp, dy, stageOf, ny, total); else hx_scale_body<float>(hx, sqrtp, dy, stageOf, ny, total);
 }
 
 // Opening of an optimistic batch in ONE launch: the checkpoint of (y, y+, w) the exact replay would start from, the verdict flag cleared, and -- sharded

@@ -420,4 +420,176 @@ __global__ void __launch_bounds__(BANDS_THREADS) k_plan_bands(BandsArgs a) {
     else { if (a.f64) bands_pack_body<double>(a); else bands_pack_body<float>(a); }
 }
 
+// ------------------------------------------------------------------------------------------------------
+// rn_solve_certificate / rn_solve_certificate_device (include/rapidnet.h; DESIGN.md "the solve certificate"): the value of the dual function at
+// the multiplier y = (xi_b, xi_s, psi) a context would warm-start from, and the penalised primal value of the minimiser z(y) of the Lagrangian
+// there.  The reference has no counterpart (its computeValueFbe, SmpcController.cu:1066-1146, is the envelope of the FBE line search).  The host
+// runs one sweep at y into buffers of the certificate's own and k_plan_report's node phase on its x(y), u(y); this kernel then makes ONE flat
+// pass over y, Hz(y) = (F x, G u) and the bounds, and one pass over the node rows:
+//   element (node i, column c), k = sqrt(p_i) d_c in the context's type, lo = k blo_c, hi = k bhi_c as the dual update rebuilds them (k_dual_fused,
+//   regen: the prox and the certificate see the same bits), everything below in double:
+//     INNER    y h                       SUPPORT  box and psi columns max(y lo, y hi), safety columns y lo     (and the |.| of both)
+//     DIST2_X  (h - clamp(h, lo, hi))^2  DIST2_S  max(lo - h, 0)^2       NORM2_X, NORM2_S  y^2 of the two xi halves       XIS_POS  max(y, 0), safety
+//   node i, row = k_plan_report's node table: ECON p_i row[ECON], SMOOTH p_i row[SMOOTH], COST_ABS the |.| of both, U_EXCESS max row[UBOX_MAX].
+// COST's summation order is therefore: a node's alpha' u and du' W du as k_plan_report's node phase sums them, the nodes as below.
+// 16 bytes per lane and stream with a scalar tail.  Every product is formed and summed in double whatever the element type is, in a fixed
+// order -- a lane over its grid-stride positions, the wave (wave_sum_f64), the workgroup's waves in LDS, the workgroups' partials by the
+// workgroup that arrives last (agent-scope release -> ticket -> acquire: k_restart_test's reduction) -- and there are no floating-point atomics:
+// two calls give the same bits.  Sharded contexts: the leading crownElems elements / crownNodes rows are replicated on every rank and enter the
+// sums on ONE rank (countCrown); the maxima are the same everywhere.  The host sums the sum block over the ranks and takes the maxima's MAX, then
+// phase 1 derives the record; an unsharded context's last arriver derives it in the same launch (finish).
+// The element type arrives as a flag and not as a template parameter (k_restart_test's idiom); the branch is uniform over the grid.
+constexpr int CERT_INNER = 0, CERT_INNER_ABS = 1, CERT_SUPPORT = 2, CERT_SUPPORT_ABS = 3, CERT_DIST2_X = 4, CERT_DIST2_S = 5, CERT_NORM2_X = 6, CERT_NORM2_S = 7,
+              CERT_ECON = 8, CERT_SMOOTH = 9, CERT_COST_ABS = 10, CERT_COUNT = 11, CERT_SUMS = 12, CERT_UEXC = 12, CERT_XISPOS = 13, CERT_PART = 14;
+constexpr int CERT_REC = 16;       // columns of the record: RN_CERT_COLS
+struct CertArgs {
+    int phase, f64;
+    const void *y, *hz;                               // [node][ny] of T
+    const void *sqrtp, *dy, *blo, *bhi, *prob;        // of T
+    const int *stageOf;
+    int bStrideStage, bStrideNode;
+    int nx, ny, nodes;
+    long long n, crownElems;
+    int crownNodes, countCrown;
+    const double *node;           // [nodes][PLAN_COLS]: k_plan_report's node phase on x(y), u(y)
+    double gammaX, gammaS;
+    double count;                 // entries of one xi half this rank counts
+    double *partials;             // [gridDim.x][CERT_PART]
+    unsigned int *ticket;         // arrival counter: the host zeroes it on the stream in front of every launch
+    double *sums;                 // [CERT_PART]: the sum block, the two maxima behind it
+    double *rec;                  // [CERT_REC]
+    int finish;                   // phase 0: the last arriver derives the record as well
+};
+template <typename T>
+__device__ __forceinline__ void cert_elem(const CertArgs &a, T yv, T hv, int node, int c, bool counted, double *s, double &xisPos) {
+#pragma clang fp contract(off)
+    const T *const sqrtp = static_cast<const T *>(a.sqrtp), *const dy = static_cast<const T *>(a.dy);
+    const T *const blo = static_cast<const T *>(a.blo), *const bhi = static_cast<const T *>(a.bhi);
+    const int stg = a.stageOf[node], bc = stg * a.bStrideStage + node * a.bStrideNode + c;
+    const bool box = c < a.nx, safe = !box && c < 2 * a.nx;
+    const T k = sqrtp[node] * dy[(size_t)stg * a.ny + c];
+    const T loT = k * blo[bc], hiT = safe ? (T)0 : k * bhi[bc];      // (the safety half has no upper bound)
+    const double lo = (double)loT, hi = (double)hiT, y = (double)yv, h = (double)hv;
+    const double ti = y * h, tl = y * lo, th = y * hi;
+    const double ts = safe ? tl : (tl > th ? tl : th);
+    double d = 0.0;
+    if (box) d = h < lo ? lo - h : (h > hi ? h - hi : 0.0);
+    else if (safe) d = h < lo ? lo - h : 0.0;
+    const double d2 = d * d, y2 = y * y;
+    if (counted) {
+        s[CERT_INNER] += ti; s[CERT_INNER_ABS] += fabs(ti); s[CERT_SUPPORT] += ts; s[CERT_SUPPORT_ABS] += fabs(ts);
+        s[CERT_DIST2_X] += box ? d2 : 0.0; s[CERT_DIST2_S] += safe ? d2 : 0.0;
+        s[CERT_NORM2_X] += box ? y2 : 0.0; s[CERT_NORM2_S] += safe ? y2 : 0.0;
+    }
+    if (safe && y > xisPos) xisPos = y;
+}
+// a lane's sums over its grid-stride positions of the flat range and of the node rows
+template <typename T>
+__device__ __forceinline__ void cert_lane_sums(const CertArgs &a, double *s, double &uExc, double &xisPos) {
+#pragma clang fp contract(off)
+    typedef typename VecOf<T>::type VT;
+    constexpr int VN = VecOf<T>::N;
+    const T *const ay = static_cast<const T *>(a.y), *const ah = static_cast<const T *>(a.hz), *const prob = static_cast<const T *>(a.prob);
+    const long long stride = (long long)gridDim.x * ELT_THREADS, gid = (long long)blockIdx.x * ELT_THREADS + threadIdx.x;
+    const long long nvec = a.n / VN;
+    for (long long iv = gid; iv < nvec; iv += stride) {
+        const VT y = reinterpret_cast<const VT *>(ay)[iv], h = reinterpret_cast<const VT *>(ah)[iv];
+        int node = (int)(iv * VN / a.ny), c = (int)(iv * VN - (long long)node * a.ny);
+#pragma unroll
+        for (int e = 0; e < VN; e++) {
+            cert_elem<T>(a, y[e], h[e], node, c, a.countCrown || iv * VN + e >= a.crownElems, s, xisPos);
+            if (++c == a.ny) { c = 0; node++; }
+        }
+    }
+    for (long long i = nvec * VN + gid; i < a.n; i += stride) {   // at most VN-1 tail elements
+        const int node = (int)(i / a.ny), c = (int)(i - (long long)node * a.ny);
+        cert_elem<T>(a, ay[i], ah[i], node, c, a.countCrown || i >= a.crownElems, s, xisPos);
+    }
+    for (long long i = gid; i < a.nodes; i += stride) {
+        const double *row = a.node + (size_t)i * PLAN_COLS;
+        const double p = (double)prob[i], te = p * row[PLAN_ECON], tq = p * row[PLAN_SMOOTH];
+        if (a.countCrown || i >= a.crownNodes) { s[CERT_ECON] += te; s[CERT_SMOOTH] += tq; s[CERT_COST_ABS] += fabs(te) + fabs(tq); }
+        uExc = row[PLAN_UBOX_MAX] > uExc ? row[PLAN_UBOX_MAX] : uExc;
+    }
+}
+// the record from the (all-rank) sums and maxima: one thread
+__device__ __forceinline__ void cert_finish(const CertArgs &a) {
+#pragma clang fp contract(off)
+    const double *s = a.sums;
+    const double cost = s[CERT_ECON] + s[CERT_SMOOTH], inner = s[CERT_INNER], support = s[CERT_SUPPORT];
+    const double dual = (cost + inner) - support;
+    const double distX = sqrt(s[CERT_DIST2_X]), distS = sqrt(s[CERT_DIST2_S]), normX = sqrt(s[CERT_NORM2_X]), normS = sqrt(s[CERT_NORM2_S]);
+    const double primal = (cost + a.gammaX * distX) + a.gammaS * distS;
+    const double u = 1.1102230246251565e-16;      // 2^-53
+    const double slack = 1.0 + 4.0 * u * sqrt(s[CERT_COUNT]);
+    const bool valid = normX <= a.gammaX * slack && normS <= a.gammaS * slack && s[CERT_XISPOS] <= u * normS;
+    double *r = a.rec;
+    r[0] = dual; r[1] = primal; r[2] = primal - dual; r[3] = cost; r[4] = inner; r[5] = support; r[6] = distX; r[7] = distS;
+    r[8] = s[CERT_UEXC]; r[9] = normX; r[10] = normS; r[11] = s[CERT_XISPOS];
+    r[12] = (s[CERT_COST_ABS] + s[CERT_INNER_ABS]) + s[CERT_SUPPORT_ABS];
+    r[13] = valid ? 1.0 : 0.0; r[14] = 0.0; r[15] = 0.0;
+}
+template <int PLAIN = 0>   // (a template so that one translation unit owns its code: instantiations/*.inc)
+__global__ void __launch_bounds__(ELT_THREADS) k_certificate(CertArgs a) {
+    constexpr int NW = ELT_THREADS / 64, FLAG = NW * CERT_PART;
+    __shared__ double sh[NW * CERT_PART + 1];   // the waves' sums and maxima; sh[FLAG] != 0: this workgroup arrived last
+    if (a.phase == 1) { if (blockIdx.x == 0 && threadIdx.x == 0) cert_finish(a); return; }
+    double s[CERT_PART];
+#pragma unroll
+    for (int k = 0; k < CERT_PART; k++) s[k] = 0.0;
+    if (a.f64) cert_lane_sums<double>(a, s, s[CERT_UEXC], s[CERT_XISPOS]); else cert_lane_sums<float>(a, s, s[CERT_UEXC], s[CERT_XISPOS]);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < CERT_PART; k++) {
+        const double v = k < CERT_SUMS ? wave_sum_f64(s[k]) : plan_wave_max(s[k]);
+        if (lane == 0) sh[wave * CERT_PART + k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double *out = a.partials + (size_t)blockIdx.x * CERT_PART;
+        for (int k = 0; k < CERT_PART; k++) {
+            double t = sh[k];
+            for (int v = 1; v < NW; v++) { const double o = sh[v * CERT_PART + k]; t = k < CERT_SUMS ? t + o : (o > t ? o : t); }
+            out[k] = t;
+        }
+        // publish the partial, then draw a ticket: the last arriver folds (release -> ticket -> acquire, as k_restart_test)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned int t = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool last = t == gridDim.x - 1;
+        if (last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        sh[FLAG] = last ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    if (sh[FLAG] == 0.0) return;
+#pragma unroll
+    for (int k = 0; k < CERT_PART; k++) s[k] = 0.0;
+    for (unsigned int b = threadIdx.x; b < gridDim.x; b += ELT_THREADS) {   // ascending per lane: a fixed order
+        const double *q = a.partials + (size_t)b * CERT_PART;
+#pragma unroll
+        for (int k = 0; k < CERT_SUMS; k++) s[k] += q[k];
+#pragma unroll
+        for (int k = CERT_SUMS; k < CERT_PART; k++) s[k] = q[k] > s[k] ? q[k] : s[k];
+    }
+    __syncthreads();      // (sh is read above by thread 0 only, before the barrier in front of the flag; written again from here)
+#pragma unroll
+    for (int k = 0; k < CERT_PART; k++) {
+        const double v = k < CERT_SUMS ? wave_sum_f64(s[k]) : plan_wave_max(s[k]);
+        if (lane == 0) sh[wave * CERT_PART + k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < CERT_PART; k++) {
+            double t = sh[k];
+            for (int v = 1; v < NW; v++) { const double o = sh[v * CERT_PART + k]; t = k < CERT_SUMS ? t + o : (o > t ? o : t); }
+            a.sums[k] = t;
+        }
+        a.sums[CERT_COUNT] = a.count;
+        if (a.finish) cert_finish(a);
+    }
+}
+
 }  // namespace rn

@@ -268,6 +268,9 @@ struct CtxBase {
     virtual int get_lipschitz(double *, int *) = 0;
     virtual int set_step_rule(int, double, int) = 0;
     virtual int get_step_rule(int *, double *, int *, double *) = 0;
+    virtual int solve_certificate(double *) = 0;
+    virtual int solve_certificate_device(void **) = 0;
+    virtual int certificate_hz(double *, double *) = 0;
 };
 
 // ---- in-process stand-in for the communicator (rn_debug_local_group_*): `n` contexts of one process, one host thread each ----
@@ -472,7 +475,8 @@ struct Ctx : CtxBase {
     void hx_scale_now() {        // (safety net: a consumer of Hx other than k_dual_stage SCALE behind an unscaled walk)
         const long long total = ntot();
         const int blocks = (int)std::min<long long>((total + ELT_THREADS - 1) / ELT_THREADS, (long long)numCUs * 16);
-        hipLaunchKernelGGL(k_hx_scale<T>, dim3(blocks), dim3(ELT_THREADS), 0, stream, d_hx, d_sqrtp, d_dy, d_stageOf, ny, total);
+        hipLaunchKernelGGL(k_hx_scale<>, dim3(blocks), dim3(ELT_THREADS), 0, stream, (void *)d_hx, (const void *)d_sqrtp, (const void *)d_dy, (const int *)d_stageOf, ny, total,
+                           sizeof(T) == 8 ? 1 : 0);
     }
     T *d_lo = nullptr, *d_hi = nullptr, *d_z = nullptr, *d_res = nullptr;
     // rn_set_bounds: d_blo / d_bhi point at the unscaled table of the granularity in force ([rows][ny]; one table per granularity, allocated by
@@ -2082,6 +2086,9 @@ struct Ctx : CtxBase {
 #include "shift_warm_start.inc"
 #include "lipschitz.inc"
 
+    // ---- the solve certificate: dual bound and optimality gap of the multiplier at hand -----------------------
+#include "certificate.inc"
+
     // ---- multi-GPU ---------------------------------------------------------------------------------------
     // The communicator of this context.  ncclCommInitRank blocks until every rank of the id has arrived -- for ever if one never does.
     // It therefore runs on a HELPER THREAD and the caller waits for it against the wall clock: after `timeoutSeconds` (< 0:
@@ -2412,6 +2419,9 @@ int rn_estimate_lipschitz(rn_ctx *ctx, int maxIterations, double tol, int checkE
 int rn_get_lipschitz(rn_ctx *ctx, double *out, int *stale) { RN_GUARD(ctx); return ctx->impl->get_lipschitz(out, stale); }
 int rn_set_step_rule(rn_ctx *ctx, int rule, double margin, int iterations) { RN_GUARD(ctx); return ctx->impl->set_step_rule(rule, margin, iterations); }
 int rn_get_step_rule(rn_ctx *ctx, int *rule, double *margin, int *iterations, double *inForce) { RN_GUARD(ctx); return ctx->impl->get_step_rule(rule, margin, iterations, inForce); }
+int rn_solve_certificate(rn_ctx *ctx, double *out) { RN_GUARD(ctx); return ctx->impl->solve_certificate(out); }
+int rn_solve_certificate_device(rn_ctx *ctx, void **record) { RN_GUARD(ctx); return ctx->impl->solve_certificate_device(record); }
+int rn_debug_certificate_hz(rn_ctx *ctx, double *hzXi, double *hzPsi) { RN_GUARD(ctx); return ctx->impl->certificate_hz(hzXi, hzPsi); }
 int rn_set_uncertainty(rn_ctx *ctx, int dflag, int pflag, double w) { RN_GUARD(ctx); return ctx->impl->set_uncertainty(dflag, pflag, w); }
 int rn_update_state_control(rn_ctx *ctx, const double *x, const double *u, const double *dm) { RN_GUARD(ctx); return ctx->impl->update_state_control(x, u, dm); }
 int rn_eliminate_input_disturbance_coupling(rn_ctx *ctx, const double *dh, const double *ah) { RN_GUARD(ctx); return ctx->impl->eliminate(dh, ah); }

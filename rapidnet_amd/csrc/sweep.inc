@@ -579,15 +579,22 @@
     // hessOut (with hessianInput, no pair): the Hessian sweep leaves x, u, H * dir and v in the caller's buffers instead of d_xdir, d_udir,
     // d_hxDir and d_v, and does not run the once-per-control-step refresh (lipschitz.inc: a context without FBE buffers, at any point
     // between two entry points)
+    // certOut (no batch, no Hessian input, whole sweep; certificate.inc): the solve step evaluated at certOut->w instead of the accelerated dual,
+    // with every affine term in place, leaving x, u, Hx and v in the caller's buffers: d_x, d_u, d_v, d_hx and primalSwept stay as they are, and a
+    // pending v product -- whose input this sweep overwrites -- is run first
     struct HessOut { T *x, *u, *hx, *v; };
-    int launch_sweep(Batch *batch, int phase = 0, const T *hessianInput = nullptr, bool primalOut = true, const T *hessianInput2 = nullptr, const HessOut *hessOut = nullptr) {
+    struct CertOut { const T *w; T *x, *u, *hx, *v; };
+    int launch_sweep(Batch *batch, int phase = 0, const T *hessianInput = nullptr, bool primalOut = true, const T *hessianInput2 = nullptr, const HessOut *hessOut = nullptr,
+                     const CertOut *certOut = nullptr) {
         RN_CHECK(!hessOut || (hessianInput && !hessianInput2 && primalOut), RN_E_STATE, "launch_sweep: an output override belongs to a single Hessian sweep");
+        RN_CHECK(!certOut || (!batch && phase == 0 && !hessianInput && primalOut), RN_E_STATE, "launch_sweep: a certificate sweep is a whole solve step outside a batch");
         Batch none{};
         Batch &bt = batch ? *batch : none;
         SweepArgs<T> a = sweep_args(bt);
         a.writePrimal = primalOut ? 1 : 0;
-        if (primalOut && !hessianInput) primalSwept = true;      // (rn_plan_report: d_x and d_u hold a plan from here on)
-        if (vPending) { if (hessianInput) { if (int rc = v_flush()) return rc; } else vPending = false; }      // (see v_flush)
+        if (primalOut && !hessianInput && !certOut) primalSwept = true;      // (rn_plan_report: d_x and d_u hold a plan from here on)
+        if (vPending) { if (hessianInput || certOut) { if (int rc = v_flush()) return rc; } else vPending = false; }      // (see v_flush)
+        if (certOut) { a.w = certOut->w; a.x = certOut->x; a.u = certOut->u; a.hx = certOut->hx; a.v = certOut->v; }
         if (hessianInput) {
             a.w = hessianInput;
             a.beta = d_zero; a.uhat = d_zero; a.e = d_zero; a.eb = d_zero; a.bw0 = d_zero;
