@@ -106,6 +106,47 @@ int rn_debug_stream_units(rn_ctx *ctx, long long out[3]);
  * rn_debug_stream_live / _units report this launch afterwards. */
 int rn_debug_stream_product(rn_ctx *ctx, int pair, double *my, double *my2, double *myB);
 
+/* The products with the SHARED operators on the matrix cores alone (k_slab.hpp: k_gemm_vlv, k_gemm_vlv_wide, k_gemm_comp, k_gemm_prep_m2, k_gemm_slab,
+ * k_gemm_shared), for a test that holds them to a plain GEMM: the caller's operators (column-major doubles, logical m x k) go through the context's own
+ * padded and fragment-ordered uploads into scratch buffers of the hook's, the caller's inputs, auxiliary rows and probabilities into scratch rows with
+ * the strides and offsets of the sweep's own buffers; ONE launch step runs -- the launching code a sweep of this context runs, with the sweep's own
+ * choice of kernel, waves, loop, operand copy and slabs per workgroup, RN_KNOB_SLAB_PIPE / _SLAB_FRAG / _VLV_WIDE / _STRUCT_LINEAR acting as on a sweep --
+ * and the outputs come back widened to double.
+ *   launch = RN_SLABP_PAIR   v_i = aux_i (+ aux2_i) - MA in_i / (2 p_i) and [L v_i; B L v_i] = MB v_i as launch_v_lv runs them (foldRoot = 0).
+ *            MA: nv x kA; MB: (nu + nx) x nv.  Dense context: kA = nv + nx, aux = m1 [nodes][2 nv] (the m1 half is read) and, on a context whose
+ *            streaming launch has a split last round, aux2 [nodes - splitFirst][2 nv].  Structured context, RN_KNOB_STRUCT_LINEAR 0: kA = nv + nx,
+ *            no aux; 3: kA = nv + nx + nu, no aux; 4: kA = nx + nu (read at offset nv of rows of nv + nx + nu), aux = c_i [nodes][nv] or NULL (a
+ *            Hessian sweep's form).  storeV = 0: v lives only in LDS (outA is then not written).  outA = v [outNodes][nv], outB [outNodes][nu + nx].
+ *            RN_E_ARG on a context whose sweep runs the composite product instead.
+ *   launch = RN_SLABP_COMP   k_gemm_comp as the default linear form of a structured context launches it: MA (nu + nx) x (nx + nu), in as under knob 4,
+ *            aux = lvconst [nodes][nu + nx] or NULL; outB [outNodes][nu + nx]; MB, aux2 and outA must be NULL.
+ *   launch = RN_SLABP_PREP_M2  k_gemm_prep_m2 (structured contexts): only MA (nv x (nx + nu)) is the caller's, the slab [a_i; b_i] is built by the kernel
+ *            from the accelerated dual as it stands (RN_BUF_ACC_*), sqrt(p) and the preconditioner rows of the context.  outA [outNodes][2 nv] (m2 in
+ *            the second half of each row, as in the sweep's buffer), outB = qa [outNodes][nx].  in, aux, aux2, prob, MB must be NULL.
+ *   launch = RN_SLABP_SINGLE  one launch_gemm for an operator `role`: 0 = [Rinv | Rinv Bbt] (EPI_V: nv x (nv + nx), aux = m1 [nodes][2 nv], aux2 as above;
+ *            dense contexts), 1 = [L; B L] (EPI_LV: (nu + nx) x nv), 2 = B (EPI_Z: nx x nu, aux = e [nodes][nx]), 3 = [T1 | T2] (EPI_V: nv x (nx + nu),
+ *            read at offset nv of rows of nv + nx + nu, aux = c_i [nodes][nv] or NULL).  outA [outNodes][m].
+ * in is compact, [nodes][k]; the hook fills the columns of a scratch row the launch must not read with 7777.  prob [nodes] where the launch scales by
+ * -1 / (2 p_i) (PAIR, COMP, roles 0 and 3), NULL elsewhere.  outNodes = (ceil(nodes / 48) + 1) * 48: the output buffers are uploaded before the launch and
+ * read back whole afterwards, so the caller's fill shows every element that was not written.  nOutA / nOutB: the doubles behind outA / outB.
+ * info[RN_SLAB_INFO_COUNT]: [0] [1] the kernel of the first / second launch (1 k_gemm_vlv, 2 k_gemm_vlv_wide, 3 k_gemm_comp, 4 k_gemm_prep_m2,
+ * 5 k_gemm_slab, 6 k_gemm_shared; 0 none), [2] waves per workgroup, [3] 1 = the software-pipelined loop, [4] 1 = fragment-ordered A operands, [5] CT,
+ * [6] grid, [7] LDS bytes, [8 .. 11] m, k, kp, ldin of the first product, [12 .. 15] of the second (0: none), [16 .. 18] waves, grid, LDS bytes of
+ * the second launch, [19] auxSplit of the first product (nodes: none), [20] the device's CUs, [21] 7 = k_struct_prep ran in front (the first product
+ * does not fit the slab), [22] outNodes, [23] the input's column offset in its rows.
+ * RN_E_STATE before the factor step; RN_E_ARG for an operand the chosen launch does not read or lacks, and for a launch this context's sweep would not
+ * run.  Changes no iterate and no operator of the context; allocates its scratch on first use; launches nothing but the product (PREP_M2 on a network
+ * too wide for the slab: k_struct_prep in front, as in the sweep). */
+enum { RN_SLABP_PAIR = 0, RN_SLABP_COMP = 1, RN_SLABP_PREP_M2 = 2, RN_SLABP_SINGLE = 3 };
+enum { RN_SLAB_INFO_COUNT = 24 };
+typedef struct {
+    int launch, role, storeV;
+    const double *MA, *MB, *in, *aux, *aux2, *prob;
+    double *outA, *outB;
+    size_t nOutA, nOutB;
+} rn_slab_product_args;
+int rn_debug_slab_product(rn_ctx *ctx, const rn_slab_product_args *args, int info[RN_SLAB_INFO_COUNT]);
+
 /* The gradient restart test (rn_set_restart, rapidnet.h) alone: runs k_restart_test on the context's current w (the last sweep's input, what
  * RN_BUF_ACC_* shows), y+ and y and returns out = {g, na2, nb2} -- the kernel can be checked without running a solve.  Allocates the kernel's
  * partials on first use; changes no iterate.  On a sharded context every rank calls it (it contains the ranks' all-reduce). */

@@ -63,7 +63,7 @@ SYMBOLS = [
     "rn_debug_set_allreduce", "rn_debug_local_group_create", "rn_debug_local_group_join", "rn_debug_local_group_destroy",
     "rn_guard_check", "rn_device_memory_info", "rn_reserve_iterations", "rn_profile_read_collective", "rn_debug_inject_allocation", "rn_guard_report", "rn_debug_guard_poke",
     "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_set_bounds", "rn_set_bounds_device", "rn_get_bounds_layout", "rn_get_bounds", "rn_debug_cut_moments",
-    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live", "rn_debug_stream_units", "rn_debug_stream_product",
+    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live", "rn_debug_stream_units", "rn_debug_stream_product", "rn_debug_slab_product",
     "rn_plan_report", "rn_plan_report_scenarios", "rn_plan_report_device",
     "rn_plan_quantiles", "rn_plan_quantiles_device", "rn_plan_paths",
     "rn_shift_warm_start", "rn_set_shift_map", "rn_get_shift_map",
@@ -262,6 +262,7 @@ def load():
     lib.rn_debug_stream_live.argtypes = [vp, dp]
     lib.rn_debug_stream_units.argtypes = [vp, dp]
     lib.rn_debug_stream_product.argtypes = [vp, C.c_int, dp, dp, dp]
+    lib.rn_debug_slab_product.argtypes = [vp, vp, vp]
     lib.rn_profile_read_collective.argtypes = [vp, dp, dp]
     lib.rn_set_tree_data.argtypes = [vp, C.c_size_t, dp, dp, dp]
     lib.rn_set_tree_data_device.argtypes = [vp, C.c_size_t, ip, vp, vp, vp]
@@ -1025,6 +1026,42 @@ class Solver:
         self._check(self.lib.rn_debug_stream_product(self.h, int(bool(pair)), out["my"].ctypes.data, out["my2"].ctypes.data if "my2" in out else None,
                                                      out["myB"].ctypes.data if pair else None))
         return out
+
+    SLAB_LAUNCHES = {"pair": 0, "comp": 1, "prep_m2": 2, "single": 3}
+    SLAB_KERNELS = {0: None, 1: "k_gemm_vlv", 2: "k_gemm_vlv_wide", 3: "k_gemm_comp", 4: "k_gemm_prep_m2", 5: "k_gemm_slab", 6: "k_gemm_shared"}
+    SLAB_INFO = ("kernel", "kernel2", "nw", "pipe", "frag", "ct", "grid", "lds", "m", "k", "kp", "ldin", "m2", "k2", "kp2", "ldin2", "nw2", "grid2", "lds2",
+                 "auxSplit", "numCUs", "structPrep", "outNodes", "inOffset")
+
+    def slabOutNodes(self):
+        """Rows of the output buffers of slabProduct: the nodes, padded past every slab and every wide workgroup."""
+        return ((self.nodes + 47) // 48 + 1) * 48
+
+    def slabProduct(self, launch, MA, MB=None, inp=None, aux=None, aux2=None, prob=None, role=0, storeV=True, ldA=None, ldB=None, fill=0.0):
+        """rn_debug_slab_product (include/rapidnet_debug.h): one launch step of the products with the shared operators, as a sweep of this context
+        shapes it, over the caller's operators (MA, MB: m x k arrays) and operands (inp [nodes][k], aux, aux2, prob).  ldA / ldB: the row lengths of
+        the two output buffers (None: that output does not exist); both are [slabOutNodes()][ld], pre-filled with `fill` and returned whole --
+        whatever the launch did not write still holds it.  Returns (outA, outB, info), info a dict over SLAB_INFO with the kernels by name."""
+        class _Args(C.Structure):
+            _fields_ = [("launch", C.c_int), ("role", C.c_int), ("storeV", C.c_int)] + [(n, C.c_void_p) for n in ("MA", "MB", "in_", "aux", "aux2", "prob", "outA", "outB")] + \
+                       [("nOutA", C.c_size_t), ("nOutB", C.c_size_t)]
+        keep = []
+
+        def _in(x, order="C"):
+            if x is None:
+                return None
+            arr = np.require(np.asarray(x, dtype=np.float64), requirements=["F" if order == "F" else "C", "A"])
+            keep.append(arr)
+            return arr.ctypes.data
+        on = self.slabOutNodes()
+        outA = np.full((on, ldA), float(fill)) if ldA else None
+        outB = np.full((on, ldB), float(fill)) if ldB else None
+        args = _Args(self.SLAB_LAUNCHES[launch], int(role), int(bool(storeV)), _in(MA, "F"), _in(MB, "F"), _in(inp), _in(aux), _in(aux2), _in(prob),
+                     outA.ctypes.data if ldA else None, outB.ctypes.data if ldB else None, outA.size if ldA else 0, outB.size if ldB else 0)
+        info = np.zeros(24, dtype=np.int32)
+        self._check(self.lib.rn_debug_slab_product(self.h, C.addressof(args), info.ctypes.data))
+        d = dict(zip(self.SLAB_INFO, (int(v) for v in info)))
+        d["kernel"], d["kernel2"] = self.SLAB_KERNELS[d["kernel"]], self.SLAB_KERNELS[d["kernel2"]]
+        return outA, outB, d
 
     def debugGuardPoke(self, nbytes):
         self._check(self.lib.rn_debug_guard_poke(self.h, int(nbytes)))

@@ -184,6 +184,7 @@ struct CtxBase {
     virtual int stream_live(long long *) = 0;
     virtual int stream_units(long long *) = 0;
     virtual int stream_product(int, double *, double *, double *) = 0;
+    virtual int slab_product(const rn_slab_product_args *, int *) = 0;
     virtual int synchronize() = 0;
     virtual void *stream_handle() = 0;
     virtual int comm_init(int, int, const void *, double timeoutSeconds = -1.0) = 0;
@@ -1959,6 +1960,144 @@ struct Ctx : CtxBase {
         if (pair) { if (int rc = download(myB, d_myB, (size_t)d.nodes * 2 * d.nv)) return rc; }
         return RN_OK;
     }
+    // rn_debug_slab_product (include/rapidnet_debug.h): one launch step of the shared-operator products (sweep.inc: run_v_lv, run_comp, run_prep_m2,
+    // run_gemm) over scratch buffers of the hook's own, with the arguments v_lv_args / prep_m2_args / gemm_args shape for a sweep of this context.
+    struct SlabScratch { T *MA = nullptr, *MAf = nullptr, *MB = nullptr, *MBf = nullptr, *in = nullptr, *aux = nullptr, *aux2 = nullptr, *prob = nullptr, *outA = nullptr, *outB = nullptr; bool ready = false; };
+    SlabScratch ss;
+    int slab_out_nodes() const { return ((d.nodes + 47) / 48 + 1) * 48; }
+    int slab_scratch() {
+        if (ss.ready) return RN_OK;
+        const int nx = d.nx, nu = d.nu, nv = d.nv;
+        const size_t nA = (size_t)pad16(std::max(nv, nu + nx)) * pad4(nv + nx + nu), nB = (size_t)pad16(nu + nx) * pad4(nv);
+        const size_t rowsAux = (size_t)std::max(2 * nv, nu + nx), on = (size_t)slab_out_nodes();
+        if (int rc = dalloc(&ss.MA, nA)) return rc;
+        if (int rc = dalloc(&ss.MAf, nA)) return rc;
+        if (int rc = dalloc(&ss.MB, nB)) return rc;
+        if (int rc = dalloc(&ss.MBf, nB)) return rc;
+        if (int rc = dalloc(&ss.in, (size_t)d.nodes * (nv + nx + nu))) return rc;
+        if (int rc = dalloc(&ss.aux, (size_t)d.nodes * rowsAux)) return rc;
+        if (int rc = dalloc(&ss.aux2, (size_t)d.nodes * rowsAux)) return rc;
+        if (int rc = dalloc(&ss.prob, (size_t)d.nodes)) return rc;
+        if (int rc = dalloc(&ss.outA, on * rowsAux)) return rc;
+        if (int rc = dalloc(&ss.outB, on * (nu + nx))) return rc;
+        ss.ready = true;
+        return RN_OK;
+    }
+    // caller's compact rows [nodes][k] into scratch rows of ld at column off; the other columns hold a value no product may read
+    int slab_put_rows(T *dst, const double *src, int k, int ld, int off) {
+        std::vector<double> tmp((size_t)d.nodes * ld, 7777.0);
+        for (int i = 0; i < d.nodes; i++) for (int j = 0; j < k; j++) tmp[(size_t)i * ld + off + j] = src[(size_t)i * k + j];
+        return upload(dst, tmp.data(), tmp.size());
+    }
+    static void slab_info_product(int *info, const GemmArgs<T> &g) { info[0] = g.m; info[1] = g.k; info[2] = g.kp; info[3] = g.ldin; }
+    int slab_product(const rn_slab_product_args *p, int *info) override {
+        RN_CHECK(p && info, RN_E_ARG, "rn_debug_slab_product: null arguments");
+        RN_CHECK(factored, RN_E_STATE, "rn_debug_slab_product: the shared operators' launches are shaped by rn_factor_step");
+        RN_CHECK(p->launch >= RN_SLABP_PAIR && p->launch <= RN_SLABP_SINGLE && p->MA, RN_E_ARG, "rn_debug_slab_product: unknown launch, or no operator");
+        RN_HIP(hipSetDevice(device));
+        const int nx = d.nx, nu = d.nu, nv = d.nv, nodes = d.nodes;
+        const size_t on = (size_t)slab_out_nodes();
+        if (int rc = slab_scratch()) return rc;
+        SweepArgs<T> a = sweep_args(Batch{});
+        a.w = p_acc_view ? p_acc_view : p_acc;
+        a.lin = lin_bits(a.lin);
+        a.sk = ss.in; a.sk2 = ss.in; a.ab = ss.in; a.v = ss.outA; a.lvb = ss.outB; a.my = ss.aux; a.my2 = ss.aux2; a.qa = ss.outB;
+        GemmArgs<T> g1{}, g2{}, gC{};
+        bool two = false;
+        int epi = EPI_V;
+        size_t needA = 0, needB = 0;
+        if (p->launch == RN_SLABP_PAIR || p->launch == RN_SLABP_COMP) {
+            a.writePrimal = p->storeV ? 1 : 0;
+            if ((a.lin & 2) && !p->aux) a.beta = d_zero;      // (the form of a Hessian sweep: no constant operand)
+            else if (a.beta == d_zero) a.beta = ss.aux;      // (any address but d_zero: only compared)
+            const bool comp = v_lv_args(a, g1, g2, gC);
+            RN_CHECK(comp == (p->launch == RN_SLABP_COMP), RN_E_ARG, "rn_debug_slab_product: this context's sweep runs the other form of the v / Lv products (RN_KNOB_STRUCT_LINEAR)");
+            if (comp) {
+                g1 = gC;
+                RN_CHECK(!p->MB && !p->outA && p->outB, RN_E_ARG, "rn_debug_slab_product: the composite product has one operator and one output, outB");
+                needB = on * (nu + nx);
+            } else {
+                two = true;
+                RN_CHECK(p->MB && p->outA && p->outB, RN_E_ARG, "rn_debug_slab_product: the pair needs MB, outA and outB");
+                needA = on * nv; needB = on * (nu + nx);
+            }
+        } else if (p->launch == RN_SLABP_PREP_M2) {
+            RN_CHECK(structured, RN_E_ARG, "rn_debug_slab_product: k_gemm_prep_m2 belongs to structured contexts");
+            RN_CHECK(!p->MB && !p->in && !p->aux && !p->aux2 && !p->prob && p->outA && p->outB, RN_E_ARG, "rn_debug_slab_product: k_gemm_prep_m2 reads the context's dual, not caller operands; outputs outA, outB");
+            a.my = ss.outA;
+            g1 = prep_m2_args(a);
+            epi = EPI_LV;
+            needA = on * 2 * nv; needB = on * nx;
+        } else {
+            RN_CHECK(!p->MB && p->outA && !p->outB, RN_E_ARG, "rn_debug_slab_product: a single product has one operator and one output, outA");
+            switch (p->role) {
+                case 0:
+                    RN_CHECK(!structured, RN_E_ARG, "rn_debug_slab_product: role 0 is the dense contexts' v product");
+                    g1 = gemm_args<EPI_V>(d_RTp, nv, nv + nx, a.sk, nv + nx, a.v, nv, a.my, 2 * nv, a.splitFirst); g1.aux2 = g1.aux2 ? ss.aux2 : nullptr; break;
+                case 1: g1 = gemm_args<EPI_LV>(d_LBLp, nu + nx, nv, ss.in, nv, a.v, nu + nx, nullptr, 0); epi = EPI_LV; break;
+                case 2: g1 = gemm_args<EPI_Z>(d_Bp, nx, nu, ss.in, nu, a.v, nx, ss.aux, nx); epi = EPI_Z; break;
+                case 3: g1 = gemm_args<EPI_V>(d_T12p, nv, nx + nu, a.sk2 + nv, nv + nx + nu, a.v, nv, p->aux ? ss.aux : nullptr, nv); g1.aux2 = nullptr; g1.auxSplit = 0; break;
+                default: RN_CHECK(false, RN_E_ARG, "rn_debug_slab_product: role 0 .. 3");
+            }
+            needA = on * g1.m;
+        }
+        const bool scaled = epi == EPI_V;
+        const bool split = g1.aux2 != nullptr && g1.auxSplit < nodes;
+        if (p->launch != RN_SLABP_PREP_M2) {
+            RN_CHECK(p->in, RN_E_ARG, "rn_debug_slab_product: no input");
+            RN_CHECK((p->prob != nullptr) == scaled, RN_E_ARG, "rn_debug_slab_product: prob belongs to the products that scale by -1 / (2 p)");
+            RN_CHECK((p->aux != nullptr) == (g1.aux != nullptr), RN_E_ARG, "rn_debug_slab_product: aux given for a launch that reads none, or missing for one that does");
+            RN_CHECK((p->aux2 != nullptr) == split, RN_E_ARG, "rn_debug_slab_product: aux2 belongs to a launch with a split last round, and that launch needs it");
+        }
+        RN_CHECK(p->nOutA == needA && p->nOutB == needB, RN_E_ARG, "rn_debug_slab_product: output sizes are outNodes * the sweep buffer's row length");
+        // operators: through the context's own uploads
+        if (int rc = upload_padded(ss.MA, p->MA, g1.m, g1.k)) return rc;
+        if (int rc = upload_fragments(ss.MAf, p->MA, g1.m, g1.k)) return rc;
+        g1.M = ss.MA; if (g1.Mf) g1.Mf = ss.MAf;
+        if (two) {
+            if (int rc = upload_padded(ss.MB, p->MB, g2.m, g2.k)) return rc;
+            if (int rc = upload_fragments(ss.MBf, p->MB, g2.m, g2.k)) return rc;
+            g2.M = ss.MB; if (g2.Mf) g2.Mf = ss.MBf;
+        }
+        if (p->launch != RN_SLABP_PREP_M2) {
+            const int off = (int)(g1.in - ss.in);
+            if (int rc = slab_put_rows(ss.in, p->in, g1.k, g1.ldin, off)) return rc;
+            info[23] = off;
+            if (p->aux) {
+                // only the rows the launch reads are the caller's; in the sweep's m1 buffer each row has 2 nv entries and the product reads the first nv
+                if (int rc = upload(ss.aux, p->aux, (size_t)nodes * g1.ldaux)) return rc;
+                g1.aux = ss.aux;
+            } else {
+                // (a pair that runs as two launches on a structured context reads the m1 half of the sweep's buffer, which stays zero there)
+                std::vector<double> z((size_t)nodes * std::max(2 * nv, nu + nx), 0.0);
+                if (int rc = upload(ss.aux, z.data(), z.size())) return rc;
+            }
+            if (split) { if (int rc = upload(ss.aux2, p->aux2, (size_t)(nodes - g1.auxSplit) * g1.ldaux)) return rc; g1.aux2 = ss.aux2; }
+            if (scaled) { if (int rc = upload(ss.prob, p->prob, (size_t)nodes)) return rc; g1.prob = ss.prob; }
+        } else info[23] = 0;
+        if (needA) { if (int rc = upload(ss.outA, p->outA, needA)) return rc; }
+        if (needB) { if (int rc = upload(ss.outB, p->outB, needB)) return rc; }
+        SlabReport rep{};
+        slabRep = &rep;
+        if (p->launch == RN_SLABP_COMP) run_comp(g1, a, 0);
+        else if (p->launch == RN_SLABP_PAIR) run_v_lv(g1, g2, a, 0);
+        else if (p->launch == RN_SLABP_PREP_M2) run_prep_m2(g1, a);
+        else if (epi == EPI_V) run_gemm<EPI_V>(g1);
+        else if (epi == EPI_LV) run_gemm<EPI_LV>(g1);
+        else run_gemm<EPI_Z>(g1);
+        slabRep = nullptr;
+        RN_HIP(hipGetLastError());
+        RN_HIP(hipStreamSynchronize(stream));
+        if (needA) { if (int rc = download(p->outA, ss.outA, needA)) return rc; }
+        if (needB) { if (int rc = download(p->outB, ss.outB, needB)) return rc; }
+        info[0] = rep.kernel[0]; info[1] = rep.kernel[1]; info[2] = rep.nw[0]; info[3] = rep.pipe; info[4] = rep.frag; info[5] = rep.ct;
+        info[6] = rep.grid[0]; info[7] = (int)rep.lds[0];
+        slab_info_product(info + 8, g1);
+        if (two) slab_info_product(info + 12, g2); else info[12] = info[13] = info[14] = info[15] = 0;
+        info[16] = rep.nw[1]; info[17] = rep.grid[1]; info[18] = (int)rep.lds[1];
+        info[19] = split ? g1.auxSplit : nodes; info[20] = numCUs; info[21] = rep.pre; info[22] = (int)on;
+        return RN_OK;
+    }
     int counters(long *out) override {
         RN_CHECK(out, RN_E_ARG, "rn_get_counters: null output");
         out[0] = optBatches; out[1] = exactBatches; out[2] = fallbacks; out[3] = optHold;
@@ -2589,6 +2728,7 @@ int rn_debug_stream_info(rn_ctx *ctx, int info[4]) { RN_GUARD(ctx); return ctx->
 int rn_debug_stream_live(rn_ctx *ctx, long long out[4]) { RN_GUARD(ctx); return ctx->impl->stream_live(out); }
 int rn_debug_stream_units(rn_ctx *ctx, long long out[3]) { RN_GUARD(ctx); return ctx->impl->stream_units(out); }
 int rn_debug_stream_product(rn_ctx *ctx, int pair, double *my, double *my2, double *myB) { RN_GUARD(ctx); return ctx->impl->stream_product(pair, my, my2, myB); }
+int rn_debug_slab_product(rn_ctx *ctx, const rn_slab_product_args *args, int *info) { RN_GUARD(ctx); return ctx->impl->slab_product(args, info); }
 int rn_debug_restart_test(rn_ctx *ctx, double out[3]) { RN_GUARD(ctx); return ctx->impl->debug_restart_test(out); }
 int rn_debug_peer_seq(rn_ctx *ctx, unsigned int seq) { RN_GUARD(ctx); return ctx->impl->debug_peer_seq(seq); }
 int rn_guard_report(long out[2]) { if (!out) return RN_E_ARG; out[0] = rn::g_guardContexts.load(); out[1] = rn::g_guardBadBytes.load(); return RN_OK; }

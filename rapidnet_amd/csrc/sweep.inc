@@ -200,43 +200,73 @@
     static CompKernel comp_kernel(bool pipe) { return pipe ? k_gemm_comp<T, true> : k_gemm_comp<T, false>; }
     static VlvKernel vlv_kernel(bool pipe) { return pipe ? k_gemm_vlv<T, true> : k_gemm_vlv<T, false>; }
     static VlvWideKernel vlv_wide_kernel(int ct) { return ct == 2 ? k_gemm_vlv_wide<T, 2> : k_gemm_vlv_wide<T, 3>; }
-    template <int EPI>
+    // What the launching steps below chose (rn_debug_slab_product's info[]): written only while the hook has set slabRep; slot 0 is the first
+    // (or only) launch of a step, slot 1 the second of a pair that runs as two launches.
+    enum { SLABK_NONE = 0, SLABK_VLV = 1, SLABK_VLV_WIDE = 2, SLABK_COMP = 3, SLABK_PREP_M2 = 4, SLABK_SLAB = 5, SLABK_SHARED = 6, SLABK_STRUCT_PREP = 7 };
+    struct SlabReport { int kernel[2], nw[2], grid[2]; long long lds[2]; int pipe, frag, ct, pre; };
+    SlabReport *slabRep = nullptr;
+    void slab_report(int slot, int kernel, int nw, int grid, size_t lds, bool pipe, bool frag, int ct) {
+        if (!slabRep) return;
+        slabRep->kernel[slot] = kernel; slabRep->nw[slot] = nw; slabRep->grid[slot] = grid; slabRep->lds[slot] = (long long)lds;
+        if (slot == 0) { slabRep->pipe = pipe ? 1 : 0; slabRep->frag = frag ? 1 : 0; slabRep->ct = ct; }
+    }
+    // The shared-operator products are launched in two steps: the *_args functions build the GemmArgs a sweep gives them, the run_* functions
+    // choose the kernel and its shape and launch.  rn_debug_slab_product builds the same arguments over scratch buffers and goes through the
+    // same run_* functions.
     // sweepSplit: the splitFirst of the sweep whose m1 `aux` holds (SweepArgs; -1: the context's own -- a pair sweep runs unsplit on a split context)
-    void launch_gemm(const T *Mp, int m, int k, const T *in, int ldin, T *out, int ldout, const T *aux, int ldaux, int sweepSplit = -1) {
+    template <int EPI>
+    GemmArgs<T> gemm_args(const T *Mp, int m, int k, const T *in, int ldin, T *out, int ldout, const T *aux, int ldaux, int sweepSplit = -1) const {
         GemmArgs<T> g{Mp, m, k, pad16(m), pad4(k), in, ldin, out, ldout, aux, ldaux, d_prob, d.nodes};
         const int sf = sweepSplit >= 0 ? sweepSplit : splitFirst;
         if (EPI == EPI_V && !structured && sf >= 0 && sf < d.nodes) { g.aux2 = d_my2; g.auxSplit = sf; }   // k_stream_gemv's split last round
+        return g;
+    }
+    template <int EPI>
+    void run_gemm(const GemmArgs<T> &g, int slot = 0) {
 #if RN_GEMM_SLAB
         const int SB = slab_stride(g.kp);
         const size_t lds = (size_t)16 * SB * sizeof(T);
         if (lds <= 64 * 1024) {   // slab kernel (default); falls back to the tile kernel when the slab does not fit
-            const int nw = slab_waves((m + 15) / 16, g.kp / 4, 0, 0);
+            const int nw = slab_waves((g.m + 15) / 16, g.kp / 4, 0, 0);
+            slab_report(slot, SLABK_SLAB, nw, (d.nodes + 15) / 16, lds, few_slabs(), g.Mf != nullptr, 0);
             hipLaunchKernelGGL(slab_kernel<EPI>(few_slabs()), dim3((d.nodes + 15) / 16), dim3(64 * nw), lds, stream, g, SB);
             return;
         }
 #endif
         const int units = (g.mp / (16 * GEMM_RT)) * ((d.nodes + 15) / 16);   // one 64 x 16 output tile per workgroup
+        slab_report(slot, SLABK_SHARED, GEMM_WAVES, units, 0, false, false, 0);
         hipLaunchKernelGGL((k_gemm_shared<T, EPI, RN_GEMM_KS>), dim3(units), dim3(GEMM_THREADS), 0, stream, g);
     }
+    template <int EPI>
+    void launch_gemm(const T *Mp, int m, int k, const T *in, int ldin, T *out, int ldout, const T *aux, int ldaux, int sweepSplit = -1) {
+        run_gemm<EPI>(gemm_args<EPI>(Mp, m, k, in, ldin, out, ldout, aux, ldaux, sweepSplit));
+    }
     // structured mode, (1) of the sweep: a_i = F_i' xi_i, b_i = G_i' psi_i and m2_i = [Bbt | L'] [a_i; b_i]
-    void launch_prep_m2(const SweepArgs<T> &a) {
+    GemmArgs<T> prep_m2_args(const SweepArgs<T> &a) const {
         const int nx = d.nx, nu = d.nu, nv = d.nv;
-#if RN_GEMM_SLAB
-        GemmArgs<T> g{d_BLp, nv, nx + nu, pad16(nv), pad4(nx + nu), d_ab, nx + nu, d_my + nv, 2 * nv, nullptr, 0, d_prob, d.nodes};
+        GemmArgs<T> g{d_BLp, nv, nx + nu, pad16(nv), pad4(nx + nu), a.ab, nx + nu, a.my + nv, 2 * nv, nullptr, 0, d_prob, d.nodes};
         if (frag_on()) g.Mf = d_BLf;
+        return g;
+    }
+    void run_prep_m2(GemmArgs<T> g, const SweepArgs<T> &a) {
+#if RN_GEMM_SLAB
         const int SB = slab_stride(g.kp);
         const size_t lds = (size_t)16 * SB * sizeof(T);
         if (lds <= 64 * 1024) {
-            const int nw = slab_waves((nv + 15) / 16, g.kp / 4, 0, 0);
+            const int nw = slab_waves((g.m + 15) / 16, g.kp / 4, 0, 0);
+            slab_report(0, SLABK_PREP_M2, nw, (d.nodes + 15) / 16, lds, few_slabs(), g.Mf != nullptr, 0);
             hipLaunchKernelGGL(prep_m2_kernel(few_slabs()), dim3((d.nodes + 15) / 16), dim3(64 * nw), lds, stream, g, a, SB);
             return;
         }
 #endif
-        const long long tot = (long long)d.nodes * (nx + nu);
+        const long long tot = (long long)d.nodes * (d.nx + d.nu);
         const int blocks = (int)std::min<long long>(4096, (tot + 255) / 256);
         hipLaunchKernelGGL(k_struct_prep<T>, dim3(blocks), dim3(256), 0, stream, a);
-        launch_gemm<EPI_LV>(d_BLp, nv, nx + nu, d_ab, nx + nu, d_my + nv, 2 * nv, nullptr, 0);
+        g.Mf = nullptr;      // (the products outside the slab family read the column-major copy)
+        run_gemm<EPI_LV>(g);
+        if (slabRep) slabRep->pre = SLABK_STRUCT_PREP;
     }
+    void launch_prep_m2(const SweepArgs<T> &a) { run_prep_m2(prep_m2_args(a), a); }
     bool v_lv_is_slab() const {
 #if RN_GEMM_SLAB
         return (size_t)16 * (slab_stride(pad4(d.nv + d.nx)) + slab_stride(pad4(d.nv))) * sizeof(T) <= 64 * 1024;
@@ -309,11 +339,14 @@
         linConstValid = true;
         return RN_OK;
     }
-    // (3) of the sweep: v_i and [L v_i ; B L v_i] for all nodes
-    void launch_v_lv(const SweepArgs<T> &a, int foldRoot) {
+    // SweepArgs::lin of a sweep's launches, from sweep_args' 0 / 1: the walks leave the Bs columns alone (bit 1); the forward walk's affine terms ride in
+    // the product's constant (bit 2)
+    int lin_bits(int lin) const { return (lin && lin_const()) ? (lin_fold() ? 7 : 3) : lin; }
+    // (3) of the sweep: v_i and [L v_i ; B L v_i] for all nodes.  v_lv_args: the two products' arguments as the sweep `a` shapes them (gC: the
+    // one product with the composite operator, where the sweep takes that form -- the return value says so)
+    bool v_lv_args(const SweepArgs<T> &a, GemmArgs<T> &gV, GemmArgs<T> &gL, GemmArgs<T> &gC) const {
         const int nx = d.nx, nu = d.nu, nv = d.nv;
-#if RN_GEMM_SLAB
-        GemmArgs<T> gV{d_RTp, nv, nv + nx, pad16(nv), pad4(nv + nx), a.sk, nv + nx, a.v, nv, a.my, 2 * nv, d_prob, d.nodes, a.my2, a.splitFirst};
+        gV = GemmArgs<T>{d_RTp, nv, nv + nx, pad16(nv), pad4(nv + nx), a.sk, nv + nx, a.v, nv, a.my, 2 * nv, d_prob, d.nodes, a.my2, a.splitFirst};
         if (a.lin) gV = GemmArgs<T>{d_RT2p, nv, nv + nx + nu, pad16(nv), pad4(nv + nx + nu), a.sk2, nv + nx + nu, a.v, nv, nullptr, 0, d_prob, d.nodes, nullptr, d.nodes};
         if (!a.writePrimal) gV.out = nullptr;   // slab kernel only: v stays in LDS for the second product
         if (structured) gV.aux = nullptr;       // m1_i is folded into the v product (d_my's m1 half stays zero): the epilogue has nothing to fetch
@@ -321,44 +354,65 @@
             gV = GemmArgs<T>{d_T12p, nv, nx + nu, pad16(nv), pad4(nx + nu), a.sk2 + nv, nv + nx + nu, a.writePrimal ? a.v : nullptr, nv,
                              a.beta == d_zero ? nullptr : d_vconst, nv, d_prob, d.nodes, nullptr, d.nodes};
         }
-        GemmArgs<T> gL{d_LBLp, nu + nx, nv, pad16(nu + nx), pad4(nv), a.v, nv, a.lvb, nu + nx, nullptr, 0, d_prob, d.nodes};
-        if ((a.lin & 2) && lin_comp()) {      // one product with the composite operator (k_gemm_comp); v_i, when it is stored, by a launch of its own
-            const bool hess = a.beta == d_zero;
-            GemmArgs<T> gC{d_MCp, nu + nx, nx + nu, pad16(nu + nx), pad4(nx + nu), a.sk2 + nv, nv + nx + nu, a.lvb, nu + nx,
-                           hess ? nullptr : d_lvconst, nu + nx, d_prob, d.nodes, nullptr, d.nodes};
-            if (frag_on()) gC.Mf = d_MCf;
-            const int SBc = slab_stride(gC.kp), nSlabs = (d.nodes + 15) / 16;
-            const int nwc = slab_waves((nu + nx + 15) / 16, gC.kp / 4, 0, 0);
-            hipLaunchKernelGGL(comp_kernel(few_slabs()), dim3(nSlabs), dim3(64 * nwc), (size_t)16 * SBc * sizeof(T), stream, gC, SBc, a, foldRoot);
-            if (a.writePrimal) {
-                if (hess || vEager || a.v != d_v) launch_gemm<EPI_V>(d_T12p, nv, nx + nu, a.sk2 + nv, nv + nx + nu, a.v, nv, hess ? nullptr : d_vconst, nv);
-                else vPending = true;
-            }
-            return;
-        }
+        gL = GemmArgs<T>{d_LBLp, nu + nx, nv, pad16(nu + nx), pad4(nv), a.v, nv, a.lvb, nu + nx, nullptr, 0, d_prob, d.nodes};
+        if (frag_on()) { gV.Mf = (a.lin & 2) ? d_T12f : (a.lin ? d_RT2f : d_RTf); gL.Mf = d_LBLf; }
+        if (!((a.lin & 2) && lin_comp())) return false;
+        // one product with the composite operator (k_gemm_comp); v_i, when it is stored, by a launch of its own
+        gC = GemmArgs<T>{d_MCp, nu + nx, nx + nu, pad16(nu + nx), pad4(nx + nu), a.sk2 + nv, nv + nx + nu, a.lvb, nu + nx,
+                         a.beta == d_zero ? nullptr : d_lvconst, nu + nx, d_prob, d.nodes, nullptr, d.nodes};
+        if (frag_on()) gC.Mf = d_MCf;
+        return true;
+    }
+    void run_comp(const GemmArgs<T> &gC, const SweepArgs<T> &a, int foldRoot) {
+        const int SBc = slab_stride(gC.kp), nSlabs = (d.nodes + 15) / 16;
+        const int nwc = slab_waves((gC.m + 15) / 16, gC.kp / 4, 0, 0);
+        slab_report(0, SLABK_COMP, nwc, nSlabs, (size_t)16 * SBc * sizeof(T), few_slabs(), gC.Mf != nullptr, 0);
+        hipLaunchKernelGGL(comp_kernel(few_slabs()), dim3(nSlabs), dim3(64 * nwc), (size_t)16 * SBc * sizeof(T), stream, gC, SBc, a, foldRoot);
+    }
+    void run_v_lv(const GemmArgs<T> &gV, const GemmArgs<T> &gL, const SweepArgs<T> &a, int foldRoot) {
+#if RN_GEMM_SLAB
         const int SB = slab_stride(gV.kp), SV = slab_stride(gL.kp);
         const size_t lds = (size_t)16 * (SB + SV) * sizeof(T);
-        if (frag_on()) { gV.Mf = (a.lin & 2) ? d_T12f : (a.lin ? d_RT2f : d_RTf); gL.Mf = d_LBLf; }
         if (lds <= 64 * 1024) {
             const int nSlabs = (d.nodes + 15) / 16;
             // many slabs per CU: one workgroup per CU with CT slabs each, every A fragment (from L2) used CT times (k_gemm_vlv_wide)
             const int ct = wide_ct(nSlabs, lds);
             if (ct >= 2 && foldRoot != 2) {
                 const int grid = (nSlabs + ct - 1) / ct, threads = 64 * wide_waves();
+                slab_report(0, SLABK_VLV_WIDE, wide_waves(), grid, lds * ct, true, gV.Mf != nullptr, ct);
                 hipLaunchKernelGGL(vlv_wide_kernel(ct), dim3(grid), dim3(threads), lds * ct, stream, gV, gL, SB, SV, a, foldRoot);
                 return;
             }
-            const int nw = slab_waves((nv + 15) / 16, gV.kp / 4, (nu + nx + 15) / 16, gL.kp / 4);
+            const int nw = slab_waves((gV.m + 15) / 16, gV.kp / 4, (gL.m + 15) / 16, gL.kp / 4);
             // sharded two-stage crown (foldRoot = 2): scratch for the root's children behind the slab buffers, so that workgroup 0 -- the
             // launch's critical path -- fills its own slab in LDS instead of draining its stores and reading them back
             const int scratch = foldRoot == 2 ? crown_scratch(lds) : 0;
             const size_t ldsAll = lds + (size_t)scratch * sizeof(T);
+            slab_report(0, SLABK_VLV, nw, nSlabs, ldsAll, few_slabs(), gV.Mf != nullptr, 1);
             hipLaunchKernelGGL(vlv_kernel(few_slabs()), dim3(nSlabs), dim3(64 * nw), ldsAll, stream, gV, gL, SB, SV, a, foldRoot, scratch);
             return;
         }
 #endif
-        launch_gemm<EPI_V>(d_RTp, nv, nv + nx, a.sk, nv + nx, a.v, nv, a.my, 2 * nv, a.splitFirst);
-        launch_gemm<EPI_LV>(d_LBLp, nu + nx, nv, a.v, nv, a.lvb, nu + nx, nullptr, 0);   // [L v_i ; B L v_i]
+        // two launches: v is always stored (the second product reads it back), from the column-major operators; the context's own split
+        // decides about the second partial of m1 as in every product outside the slab pair
+        GemmArgs<T> g1 = gemm_args<EPI_V>(gV.M, gV.m, gV.k, gV.in, gV.ldin, const_cast<T *>(gL.in), gV.ldout, a.my, 2 * d.nv, a.splitFirst);
+        g1.prob = gV.prob; if (g1.aux2) g1.aux2 = gV.aux2;
+        GemmArgs<T> g2 = gL; g2.Mf = nullptr;
+        run_gemm<EPI_V>(g1, 0);
+        run_gemm<EPI_LV>(g2, 1);   // [L v_i ; B L v_i]
+    }
+    void launch_v_lv(const SweepArgs<T> &a, int foldRoot) {
+        GemmArgs<T> gV, gL, gC;
+        if (v_lv_args(a, gV, gL, gC)) {
+            run_comp(gC, a, foldRoot);
+            if (a.writePrimal) {
+                const bool hess = a.beta == d_zero;
+                if (hess || vEager || a.v != d_v) launch_gemm<EPI_V>(d_T12p, d.nv, d.nx + d.nu, a.sk2 + d.nv, d.nv + d.nx + d.nu, a.v, d.nv, hess ? nullptr : d_vconst, d.nv);
+                else vPending = true;
+            }
+            return;
+        }
+        run_v_lv(gV, gL, a, foldRoot);
     }
     // crown handling of the forward sweep: 0 = crown launches of their own; 1 = every chain workgroup walks its crown path and
     // the first descendant chain of a crown node writes it; 2 (sharded) = crown nodes dealt round-robin to the workgroups
@@ -417,8 +471,7 @@
         SweepPlan p{};
         const int cs = a.chainStage;
         p.phase = phase;
-        // the walks leave the Bs columns alone (bit 1); the forward walk's affine terms ride in the product's constant (bit 2)
-        p.lin = (a.lin && lin_const()) ? (lin_fold() ? 7 : 3) : a.lin;
+        p.lin = lin_bits(a.lin);
         p.form = p.lin ? FORM_LIN : structured ? FORM_STRUCT : FORM_DENSE;
         // one-shot exchange (inside rn_apg_iterate batches only): the launch that produces the cut parents' local sums pushes them
         // to every peer, the crown launch gathers them -- no collective in between

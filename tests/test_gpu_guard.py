@@ -156,6 +156,15 @@ def test_long_horizon_under_guard(guard):
     guard["contexts"] = lhz.guard_body()
 
 
+def test_slab_products_under_guard(guard):
+    """rn_debug_slab_product's scratch operators, operand rows and outputs between red zones (tests/test_gpu_slab_product.py): a last slab of one
+    node, the wide kernel's last workgroup of one node, the linear form's reads at an offset into longer rows, the first structured product and
+    the tile kernel's 64-row groups past m -- payloads start as NaN, so a read outside what the hook wrote shows in the exact comparisons"""
+    import test_gpu_slab_product as slp
+
+    guard["contexts"] = slp.guard_body()
+
+
 def test_barcelona31_under_guard(guard):
     """The full-size K = 31 Barcelona config: the kernel instantiations and launch shapes of the headline workload (G = 8 spans,
     two slots per thread, pipelined slab products, k_dual_stage tiles)."""
