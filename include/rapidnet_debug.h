@@ -161,6 +161,48 @@ int rn_debug_cut_moments(rn_ctx *ctx, double *E, double *P, size_t nParents);
  * RN_E_STATE before the first certificate.  Changes nothing. */
 int rn_debug_certificate_hz(rn_ctx *ctx, double *hzXi, double *hzPsi);
 
+/* The dual update of ONE iteration alone (k_dual.hpp: k_dual_stage, k_dual_fused, its fix-up pass and the bookkeeping kernels), for a test that
+ * holds it to an exactly rounded restatement.  Inputs are the context's buffers as they stand: Hx = what RN_BUF_PRIMAL_* shows, w = RN_BUF_ACC_*,
+ * y = RN_BUF_UPD_* (the yprev of the batch loop's arguments); bounds, sqrt(p) and the preconditioner rows are the context's own.  The launching code is
+ * the batch loop's (sweep.inc: dual_main_args / run_dual_main, run_close_optimistic, run_close_exact_sharded, exact_fixup_args / run_exact_fixup);
+ * outputs, partials, iteration state and the history slot are scratch of the hook's own, allocated on first use: no iterate, no history entry and no
+ * iteration state of the context changes.  The launches are enqueued back to back; the hook synchronises behind the last one.
+ *   form = RN_DUALP_MAIN             the main pass only, as launch_dual_main chooses it: k_dual_stage with the context's trips and pipe (RN_KNOB_DUAL_TRIPS /
+ *                                    _PIPE act as in a batch) or the flat k_dual_fused; flat = 1 forces the flat kernel, as an exact sharded batch does.
+ *                                    unscaled = 1: Hx holds the primal values an unscaled walk leaves (k_dual_stage SCALE; flat: k_hx_scale in front, on a copy).
+ *          RN_DUALP_EXACT            the main pass, then the single-GPU fix-up launch (decideHere, finalizedEarly, min(eltBlocks, RN_FIXUP_BLOCKS) workgroups)
+ *          RN_DUALP_EXACT_SHARDED    the flat main pass, k_reduce_dist, the context's all-reduce where it has a communicator, k_decide_from, the fix-up
+ *                                    launch, k_finalize
+ *          RN_DUALP_OPTIMISTIC_CLOSE the main pass and k_finalize_optimistic (which sets the verdict flag)
+ *          RN_DUALP_INFO             launches nothing: fills the record's launch cells only
+ *          RN_DUALP_NEXT_W           launches nothing: wnext receives the buffer the next sweep would read as w
+ *   materialize: 1 = z and res are written too (the last iteration of a batch).  iteration = t: the extrapolation parameter is entry t + 1 of the context's
+ *   lambda table.  A combination the library never launches is RN_E_ARG: unscaled with materialize on a stage-tiled shape, unscaled in the exact forms.
+ * ynew, wnext, z, res [nodes][ny] (the context's interleaved rows: 2 nx xi columns, nu psi columns): uploaded before the launches and read back whole, so the
+ * caller's fill shows every element that was not written.  lo, hi [nodes][ny]: the materialised scaled bounds.  sqrtp [nodes], dy [N][ny], blo / bhi
+ * [bRows][ny], stageOf [nodes]: the tables the kernels rebuild the bounds from (any of these NULL: skipped).  partials [nPartials][8]: the raw partials of
+ * the main pass {d2x, d2s, absXi, valXi, absPsi, valPsi, idxXi, idxPsi} (an index that was never set reads -1); RN_E_ARG when the launch has more.
+ * info[RN_DUAL_INFO_COUNT]: [0] lambda, [1] 1 / lambda, [2] the extrapolation parameter, each as the kernel's type holds it; [3] [4] thrX, thrS; [5] [6] d2x,
+ * d2s: the fold of the main pass's partials (k_reduce_dist's, i.e. fold_partials'); [7] [8] distX, distS, [9] tripped, [10] [11] scaleX, scaleS, [12]
+ * violated, from the scratch iteration state; [13 .. 15] |.|, signed value and element index of the xi arg-max, [16 .. 18] of the psi one: value and |.| from the
+ * history parts the device wrote (MAIN: NaN), the index folded on the host from the partials of the pass that decided them; [19] the history entry (MAIN:
+ * NaN); [20] kernel: 1 k_dual_stage, 0 k_dual_fused; [21] grid; [22] trips; [23] pipe; [24] crownBlocks; [25] bps; [26] vpn; [27] cs; [28] K; [29] node0;
+ * [30] eltBlocks; [31] fix-up workgroups; [32] crownElems; [33] countCrown; [34] 1 = the SCALE instantiation ran; [35] [36] the bounds tables' strides per
+ * stage / per node; [37] rows of the bounds tables; [38] 1 = k_hx_scale ran in front; [39] the iteration counter of the scratch state afterwards.
+ * RN_E_STATE before the factor step and under global FBE / NAMA. */
+enum { RN_DUALP_MAIN = 0, RN_DUALP_EXACT = 1, RN_DUALP_EXACT_SHARDED = 2, RN_DUALP_OPTIMISTIC_CLOSE = 3, RN_DUALP_INFO = 4, RN_DUALP_NEXT_W = 5 };
+enum { RN_DUAL_INFO_COUNT = 40 };
+typedef struct {
+    int form, materialize, flat, unscaled, iteration;
+    double *ynew, *wnext, *z, *res;
+    double *lo, *hi;
+    double *sqrtp, *dy, *blo, *bhi;
+    int *stageOf;
+    double *partials;
+    size_t nPartials;
+} rn_dual_update_args;
+int rn_debug_dual_update(rn_ctx *ctx, const rn_dual_update_args *args, double info[RN_DUAL_INFO_COUNT]);
+
 #ifdef __cplusplus
 }
 #endif

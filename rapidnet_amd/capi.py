@@ -63,7 +63,7 @@ SYMBOLS = [
     "rn_debug_set_allreduce", "rn_debug_local_group_create", "rn_debug_local_group_join", "rn_debug_local_group_destroy",
     "rn_guard_check", "rn_device_memory_info", "rn_reserve_iterations", "rn_profile_read_collective", "rn_debug_inject_allocation", "rn_guard_report", "rn_debug_guard_poke",
     "rn_set_tree_data", "rn_set_tree_data_device", "rn_get_tree_data", "rn_set_bounds", "rn_set_bounds_device", "rn_get_bounds_layout", "rn_get_bounds", "rn_debug_cut_moments",
-    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live", "rn_debug_stream_units", "rn_debug_stream_product", "rn_debug_slab_product",
+    "rn_fbe_counters", "rn_peer_inbox_create", "rn_peer_inbox_connect", "rn_debug_peer_inbox_connect_local", "rn_debug_peer_seq", "rn_set_exchange_transport", "rn_exchange_autotune", "rn_set_fused_walk_dual", "rn_debug_set_knob", "rn_debug_stream_info", "rn_debug_restart_test", "rn_debug_stream_live", "rn_debug_stream_units", "rn_debug_stream_product", "rn_debug_slab_product", "rn_debug_dual_update",
     "rn_plan_report", "rn_plan_report_scenarios", "rn_plan_report_device",
     "rn_plan_quantiles", "rn_plan_quantiles_device", "rn_plan_paths",
     "rn_shift_warm_start", "rn_set_shift_map", "rn_get_shift_map",
@@ -263,6 +263,7 @@ def load():
     lib.rn_debug_stream_units.argtypes = [vp, dp]
     lib.rn_debug_stream_product.argtypes = [vp, C.c_int, dp, dp, dp]
     lib.rn_debug_slab_product.argtypes = [vp, vp, vp]
+    lib.rn_debug_dual_update.argtypes = [vp, vp, vp]
     lib.rn_profile_read_collective.argtypes = [vp, dp, dp]
     lib.rn_set_tree_data.argtypes = [vp, C.c_size_t, dp, dp, dp]
     lib.rn_set_tree_data_device.argtypes = [vp, C.c_size_t, ip, vp, vp, vp]
@@ -1062,6 +1063,44 @@ class Solver:
         d = dict(zip(self.SLAB_INFO, (int(v) for v in info)))
         d["kernel"], d["kernel2"] = self.SLAB_KERNELS[d["kernel"]], self.SLAB_KERNELS[d["kernel2"]]
         return outA, outB, d
+
+    DUAL_FORMS = {"main": 0, "exact": 1, "exact_sharded": 2, "optimistic_close": 3, "info": 4, "next_w": 5}
+    DUAL_INFO = ("lambda", "invLambda", "ln", "thrX", "thrS", "d2x", "d2s", "distX", "distS", "tripped", "scaleX", "scaleS", "violated", "absXi", "valXi", "idxXi",
+                 "absPsi", "valPsi", "idxPsi", "hist", "kernel", "grid", "trips", "pipe", "crownBlocks", "bps", "vpn", "cs", "K", "node0", "eltBlocks", "fixBlocks",
+                 "crownElems", "countCrown", "scale", "bStrideStage", "bStrideNode", "bRows", "preScale", "itAfter")
+
+    def debugDualUpdate(self, form="main", materialize=False, flat=False, unscaled=False, iteration=0, fill=7777.0, tables=False):
+        """rn_debug_dual_update (include/rapidnet_debug.h): the dual update of one iteration alone on the context's buffers as they stand (Hx =
+        BUF_PRIMAL_*, w = BUF_ACC_*, y = BUF_UPD_*), through the batch loop's own launch steps.  Returns (out, info): out["ynew"], ["wnext"], ["z"],
+        ["res"] are [nodes][ny] in the context's interleaved rows, pre-filled with `fill` (what was not written still holds it); out["partials"]
+        [grid][8] the raw partials of the main pass; tables=True adds lo, hi [nodes][ny], sqrtp, dy [N][ny], blo, bhi [bRows][ny], stageOf.  info: a dict
+        over DUAL_INFO (floats; "kernel" by name).  form "info" launches nothing (out holds the fills), "next_w" returns only out["wnext"]."""
+        class _Args(C.Structure):
+            _fields_ = [(n, C.c_int) for n in ("form", "materialize", "flat", "unscaled", "iteration")] + \
+                       [(n, C.c_void_p) for n in ("ynew", "wnext", "z", "res", "lo", "hi", "sqrtp", "dy", "blo", "bhi", "stageOf", "partials")] + [("nPartials", C.c_size_t)]
+        f = self.DUAL_FORMS[form]
+        shape = (self.nodes, self.ny)
+        info = np.zeros(len(self.DUAL_INFO))
+        if form == "next_w":
+            w = np.full(shape, float(fill))
+            a = _Args(f, 0, 0, 0, int(iteration), None, w.ctypes.data, *([None] * 10), 0)
+            self._check(self.lib.rn_debug_dual_update(self.h, C.addressof(a), info.ctypes.data))
+            return {"wnext": w}, None
+        a0 = _Args(self.DUAL_FORMS["info"], int(bool(materialize)), int(bool(flat)), int(bool(unscaled)), int(iteration), *([None] * 12), 0)
+        self._check(self.lib.rn_debug_dual_update(self.h, C.addressof(a0), info.ctypes.data))
+        d0 = dict(zip(self.DUAL_INFO, (float(v) for v in info)))
+        out = {k: np.full(shape, float(fill)) for k in ("ynew", "wnext", "z", "res")}
+        out["partials"] = np.full((int(d0["grid"]), 8), float(fill))
+        if tables:
+            out.update(lo=np.zeros(shape), hi=np.zeros(shape), sqrtp=np.zeros(self.nodes), dy=np.zeros((self.N, self.ny)), blo=np.zeros((int(d0["bRows"]), self.ny)),
+                       bhi=np.zeros((int(d0["bRows"]), self.ny)), stageOf=np.zeros(self.nodes, dtype=np.int32))
+        ptr = lambda k: out[k].ctypes.data if k in out else None
+        a = _Args(f, int(bool(materialize)), int(bool(flat)), int(bool(unscaled)), int(iteration), ptr("ynew"), ptr("wnext"), ptr("z"), ptr("res"), ptr("lo"), ptr("hi"),
+                  ptr("sqrtp"), ptr("dy"), ptr("blo"), ptr("bhi"), ptr("stageOf"), ptr("partials"), out["partials"].shape[0])
+        self._check(self.lib.rn_debug_dual_update(self.h, C.addressof(a), info.ctypes.data))
+        d = dict(zip(self.DUAL_INFO, (float(v) for v in info)))
+        d["kernel"] = "k_dual_stage" if d["kernel"] == 1 else "k_dual_fused"
+        return out, d
 
     def debugGuardPoke(self, nbytes):
         self._check(self.lib.rn_debug_guard_poke(self.h, int(nbytes)))

@@ -636,7 +636,7 @@ __global__ void __launch_bounds__(ELT_THREADS) k_prox_clamp(DualArgs<T> a) {
     double d2x = 0, d2s = 0;
     for (long long i = (long long)blockIdx.x * ELT_THREADS + threadIdx.x; i < a.n; i += (long long)gridDim.x * ELT_THREADS) {
         const int c = (int)(i % a.ny);
-        const T t = a.hx[i] + a.invLambda * a.w[i];
+        const T t = fma_rn(a.invLambda, a.w[i], a.hx[i]);   // dual_elem's t
         const T lo = a.lo[i], hi = a.hi[i];
         const T z = t < lo ? lo : (t > hi ? hi : t);
         a.z[i] = z;
@@ -660,15 +660,22 @@ __global__ void k_prox_soft(DualArgs<T> a) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long long)gridDim.x * blockDim.x) {
         const int c = (int)(i % a.ny);
         if (c >= 2 * a.nx) continue;
-        const T t = a.hx[i] + a.invLambda * a.w[i];
+        const T t = fma_rn(a.invLambda, a.w[i], a.hx[i]);   // dual_elem's t
         const T z = a.z[i];
-        a.z[i] = z + (c < a.nx ? scX : scS) * (t - z);
+        a.z[i] = fma_rn(c < a.nx ? scX : scS, t - z, z);   // dual_elem's fix-up of z
     }
 }
+// out = alpha x + beta y, the roundings spelled out as in dual_elem: beta y is fused into the sum, alpha x is rounded (the step-wise callers pass
+// alpha = +-1, so it is exact).  rn_dual_update (1, lambda) then stores fma(lambda, res, w), the fused kernels' y+, and rn_compute_fixed_point_residual
+// (1, -1) stores hx - z.  Left to the compiler's contraction this was fma(alpha, x, round(beta y)) in fp64 and round(alpha x) + round(beta y) in
+// fp32: y+ one ulp off the fused kernels' (tests/test_gpu_dual_update.py).
 template <typename T>
-__global__ void k_axpby(T *out, const T *x, const T *y, T alpha, T beta, long long n) {   // out = alpha x + beta y
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        out[i] = alpha * x[i] + beta * y[i];
+__global__ void k_axpby(T *out, const T *x, const T *y, T alpha, T beta, long long n) {
+#pragma clang fp contract(off)
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const T ax = alpha * x[i];
+        out[i] = fma_rn(beta, y[i], ax);
+    }
 }
 // arg-max |res| partials for rn_update_primal_infeasibility (SmpcController.cu:1480-1496)
 template <typename T>

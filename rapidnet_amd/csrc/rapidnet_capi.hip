@@ -184,6 +184,7 @@ struct CtxBase {
     virtual int stream_live(long long *) = 0;
     virtual int stream_units(long long *) = 0;
     virtual int stream_product(int, double *, double *, double *) = 0;
+    virtual int dual_update_alone(const rn_dual_update_args *, double *) = 0;
     virtual int slab_product(const rn_slab_product_args *, int *) = 0;
     virtual int synchronize() = 0;
     virtual void *stream_handle() = 0;
@@ -473,10 +474,10 @@ struct Ctx : CtxBase {
         if (k == RN_KNOB_DUAL_TRIPS || k == RN_KNOB_DUAL_PIPE) dual_stage_setup();
         return RN_OK;
     }
-    void hx_scale_now() {        // (safety net: a consumer of Hx other than k_dual_stage SCALE behind an unscaled walk)
+    void hx_scale_now(T *hx) {   // (safety net: a consumer of Hx other than k_dual_stage SCALE behind an unscaled walk)
         const long long total = ntot();
         const int blocks = (int)std::min<long long>((total + ELT_THREADS - 1) / ELT_THREADS, (long long)numCUs * 16);
-        hipLaunchKernelGGL(k_hx_scale<>, dim3(blocks), dim3(ELT_THREADS), 0, stream, (void *)d_hx, (const void *)d_sqrtp, (const void *)d_dy, (const int *)d_stageOf, ny, total,
+        hipLaunchKernelGGL(k_hx_scale<>, dim3(blocks), dim3(ELT_THREADS), 0, stream, (void *)hx, (const void *)d_sqrtp, (const void *)d_dy, (const int *)d_stageOf, ny, total,
                            sizeof(T) == 8 ? 1 : 0);
     }
     T *d_lo = nullptr, *d_hi = nullptr, *d_z = nullptr, *d_res = nullptr;
@@ -1386,21 +1387,13 @@ struct Ctx : CtxBase {
             else {
                 hipEvent_t e3 = prof_begin(3);
                 if (b.optimistic) {   // the batch's last bookkeeping gets a launch of its own
-                    hipLaunchKernelGGL(k_finalize_optimistic<T>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, main_partials(), d_state, tail, d_hist, d_histParts,
-                                       histCap, b.sharded ? -1.0 : penX / stepSize, b.sharded ? -1.0 : penXs / stepSize,
-                                       first, b.sharded ? -1 : (recTol >= 0 ? n : 0), recTol, b.sharded ? nullptr : h_rec);
+                    run_close_optimistic(a, main_partials(), tail, b.sharded, first, recTol >= 0 ? n : 0, recTol, h_rec);
                 } else if (b.sharded) {   // tree-global distances: sum the ranks' dist^2 (2 doubles) before deciding
-                    hipLaunchKernelGGL(k_reduce_dist<>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, eltBlocks, d_dist2);
-                    if (int rc = all_reduce(d_dist2, 2, true, "ncclAllReduce(dist)")) return fail_batch(rc);
-                    hipLaunchKernelGGL(k_decide_from<>, dim3(1), dim3(1), 0, stream, d_dist2, d_state, a.thrX, a.thrS);
-                    hipLaunchKernelGGL(dual_fused_kernel(last, true), dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, a);
-                    hipLaunchKernelGGL(k_finalize<>, dim3(1), dim3(ELT_THREADS), 0, stream, d_partials, eltBlocks, d_state, d_hist, d_histParts, histCap);
+                    if (int rc = run_close_exact_sharded(a, last, d_dist2)) return fail_batch(rc);
                 } else {   // single GPU: the (small) fix-up launch also decides and does the bookkeeping (kernels.hpp, decideHere)
-                    a.finalizedEarly = 1;
-                    a.decideHere = 1; a.itHost = h_it; a.nMain = main_partials(); a.mainPartials = d_partials; a.partials = d_partials2;
+                    a = exact_fixup_args(a, h_it, main_partials(), d_partials2);
                     if (last && recTol >= 0) { a.recFirst = first; a.recN = n; a.recTol = recTol; a.hostRec = h_rec; }   // the launch that closes the batch
-                    const int fixBlocks = std::min(eltBlocks, RN_FIXUP_BLOCKS);
-                    hipLaunchKernelGGL(dual_fused_kernel(last, true), dim3(fixBlocks), dim3(ELT_THREADS), 0, stream, a);
+                    run_exact_fixup(a, last);
                 }
                 prof_end(e3);
             }
@@ -1958,6 +1951,142 @@ struct Ctx : CtxBase {
         if (int rc = download(my, d_my, (size_t)d.nodes * 2 * d.nv)) return rc;
         if (my2) { if (int rc = download(my2, d_my2, (size_t)(d.nodes - a.splitFirst) * 2 * d.nv)) return rc; }
         if (pair) { if (int rc = download(myB, d_myB, (size_t)d.nodes * 2 * d.nv)) return rc; }
+        return RN_OK;
+    }
+    // rn_debug_dual_update (include/rapidnet_debug.h): the dual update of one iteration alone, through the batch loop's own launch steps (sweep.inc),
+    // with outputs, partials, iteration state and history slot in scratch of the hook's own
+    struct DualScratch { T *yn = nullptr, *wn = nullptr, *z = nullptr, *res = nullptr, *hx = nullptr; Partial *parts = nullptr, *parts2 = nullptr;
+                         IterState *st = nullptr; double *hist = nullptr, *dist2 = nullptr; bool ready = false; };
+    DualScratch dsx;
+    int dual_scratch() {
+        if (dsx.ready) return RN_OK;
+        const size_t n = (size_t)ntot();
+        if (int rc = dalloc(&dsx.yn, n)) return rc;
+        if (int rc = dalloc(&dsx.wn, n)) return rc;
+        if (int rc = dalloc(&dsx.z, n)) return rc;
+        if (int rc = dalloc(&dsx.res, n)) return rc;
+        if (int rc = dalloc(&dsx.hx, n)) return rc;
+        if (int rc = dalloc(&dsx.parts, (size_t)std::max(ELT_MAX_BLOCKS, RN_DUAL_STAGE_MAX_BLOCKS))) return rc;
+        if (int rc = dalloc(&dsx.parts2, (size_t)ELT_MAX_BLOCKS)) return rc;
+        if (int rc = dalloc(&dsx.st, 1)) return rc;
+        if (int rc = dalloc(&dsx.hist, 5)) return rc;      // the history entry and its four parts
+        if (int rc = dalloc(&dsx.dist2, 2)) return rc;
+        dsx.ready = true;
+        return RN_OK;
+    }
+    int dual_update_alone(const rn_dual_update_args *p, double *info) override {
+        RN_CHECK(p && info, RN_E_ARG, "rn_debug_dual_update: null arguments");
+        RN_CHECK(factored && d_hx && p_acc_view && p_upd, RN_E_STATE, "rn_debug_dual_update before the factor step");
+        RN_CHECK(algorithm == RN_ALG_APG, RN_E_STATE, "rn_debug_dual_update: the dual update of global FBE / NAMA is another one (fbe_methods.inc)");
+        RN_CHECK(!poisoned, RN_E_STATE, "rn_debug_dual_update: an earlier batch failed half-way; call rn_apg_reset first");
+        RN_CHECK(p->form >= RN_DUALP_MAIN && p->form <= RN_DUALP_NEXT_W, RN_E_ARG, "rn_debug_dual_update: unknown form");
+        RN_CHECK(p->iteration >= 0 && p->iteration < (1 << 24), RN_E_ARG, "rn_debug_dual_update: iteration out of range");
+        RN_HIP(hipSetDevice(device));
+        const size_t n = (size_t)ntot();
+        if (p->form == RN_DUALP_NEXT_W) {
+            RN_CHECK(p->wnext, RN_E_ARG, "rn_debug_dual_update: NEXT_W needs wnext");
+            RN_CHECK(acc_ready, RN_E_STATE, "rn_debug_dual_update: the next sweep would re-derive w (the iterates were edited)");
+            return download(p->wnext, p_acc, n);
+        }
+        const bool launches = p->form != RN_DUALP_INFO;
+        const bool mat = p->materialize != 0, unscaled = p->unscaled != 0, sharded = p->form == RN_DUALP_EXACT_SHARDED;
+        const bool exact = p->form == RN_DUALP_EXACT || sharded;
+        // the flat kernel: where the shape is not eligible, on request, and in the exact sharded form (whose fix-up and k_finalize fold eltBlocks partials)
+        const bool flat = dualU == 0 || p->flat != 0 || sharded;
+        RN_CHECK(!(unscaled && exact), RN_E_ARG, "rn_debug_dual_update: only optimistic batches walk unscaled; an exact form never meets an unscaled Hx");
+        RN_CHECK(!(unscaled && mat && !flat), RN_E_ARG, "rn_debug_dual_update: k_dual_stage has no instantiation with SCALE and MATERIALIZE (the batch's last sweep walks scaled)");
+        RN_CHECK(!launches || (p->ynew && p->wnext), RN_E_ARG, "rn_debug_dual_update: ynew and wnext are required");
+        RN_CHECK(!launches || !mat || (p->z && p->res), RN_E_ARG, "rn_debug_dual_update: a materialising pass needs z and res");
+        const int t = p->iteration;
+        if (int rc = ensure_tables(t + 1)) return rc;
+        if (int rc = dual_scratch()) return rc;
+        DualArgs<T> a = dual_args();
+        a.w = p_acc_view;
+        a.ynew = dsx.yn; a.wnext = dsx.wn; a.z = dsx.z; a.res = dsx.res;
+        a.st = dsx.st; a.partials = dsx.parts;
+        // the kernels index the history and the lambda table by iteration: slot t of both views is the hook's scratch entry / the table's entry t
+        a.lamNext = d_lam; a.hist = dsx.hist - t; a.histParts = dsx.hist + 1 - 4 * (ptrdiff_t)t; a.histCap = t + 1;
+        const DualMainLaunch m = dual_main_args(flat, unscaled, mat, h_lam[t + 1]);
+        RN_CHECK(!p->partials || !launches || p->nPartials >= (size_t)m.blocks, RN_E_ARG, "rn_debug_dual_update: the main pass leaves more partials than the caller's array holds");
+        const DualArgs<T> fx = exact_fixup_args(a, t, m.blocks, dsx.parts2);
+        for (int i = 0; i < RN_DUAL_INFO_COUNT; i++) info[i] = 0.0;
+        info[0] = (double)a.lambda; info[1] = (double)a.invLambda; info[2] = (double)(T)h_lam[t + 1]; info[3] = a.thrX; info[4] = a.thrS;
+        for (int i = 5; i < 20; i++) info[i] = std::nan("");
+        info[20] = flat ? 0 : 1; info[21] = m.blocks; info[22] = flat ? 0 : m.g.trips; info[23] = m.pipe; info[24] = flat ? 0 : m.g.crownBlocks;
+        info[25] = flat ? 0 : m.g.bps; info[26] = flat ? 0 : m.g.vpn; info[27] = flat ? 0 : m.g.cs; info[28] = flat ? 0 : m.g.K; info[29] = flat ? 0 : m.g.node0;
+        info[30] = eltBlocks; info[31] = exact_fixup_blocks(); info[32] = a.crownElems; info[33] = a.countCrown; info[34] = m.scale ? 1 : 0;
+        info[35] = a.bStrideStage; info[36] = a.bStrideNode; info[37] = (double)bounds_rows(boundsGran); info[38] = m.preScale ? 1 : 0;
+        if (p->lo) { if (int rc = download(p->lo, d_lo, n)) return rc; }
+        if (p->hi) { if (int rc = download(p->hi, d_hi, n)) return rc; }
+        if (p->sqrtp) { if (int rc = download(p->sqrtp, d_sqrtp, (size_t)d.nodes)) return rc; }
+        if (p->dy) { if (int rc = download(p->dy, d_dy, (size_t)d.N * ny)) return rc; }
+        if (p->blo) { if (int rc = download(p->blo, d_blo, bounds_rows(boundsGran) * ny)) return rc; }
+        if (p->bhi) { if (int rc = download(p->bhi, d_bhi, bounds_rows(boundsGran) * ny)) return rc; }
+        if (p->stageOf) RN_HIP(hipMemcpy(p->stageOf, d_stageOf, (size_t)d.nodes * sizeof(int), hipMemcpyDeviceToHost));
+        if (!launches) return RN_OK;
+        // the caller's fill under the outputs, the scratch state at iteration t
+        if (int rc = upload(dsx.yn, p->ynew, n)) return rc;
+        if (int rc = upload(dsx.wn, p->wnext, n)) return rc;
+        if (p->z) { if (int rc = upload(dsx.z, p->z, n)) return rc; }
+        if (p->res) { if (int rc = upload(dsx.res, p->res, n)) return rc; }
+        IterState st0{};
+        st0.it = t;
+        RN_HIP(hipMemcpyAsync(dsx.st, &st0, sizeof st0, hipMemcpyHostToDevice, stream));
+        const double nanv = std::nan("");
+        const double h0[5] = {nanv, nanv, nanv, nanv, nanv};
+        RN_HIP(hipMemcpyAsync(dsx.hist, h0, sizeof h0, hipMemcpyHostToDevice, stream));
+        RN_HIP(hipStreamSynchronize(stream));   // (st0, h0 are locals)
+        if (m.preScale) {   // as hx_scale_now in launch_dual_main, on a copy: the context's Hx stays what it is
+            RN_HIP(hipMemcpyAsync(dsx.hx, d_hx, n * sizeof(T), hipMemcpyDeviceToDevice, stream));
+            hx_scale_now(dsx.hx);
+            a.hx = dsx.hx;
+        }
+        run_dual_main(m, a, mat);
+        // (the fold the record reports: fold_partials over the main pass's partials, into scratch; reads only)
+        hipLaunchKernelGGL(k_reduce_dist<>, dim3(1), dim3(ELT_THREADS), 0, stream, (const Partial *)dsx.parts, m.blocks, dsx.dist2);
+        double d2main[2] = {0, 0};
+        RN_HIP(hipMemcpyAsync(d2main, dsx.dist2, sizeof d2main, hipMemcpyDeviceToHost, stream));
+        if (p->form == RN_DUALP_EXACT) run_exact_fixup(fx, mat);
+        else if (sharded) { if (int rc = run_close_exact_sharded(a, mat, dsx.dist2)) return rc; }
+        else if (p->form == RN_DUALP_OPTIMISTIC_CLOSE) run_close_optimistic(a, m.blocks, nullptr, false, 0, -1, -1.0, nullptr);
+        RN_HIP(hipGetLastError());
+        IterState st1{};
+        double h1[5];
+        std::vector<Partial> hp((size_t)m.blocks), hp2;
+        RN_HIP(hipMemcpyAsync(&st1, dsx.st, sizeof st1, hipMemcpyDeviceToHost, stream));
+        RN_HIP(hipMemcpyAsync(h1, dsx.hist, sizeof h1, hipMemcpyDeviceToHost, stream));
+        RN_HIP(hipMemcpyAsync(hp.data(), dsx.parts, hp.size() * sizeof(Partial), hipMemcpyDeviceToHost, stream));
+        RN_HIP(hipStreamSynchronize(stream));
+        info[5] = d2main[0]; info[6] = d2main[1];
+        if (p->form != RN_DUALP_MAIN) { info[7] = st1.distX; info[8] = st1.distS; info[9] = st1.tripped; info[10] = st1.scaleX; info[11] = st1.scaleS; }
+        info[12] = st1.violated; info[39] = st1.it;
+        // which partials decided the arg-max: the fix-up's when it ran to the end (EXACT: its own array; EXACT_SHARDED: it overwrote the main pass's, read
+        // back above, so the raw main partials the caller gets are then the fix-up's -- the sharded form has one array, as in the batch loop)
+        const std::vector<Partial> *dec = &hp;
+        if (p->form == RN_DUALP_EXACT && st1.tripped) {
+            hp2.resize((size_t)exact_fixup_blocks());
+            RN_HIP(hipMemcpy(hp2.data(), dsx.parts2, hp2.size() * sizeof(Partial), hipMemcpyDeviceToHost));
+            dec = &hp2;
+        }
+        double aX = -1, aP = -1; long long iX = 0x7fffffffffffffffLL, iP = iX;
+        for (const Partial &q : *dec) {
+            if (q.absXi > aX || (q.absXi == aX && q.idxXi < iX)) { aX = q.absXi; iX = q.idxXi; }
+            if (q.absPsi > aP || (q.absPsi == aP && q.idxPsi < iP)) { aP = q.absPsi; iP = q.idxPsi; }
+        }
+        info[13] = h1[1]; info[14] = h1[2]; info[15] = iX == 0x7fffffffffffffffLL ? -1.0 : (double)iX;
+        info[16] = h1[3]; info[17] = h1[4]; info[18] = iP == 0x7fffffffffffffffLL ? -1.0 : (double)iP;
+        info[19] = h1[0];
+        if (p->partials)
+            for (size_t b = 0; b < hp.size(); b++) {
+                const Partial &q = hp[b];
+                double *o = p->partials + 8 * b;
+                o[0] = q.d2x; o[1] = q.d2s; o[2] = q.absXi; o[3] = q.valXi; o[4] = q.absPsi; o[5] = q.valPsi;
+                o[6] = q.idxXi == 0x7fffffffffffffffLL ? -1.0 : (double)q.idxXi; o[7] = q.idxPsi == 0x7fffffffffffffffLL ? -1.0 : (double)q.idxPsi;
+            }
+        if (int rc = download(p->ynew, dsx.yn, n)) return rc;
+        if (int rc = download(p->wnext, dsx.wn, n)) return rc;
+        if (p->z) { if (int rc = download(p->z, dsx.z, n)) return rc; }
+        if (p->res) { if (int rc = download(p->res, dsx.res, n)) return rc; }
         return RN_OK;
     }
     // rn_debug_slab_product (include/rapidnet_debug.h): one launch step of the shared-operator products (sweep.inc: run_v_lv, run_comp, run_prep_m2,
@@ -2729,6 +2858,7 @@ int rn_debug_stream_live(rn_ctx *ctx, long long out[4]) { RN_GUARD(ctx); return 
 int rn_debug_stream_units(rn_ctx *ctx, long long out[3]) { RN_GUARD(ctx); return ctx->impl->stream_units(out); }
 int rn_debug_stream_product(rn_ctx *ctx, int pair, double *my, double *my2, double *myB) { RN_GUARD(ctx); return ctx->impl->stream_product(pair, my, my2, myB); }
 int rn_debug_slab_product(rn_ctx *ctx, const rn_slab_product_args *args, int *info) { RN_GUARD(ctx); return ctx->impl->slab_product(args, info); }
+int rn_debug_dual_update(rn_ctx *ctx, const rn_dual_update_args *args, double info[RN_DUAL_INFO_COUNT]) { RN_GUARD(ctx); return ctx->impl->dual_update_alone(args, info); }
 int rn_debug_restart_test(rn_ctx *ctx, double out[3]) { RN_GUARD(ctx); return ctx->impl->debug_restart_test(out); }
 int rn_debug_peer_seq(rn_ctx *ctx, unsigned int seq) { RN_GUARD(ctx); return ctx->impl->debug_peer_seq(seq); }
 int rn_guard_report(long out[2]) { if (!out) return RN_E_ARG; out[0] = rn::g_guardContexts.load(); out[1] = rn::g_guardBadBytes.load(); return RN_OK; }

@@ -756,17 +756,63 @@
         if (materialize) return pipe == 1 ? k_dual_stage<T, true, 1> : k_dual_stage<T, true, 2>;
         return pipe == 1 ? k_dual_stage<T, false, 1> : k_dual_stage<T, false, 2>;
     }
-    void launch_dual_main(Batch &b, const DualArgs<T> &a, bool materialize) {
-        const bool hxUnscaled = std::exchange(b.hxUnscaled, false);
-        const bool flat = dual_main_flat(b.optimistic);
-        const bool scale = hxUnscaled && !materialize && !flat;      // unscaled walk: k_dual_stage SCALE forms Hx; every other consumer gets it scaled first
-        if (hxUnscaled && !scale) hx_scale_now();
-        mainPartials = flat ? eltBlocks : dualBlocks;
-        if (flat) {
-            hipLaunchKernelGGL(dual_fused_kernel(materialize, false), dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, a);
+    // "build the arguments" / "launch them", as v_lv_args / run_v_lv: what the main pass of ONE iteration is -- which kernel, how many workgroups
+    // (= partials), whether Hx has to be scaled in front -- and the launch of exactly that.  run_batch (launch_dual_main) and rn_debug_dual_update
+    // go through the same two steps.
+    struct DualMainLaunch {
+        bool flat, scale, preScale;   // k_dual_fused / k_dual_stage; SCALE instantiation; k_hx_scale in front (unscaled Hx that SCALE cannot take)
+        int blocks, pipe;
+        DualStageShape g;             // (stage-tiled only; lnNext filled in)
+    };
+    DualMainLaunch dual_main_args(bool flat, bool hxUnscaled, bool materialize, double lnNext) const {
+        DualMainLaunch m{};
+        m.flat = flat;
+        m.scale = hxUnscaled && !materialize && !flat;      // unscaled walk: k_dual_stage SCALE forms Hx; every other consumer gets it scaled first
+        m.preScale = hxUnscaled && !m.scale;
+        m.blocks = flat ? eltBlocks : dualBlocks;
+        m.pipe = flat ? 0 : dualU;
+        if (!flat) { m.g = dshape; m.g.lnNext = lnNext; }
+        return m;
+    }
+    void run_dual_main(const DualMainLaunch &m, const DualArgs<T> &a, bool materialize) {
+        if (m.flat) {
+            hipLaunchKernelGGL(dual_fused_kernel(materialize, false), dim3(m.blocks), dim3(ELT_THREADS), 0, stream, a);
             return;
         }
-        DualStageShape g = dshape;
-        g.lnNext = h_lam[h_it + 1 - lamBase];   // ensure_tables(h_it + n) has run: the table covers every iteration of the batch
-        hipLaunchKernelGGL(dual_stage_kernel(materialize, dualU, scale), dim3(dualBlocks), dim3(ELT_THREADS), 0, stream, a, g);
+        hipLaunchKernelGGL(dual_stage_kernel(materialize, m.pipe, m.scale), dim3(m.blocks), dim3(ELT_THREADS), 0, stream, a, m.g);
+    }
+    void launch_dual_main(Batch &b, const DualArgs<T> &a, bool materialize) {
+        const bool hxUnscaled = std::exchange(b.hxUnscaled, false);
+        // ensure_tables(h_it + n) has run: the table covers every iteration of the batch
+        const DualMainLaunch m = dual_main_args(dual_main_flat(b.optimistic), hxUnscaled, materialize, h_lam[h_it + 1 - lamBase]);
+        if (m.preScale) hx_scale_now(d_hx);
+        mainPartials = m.blocks;
+        run_dual_main(m, a, materialize);
+    }
+    // The bookkeeping of an iteration that gets launches of its own, in the three forms run_batch knows (the fourth rides in the next sweep: FinArgs).
+    // Everything they touch arrives in the DualArgs (state, partials, history) and in the parameters: rn_debug_dual_update hands them scratch.
+    // optimistic: fold, history entry, distance check into the verdict flag (single GPU) or the dist^2 into the cut payload's tail (sharded)
+    void run_close_optimistic(const DualArgs<T> &a, int nMain, T *tail, bool sharded, int recFirst, int recN, double recTol, BatchRecord *hostRec) {
+        hipLaunchKernelGGL(k_finalize_optimistic<T>, dim3(1), dim3(ELT_THREADS), 0, stream, (const Partial *)a.partials, nMain, a.st, tail, a.hist, a.histParts,
+                           a.histCap, sharded ? -1.0 : a.thrX, sharded ? -1.0 : a.thrS, recFirst, sharded ? -1 : recN, recTol, sharded ? nullptr : hostRec);
+    }
+    // exact, sharded: tree-global distances -- sum the ranks' dist^2 (2 doubles) before deciding; the flat fix-up pass; the history entry
+    int run_close_exact_sharded(const DualArgs<T> &a, bool materialize, double *dist2) {
+        hipLaunchKernelGGL(k_reduce_dist<>, dim3(1), dim3(ELT_THREADS), 0, stream, (const Partial *)a.partials, eltBlocks, dist2);
+        if (has_comm()) { if (int rc = all_reduce(dist2, 2, true, "ncclAllReduce(dist)")) return rc; }
+        hipLaunchKernelGGL(k_decide_from<>, dim3(1), dim3(1), 0, stream, (const double *)dist2, a.st, a.thrX, a.thrS);
+        hipLaunchKernelGGL(dual_fused_kernel(materialize, true), dim3(eltBlocks), dim3(ELT_THREADS), 0, stream, a);
+        hipLaunchKernelGGL(k_finalize<>, dim3(1), dim3(ELT_THREADS), 0, stream, (const Partial *)a.partials, eltBlocks, a.st, a.hist, a.histParts, a.histCap);
+        return RN_OK;
+    }
+    // exact, single GPU: the (small) fix-up launch also decides and does the bookkeeping (k_dual.hpp, decideHere).  The arguments first -- the
+    // caller may add a batch record to them -- then the launch.
+    DualArgs<T> exact_fixup_args(DualArgs<T> a, int itHost, int nMain, Partial *fixPartials) const {
+        a.finalizedEarly = 1;
+        a.decideHere = 1; a.itHost = itHost; a.nMain = nMain; a.mainPartials = a.partials; a.partials = fixPartials;
+        return a;
+    }
+    int exact_fixup_blocks() const { return std::min(eltBlocks, RN_FIXUP_BLOCKS); }
+    void run_exact_fixup(const DualArgs<T> &a, bool materialize) {
+        hipLaunchKernelGGL(dual_fused_kernel(materialize, true), dim3(exact_fixup_blocks()), dim3(ELT_THREADS), 0, stream, a);
     }

@@ -165,6 +165,15 @@ def test_slab_products_under_guard(guard):
     guard["contexts"] = slp.guard_body()
 
 
+def test_dual_update_hook_under_guard(guard):
+    """rn_debug_dual_update's scratch outputs, partials, iteration state and history slot between red zones (tests/test_gpu_dual_update.py): the
+    stage-tiled kernel's partial last tile of two vectors and its idle trips, the flat kernel's scalar tail, the fix-up launch and the bookkeeping
+    kernels writing into the hook's own state -- payloads start as NaN, so a read of something nobody wrote shows in the exact comparisons"""
+    import test_gpu_dual_update as du
+
+    guard["contexts"] = du.guard_body()
+
+
 def test_barcelona31_under_guard(guard):
     """The full-size K = 31 Barcelona config: the kernel instantiations and launch shapes of the headline workload (G = 8 spans,
     two slots per thread, pipelined slab products, k_dual_stage tiles)."""
